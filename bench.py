@@ -6,6 +6,11 @@ Contract (one JSON line on rank 0):
                                                           child processes, one per GPU - launch_ranks)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (N > 1 under a launcher: the same ranks)
 
+A plain run sets up, warms up, times the --steps steps and prints the line (value, ms_per_step, ...).  Everything else the
+benchmark measures or checks - recall@10 / parity against the oracle, the CPU baseline, the sustained leg, the search
+statistics, the roofline with its measured ceiling and power, the exchange of a sharded run - runs only with --full.
+--dump-outputs DIR writes what the timed path returned in its last timed step as DIR/<name>.npy (dump_outputs).
+
 Workload (BASELINE.json): configs[2] "10M x 768 bf16 corpus, batch-256 queries" - the shape the
 north-star target is quoted on; it fits one GPU (15.36 GB).  One step = one batch of 256 queries
 searched against the whole corpus (inputs resident in HBM).  With N > 1 the SAME corpus is
@@ -321,6 +326,30 @@ def rehearse_launch(args, real_stdout):
     dist.destroy_process_group()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """`--dump-outputs DIR`: one DIR/<name>.npy per array the timed path handed its caller in the last timed step, floats as
+    float32 / float64 and integers as float64 (exact below 2**53).  Arrays share their leading (query) axis; should they
+    come to more than 64 MB, the same fixed, seeded sample of rows is kept from each and its row numbers go to
+    DIR/sample_rows.npy."""
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = a.astype(np.float32 if a.dtype in (np.float32, np.float16) else np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = next(iter(out.values())).shape[0]
+        keep = max(1, int(DUMP_LIMIT_BYTES // (total / n + 8)))          # + 8: the row number itself
+        rows = np.sort(np.random.default_rng(2024).choice(n, keep, replace=False))
+        out = {name: a[rows] for name, a in out.items()}
+        out["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
+
+
 def run_c1(args, real_stdout):
     """BASELINE.json configs[0]: `evaluate_retrieval` (compare_embeddings.py:55-92) on ~1k theorems and 73 queries - the
     [Q x N] cosine matrix and the six metrics, end to end.  The reference runs this on the host (numpy / torch-CPU); this
@@ -365,22 +394,31 @@ def run_c1(args, real_stdout):
     for _ in range(args.steps):
         report = step()
     dt = time.perf_counter() - t0
-    # the checker: the oracle's restatement of the reference's own functions on the same embeddings
-    sim = oracle.cos_sim(q_emb, s_emb)
-    want = {"P@1": oracle.precision_at_k(sim, qrels, k=1), "H@3": oracle.hit_at_k(sim, qrels, k=3), "MRR@3": oracle.mrr_at_k(sim, qrels, k=3),
-            "nDCG@3": oracle.ndcg_at_k(sim, qrels, k=3), "ERR@3": oracle.err_at_k(sim, qrels, k=3),
-            "Q-measure@3": oracle.q_measure_at_k(sim, qrels, k=3)}
     got = {ln.split(" | ")[0]: float(ln.split(" | ")[1]) for ln in report.splitlines() if " | " in ln}
-    viol = [k_ for k_, v in want.items() if abs(got.get(k_, float("nan")) - v) > 1e-9]
-    t1 = time.perf_counter()
-    reps = 0
-    while time.perf_counter() - t1 < 3.0 or reps < 3:
+    if args.dump_outputs:
+        # what the call hands back: its report's six metrics, in the report's order
+        dump_outputs(args.dump_outputs, {"metrics": np.array(list(got.values()), dtype=np.float64)})
+    parity = cpu_baseline = None
+    if args.full:
+        # the checker: the oracle's restatement of the reference's own functions on the same embeddings
         sim = oracle.cos_sim(q_emb, s_emb)
-        for fn, kk in ((oracle.precision_at_k, 1), (oracle.hit_at_k, 3), (oracle.mrr_at_k, 3), (oracle.ndcg_at_k, 3),
-                       (oracle.err_at_k, 3), (oracle.q_measure_at_k, 3)):
-            fn(sim, qrels, k=kk)
-        reps += 1
-    t_cpu = (time.perf_counter() - t1) / reps
+        want = {"P@1": oracle.precision_at_k(sim, qrels, k=1), "H@3": oracle.hit_at_k(sim, qrels, k=3), "MRR@3": oracle.mrr_at_k(sim, qrels, k=3),
+                "nDCG@3": oracle.ndcg_at_k(sim, qrels, k=3), "ERR@3": oracle.err_at_k(sim, qrels, k=3),
+                "Q-measure@3": oracle.q_measure_at_k(sim, qrels, k=3)}
+        viol = [k_ for k_, v in want.items() if abs(got.get(k_, float("nan")) - v) > 1e-9]
+        parity = {"metrics_checked": len(want), "violations": len(viol), "tolerance": 1e-9, "metrics": got}
+        t1 = time.perf_counter()
+        reps = 0
+        while time.perf_counter() - t1 < 3.0 or reps < 3:
+            sim = oracle.cos_sim(q_emb, s_emb)
+            for fn, kk in ((oracle.precision_at_k, 1), (oracle.hit_at_k, 3), (oracle.mrr_at_k, 3), (oracle.ndcg_at_k, 3),
+                           (oracle.err_at_k, 3), (oracle.q_measure_at_k, 3)):
+                fn(sim, qrels, k=kk)
+            reps += 1
+        t_cpu = (time.perf_counter() - t1) / reps
+        cpu_baseline = {"value": round(nq / t_cpu, 1), "unit": "queries/s", "cores": 1, "kind": "port",
+                        "sample": f"the oracle's restatement of the reference formulation (numpy cos_sim + six full argsorts, "
+                                  f"compare_embeddings.py:61-92) on the same embeddings, {reps} repetitions, {t_cpu * 1e3:.2f} ms each, one core"}
     line = {
         "metric": "queries/sec, evaluate_retrieval (cosine matrix + six retrieval metrics) over N x 768 theorem embeddings",
         "value": round(nq * args.steps / dt, 1), "unit": "queries/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -389,11 +427,10 @@ def run_c1(args, real_stdout):
         "config": {"workload": f"compare_embeddings.evaluate_retrieval on {n} theorems x {nq} queries, d = {D}, six metrics at k = 3 "
                                "(BASELINE.json configs[0]); runs through libtsearch on the GPU: the product has no CPU compute path",
                    "rows": n, "dim": D, "batch": nq, "k": 3},
-        "parity": {"metrics_checked": len(want), "violations": len(viol), "tolerance": 1e-9, "metrics": got},
+        "full": args.full,
+        "parity": parity,
         "roofline": None,
-        "cpu_baseline": {"value": round(nq / t_cpu, 1), "unit": "queries/s", "cores": 1, "kind": "port",
-                         "sample": f"the oracle's restatement of the reference formulation (numpy cos_sim + six full argsorts, "
-                                   f"compare_embeddings.py:61-92) on the same embeddings, {reps} repetitions, {t_cpu * 1e3:.2f} ms each, one core"},
+        "cpu_baseline": cpu_baseline,
     }
     os.write(real_stdout, (json.dumps(line) + "\n").encode())
 
@@ -442,8 +479,8 @@ def main():
                     help="searches in flight: the timed loop alternates this many handles on the same rows (the index and "
                          "views of it, ts_index_view), each on its own stream, so that the small kernels at the head of "
                          "step i + 1 overlap the tail of step i (independent batches back to back, streamlit_app.py:165-173); "
-                         "1 = one handle, one stream (default: measured on one box, two in flight gain 0.0 % on the 10M corpus and "
-                         "2 % on an eighth of it - the full pass holds every CU, so the small kernels of the other search "
+                         "1 = one handle, one stream (default: measured on one box, two in flight gain 0.0 %% on the 10M corpus and "
+                         "2 %% on an eighth of it - the full pass holds every CU, so the small kernels of the other search "
                          "only move, they do not hide - and the event brackets of overlapping passes stop being kernel time)")
     ap.add_argument("--encoder-graph", action="store_true",
                     help="c5: capture the encoder forward in a HIP graph per stream and replay it every step (default: eager "
@@ -464,7 +501,17 @@ def main():
                          "search (rehearse_launch); prints what was exercised, not a benchmark line")
     ap.add_argument("--zero-queries", action="store_true", help="diagnostic: all-zero queries (power probe)")
     ap.add_argument("--zero-corpus", action="store_true", help="diagnostic: all-zero corpus (power probe)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg the headline figure does not need: recall@10 / parity against the oracle, the CPU "
+                         "baseline, the sustained leg, the search statistics, the roofline (measured ceiling, power, traffic) and "
+                         "the exchange measurement of a sharded run (default: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy: "
+                         "scores (float32) and indices (float64) of the top-k, [batch x k]; c1: metrics (float64, the six "
+                         "values of evaluate_retrieval's report in its order)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     global D
     D = args.dim or (1024 if (args.workload == "c3q" or (args.workload == "c5" and args.encoder == "qwen")) else 768)
     if args.workload != "c1" and args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -537,7 +584,7 @@ def main():
         data = synthetic.synth_chunk(c, CH, D, bf16=bf16) if not args.zero_corpus else np.zeros((CH, D), np.uint16 if bf16 else np.float32)
         a, b = max(lo, c * CH), min(hi, (c + 1) * CH)
         ix.upload(data[a - c * CH:b - c * CH], a - lo)
-        if cache_ok or (c == 0 and rank == 0):
+        if args.full and (cache_ok or (c == 0 and rank == 0)):
             cache[c] = data
         return c
 
@@ -741,6 +788,19 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     qps = nq * args.steps / dt
 
+    def read_results():
+        """Scores and indices [nq x K] of the last step that ran, on the host (every rank holds the merged answer)."""
+        if searcher is not None:
+            fs, fi, done = last_out[0]
+            done.synchronize()
+            return fs.cpu().numpy(), fi.cpu().numpy()
+        raw = res[last_out[0]].cpu().numpy()
+        return raw[: nq * K * 4].view(np.float32).reshape(nq, K), raw[idx_off: idx_off + nq * K * 8].view(np.int64).reshape(nq, K)
+
+    if args.dump_outputs and rank == 0:
+        res_s, res_i = read_results()
+        dump_outputs(args.dump_outputs, {"scores": res_s, "indices": res_i})
+
     # ---- sustained: the same step, `--sustained-steps` more of them back to back (the timed region above is the
     # contract's K steps - 63 ms at the default; a second of back-to-back passes lets the clock settle) -----------------
     sustained, power = None, None
@@ -761,7 +821,7 @@ def main():
             sp_["rows_per_launch"] = max(sp_["rows_per_launch"], p_["rows_per_launch"])
         return sp_
 
-    if sustained_steps > 0 and args.workload != "c1":
+    if args.full and sustained_steps > 0 and args.workload != "c1":
         barrier()
         # the sustained leg runs as the timed region does: with the brackets on one rank, bare on a sharded run (whose kernel
         # time comes from a third, bracketed leg right behind; round 4 bracketed the sustained leg itself, and its step read
@@ -817,7 +877,7 @@ def main():
     # ---- the exchange as the communicator saw it (N > 1): backend, world, one device per rank, and what ONE all-gather of
     # the packed per-shard top-k costs on the side stream (outside the timed region; every rank takes part) ----------------
     exchange = None
-    if searcher is not None:
+    if args.full and searcher is not None:
         exchange = searcher.measure_exchange(nq, K)
         exchange["placement"] = "overlap (side stream, beside the next step's search)" if overlap[0] else "inline (the search's own stream)"
         exchange["placement_trial"] = placement_trial
@@ -826,7 +886,7 @@ def main():
 
     # ---- how the search ran (one extra search outside the timed region): algorithm, levels, candidates ----------------
     search_stats, stats_algo = None, None
-    if not mask_ptr and encoder is None:
+    if args.full and not mask_ptr and encoder is None:
         _, _, st_ = ix.search(q_host, K, algo=args.algo, return_stats=True)
         stats_algo = {1: "scan", 2: "mfma"}.get(st_["algo"])
         if st_["algo"] == 2:
@@ -838,81 +898,78 @@ def main():
     # ---- roofline of the dominant kernel (live hipEvent brackets inside the library, on the launch stream) ---------
     # One launch of the dominant kernel reads the local corpus once for the whole batch: algorithmic bytes = rows * d * s
     # (SURVEY 8d), flops = 2 * batch * rows * d.  Both ceilings are reported; `bound` names the nearer one.
-    kern_ms = prof["total_ms"] / max(1, prof["launches"])
-    launches_per_step = prof["launches"] / max(1, prof.get("steps", args.steps))
-    alg_bytes = prof["rows_per_launch"] * D * elem
-    q_per_launch = nq / max(1.0, launches_per_step)
-    alg_flops = 2.0 * q_per_launch * prof["rows_per_launch"] * D
-    achieved = alg_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
-    tflops = alg_flops / (kern_ms * 1e-3) / 1e12 if kern_ms > 0 else 0.0
-    mfma_peak = MFMA_PEAK_TFLOPS["bf16" if bf16 else "f32"]
-    hbm_frac, mfma_frac = achieved / HBM_PEAK_GBS, tflops / mfma_peak
-    traffic = None
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath) and not args.nq and not args.rows and not mask_ptr:
-        try:
-            tb = json.load(open(tpath)).get(f"{args.workload}_n{world}")
-            if tb:
-                traffic = {"bytes": tb, "source": "profiles/traffic.json: offline rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of "
-                                                  "this command (tools/run_profiles.sh), not an observation of this run"}
-        except Exception:
-            traffic = None
-    kernel_name = {"mfma": "mfma16_topk_kernel", "scan": "scan_kernel"}.get(stats_algo or ("scan" if mask_ptr and nq <= 4 else None), "unknown")
-    if stats_algo is None and encoder is not None:
-        kernel_name = "mfma16_topk_kernel"
-    # ---- the ceiling of this pass on THIS device, measured on the resident corpus right here (tools/microbench/
-    # mfma_stream_ceiling.hip: the product's tile loop without epilogue / candidates, its DMA stream alone, its matrix work
-    # alone, and the same MFMA count with operands in registers = the random-data matrix rate under this device's power cap)
-    ceiling = None
-    if (rank == 0 and world == 1 and not args.no_ceiling and bf16 and D == 768 and nq == 256 and encoder is None
-            and not mask_ptr and n_local >= 64 * 512):
-        try:
-            import ctypes as C
-            cl = C.CDLL(os.path.join(ROOT, "tools", "microbench", "build", "libts_ceiling.so"))
-            cl.ts_ceiling_run.restype = C.c_int
-            cl.ts_ceiling_run.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p]
-            ms4 = (C.c_double * 4)()
-            torch.cuda.synchronize()
-            rows_c = n_local // 32 * 32
-            if cl.ts_ceiling_run(local_rank, C.c_void_p(ix.info()["rows_ptr"]), rows_c, C.c_void_p(q_dev.data_ptr()), 3, 5, ms4, None) == 0:
-                fl = 2.0 * 256 * rows_c * D
-                ceiling = {"stream_plus_mfma_ms": round(ms4[0], 4), "stream_only_ms": round(ms4[1], 4),
-                           "mfma_lds_only_ms": round(ms4[2], 4), "bare_mfma_ms": round(ms4[3], 4),
-                           "measured_gemm_tflops": round(fl / (ms4[3] * 1e-3) / 1e12, 1),
-                           "stream_plus_mfma_hbm_frac": round(rows_c * D * 2 / (ms4[0] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                           "kernel_over_stream_plus_mfma": round(kern_ms / ms4[0], 4) if ms4[0] > 0 else None,
-                           "how": "same run, same device, the resident corpus: 3 interleaved rounds x 5 launches per leg of "
-                                  "tools/microbench/mfma_stream_ceiling.hip"}
-        except OSError as e:
-            log(rank, f"ceiling legs skipped: {e}")
-    by_mfma = mfma_frac > hbm_frac
-    roofline = {"bound": "mfma" if by_mfma else "hbm", "kernel": kernel_name,
-                "achieved": round(tflops if by_mfma else achieved, 1), "peak": mfma_peak if by_mfma else HBM_PEAK_GBS,
-                "unit": "TFLOP/s" if by_mfma else "GB/s", "frac": round(mfma_frac if by_mfma else hbm_frac, 4),
-                "hbm_achieved_gbs": round(achieved, 1), "hbm_peak_gbs": HBM_PEAK_GBS, "hbm_frac": round(hbm_frac, 4),
-                "mfma_achieved_tflops": round(tflops, 1), "mfma_peak_tflops": mfma_peak, "mfma_frac": round(mfma_frac, 4),
-                "mfma_frac_of_measured_gemm_rate": (round(tflops / ceiling["measured_gemm_tflops"], 4) if ceiling else None),
-                "mfma_frac_of_guide_gemm_rate": round(tflops / MFMA_RANDOM_DATA_GEMM_TFLOPS, 4) if bf16 else None,
-                "ceiling": ceiling,
-                "power": power,
-                "traffic": traffic,
-                "kernel_ms": round(kern_ms, 4), "launches_per_step": launches_per_step,
-                "kernel_ms_from": "hipEvent brackets over the timed region" if bracket_timed else
-                                  "hipEvent brackets over a separate leg of <= 100 steps behind the timed region and the sustained leg (which both run without them)",
-                "algorithmic_bytes_per_launch": alg_bytes, "algorithmic_flops_per_launch": alg_flops}
+    roofline = None
+    if args.full:
+        kern_ms = prof["total_ms"] / max(1, prof["launches"])
+        launches_per_step = prof["launches"] / max(1, prof.get("steps", args.steps))
+        alg_bytes = prof["rows_per_launch"] * D * elem
+        q_per_launch = nq / max(1.0, launches_per_step)
+        alg_flops = 2.0 * q_per_launch * prof["rows_per_launch"] * D
+        achieved = alg_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
+        tflops = alg_flops / (kern_ms * 1e-3) / 1e12 if kern_ms > 0 else 0.0
+        mfma_peak = MFMA_PEAK_TFLOPS["bf16" if bf16 else "f32"]
+        hbm_frac, mfma_frac = achieved / HBM_PEAK_GBS, tflops / mfma_peak
+        traffic = None
+        tpath = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tpath) and not args.nq and not args.rows and not mask_ptr:
+            try:
+                tb = json.load(open(tpath)).get(f"{args.workload}_n{world}")
+                if tb:
+                    traffic = {"bytes": tb, "source": "profiles/traffic.json: offline rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of "
+                                                      "this command (tools/run_profiles.sh), not an observation of this run"}
+            except Exception:
+                traffic = None
+        kernel_name = {"mfma": "mfma16_topk_kernel", "scan": "scan_kernel"}.get(stats_algo or ("scan" if mask_ptr and nq <= 4 else None), "unknown")
+        if stats_algo is None and encoder is not None:
+            kernel_name = "mfma16_topk_kernel"
+        # ---- the ceiling of this pass on THIS device, measured on the resident corpus right here (tools/microbench/
+        # mfma_stream_ceiling.hip: the product's tile loop without epilogue / candidates, its DMA stream alone, its matrix work
+        # alone, and the same MFMA count with operands in registers = the random-data matrix rate under this device's power cap)
+        ceiling = None
+        if (rank == 0 and world == 1 and not args.no_ceiling and bf16 and D == 768 and nq == 256 and encoder is None
+                and not mask_ptr and n_local >= 64 * 512):
+            try:
+                import ctypes as C
+                cl = C.CDLL(os.path.join(ROOT, "tools", "microbench", "build", "libts_ceiling.so"))
+                cl.ts_ceiling_run.restype = C.c_int
+                cl.ts_ceiling_run.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p]
+                ms4 = (C.c_double * 4)()
+                torch.cuda.synchronize()
+                rows_c = n_local // 32 * 32
+                if cl.ts_ceiling_run(local_rank, C.c_void_p(ix.info()["rows_ptr"]), rows_c, C.c_void_p(q_dev.data_ptr()), 3, 5, ms4, None) == 0:
+                    fl = 2.0 * 256 * rows_c * D
+                    ceiling = {"stream_plus_mfma_ms": round(ms4[0], 4), "stream_only_ms": round(ms4[1], 4),
+                               "mfma_lds_only_ms": round(ms4[2], 4), "bare_mfma_ms": round(ms4[3], 4),
+                               "measured_gemm_tflops": round(fl / (ms4[3] * 1e-3) / 1e12, 1),
+                               "stream_plus_mfma_hbm_frac": round(rows_c * D * 2 / (ms4[0] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                               "kernel_over_stream_plus_mfma": round(kern_ms / ms4[0], 4) if ms4[0] > 0 else None,
+                               "how": "same run, same device, the resident corpus: 3 interleaved rounds x 5 launches per leg of "
+                                      "tools/microbench/mfma_stream_ceiling.hip"}
+            except OSError as e:
+                log(rank, f"ceiling legs skipped: {e}")
+        by_mfma = mfma_frac > hbm_frac
+        roofline = {"bound": "mfma" if by_mfma else "hbm", "kernel": kernel_name,
+                    "achieved": round(tflops if by_mfma else achieved, 1), "peak": mfma_peak if by_mfma else HBM_PEAK_GBS,
+                    "unit": "TFLOP/s" if by_mfma else "GB/s", "frac": round(mfma_frac if by_mfma else hbm_frac, 4),
+                    "hbm_achieved_gbs": round(achieved, 1), "hbm_peak_gbs": HBM_PEAK_GBS, "hbm_frac": round(hbm_frac, 4),
+                    "mfma_achieved_tflops": round(tflops, 1), "mfma_peak_tflops": mfma_peak, "mfma_frac": round(mfma_frac, 4),
+                    "mfma_frac_of_measured_gemm_rate": (round(tflops / ceiling["measured_gemm_tflops"], 4) if ceiling else None),
+                    "mfma_frac_of_guide_gemm_rate": round(tflops / MFMA_RANDOM_DATA_GEMM_TFLOPS, 4) if bf16 else None,
+                    "ceiling": ceiling,
+                    "power": power,
+                    "traffic": traffic,
+                    "kernel_ms": round(kern_ms, 4), "launches_per_step": launches_per_step,
+                    "kernel_ms_from": "hipEvent brackets over the timed region" if bracket_timed else
+                                      "hipEvent brackets over a separate leg of <= 100 steps behind the timed region and the sustained leg (which both run without them)",
+                    "algorithmic_bytes_per_launch": alg_bytes, "algorithmic_flops_per_launch": alg_flops}
 
     # ---- recall@10 of EVERY query against the oracle (fp64 scores of the same bf16/fp32 values; oracle.ChunkedTruth
     # applies check_topk_against_truth's protocol: pinned ranks exact, near-tie runs as sets, scores within 1e-5) --------
-    if searcher is not None:
-        fs, fi, done = last_out[0]
-        done.synchronize()
-        res_s, res_i = fs.cpu().numpy(), fi.cpu().numpy()
-    else:
-        raw = res[last_out[0]].cpu().numpy()
-        res_s = raw[: nq * K * 4].view(np.float32).reshape(nq, K)
-        res_i = raw[idx_off: idx_off + nq * K * 8].view(np.int64).reshape(nq, K)
+    check = args.full and not args.no_recall
+    if check:
+        res_s, res_i = read_results()
     recall, parity = None, None
-    if not args.no_recall and encoder is not None:
+    if check and encoder is not None:
         # what the index multiplied in the step that is checked: the static output of that step's graph, or a fresh forward
         g_ = enc_graphs.get(id(lanes[(step_no[0] - 1) % len(lanes)]))
         e_ = g_[1] if g_ is not None else encode_queries()
@@ -920,7 +977,7 @@ def main():
             q_host = e_.view(torch.int16).cpu().numpy().view(np.uint16) if e_.dtype == torch.bfloat16 else oracle.f32_to_bf16_bits(e_.float().cpu().numpy())
         else:
             q_host = e_.float().cpu().numpy()
-    if not args.no_recall:
+    if check:
         qf = oracle.bf16_bits_to_f32(q_host) if bf16 else q_host
         truth = oracle.ChunkedTruth(qf, res_i, K)
         t_chk = time.time()
@@ -953,7 +1010,7 @@ def main():
 
     # ---- CPU baseline: the reference's formulation on the host cores, MEASURED on a bounded sample (no scaling) --------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         q_s = oracle.bf16_bits_to_f32(q_host) if bf16 else q_host
         mem_avail = 0
         try:
@@ -1028,6 +1085,7 @@ def main():
             "value": round(qps, 1), "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
             "scaling": "strong", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
+            "full": args.full,
             "config": {"workload": f"{rows_total}x{D} {dtype} corpus, batch-{nq} queries, top-{K} "
                                    + (f"(BASELINE.json configs[{ {'c1': 0, 'c2': 1, 'c2b': 1, 'c3': 2, 'c4': 3, 'c5': 4}[args.workload] }])" if args.workload != "c3q" else
                                       "(the reference's production table shape, theorem_embedding_qwen vector(1024): streamlit_app.py:49, rds_schema.sql:50-56; not a BASELINE.json config)") + (f", {args.encoder_dtype} encoder forward in the loop ({args.seq_len} tokens/query, random-init " + ("Qwen3-Embedding-0.6B shape: the production embedder, streamlit_app.py:55)" if args.encoder == "qwen" else "embeddinggemma-300m shape: the reference's second embedder, embedders.py:1-4)" if args.encoder == "gemma" else "BERT-base shape)") if encoder is not None else ""),

@@ -325,7 +325,7 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--rows", "300000", "--nq", "16", "--steps", "2",
-                          "--warmup", "1"], capture_output=True, text=True, timeout=280, cwd=root)
+                          "--warmup", "1", "--full"], capture_output=True, text=True, timeout=280, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, out.stdout
@@ -345,6 +345,48 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     cpu = doc["cpu_baseline"]
     assert cpu["kind"] in ("port", "reference") and cpu["cores"] >= 1 and cpu["value"] > 0 and cpu["sample"]
     assert doc["recall_at_10"] == 1.0
+
+
+def test_bench_plain_run_times_only_its_steps_and_dumps_what_they_returned(tmp_path):
+    """A plain bench.py run: the contract's keys, exactly --steps timed steps, none of --full's legs; --dump-outputs writes
+    the last timed step's answer, and a --full run of the same arguments (whose parity leg checks every query against the
+    oracle) writes the same arrays, bit for bit.  configs[0] (c1) the same way: its six metrics are what --full's parity
+    leg read from the report."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(extra, out_dir):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", str(out_dir)] + extra, capture_output=True, text=True, timeout=280, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, out.stdout
+        return json.loads(lines[0])
+
+    search = ["--rows", "300000", "--nq", "16"]
+    doc = run(search, tmp_path / "plain")
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in doc, key
+    assert doc["steps"] == 3 and doc["full"] is False and doc["unit"] == "queries/s" and doc["dtype"] == "bf16"
+    assert doc["value"] == pytest.approx(16 / (doc["ms_per_step"] * 1e-3), rel=1e-3)
+    for key in ("recall_at_10", "parity", "search_stats", "sustained", "roofline", "cpu_baseline"):
+        assert doc[key] is None, key
+    full = run(search + ["--full", "--no-cpu-baseline", "--sustained-steps", "4"], tmp_path / "full")
+    assert full["full"] is True and full["recall_at_10"] == 1.0 and full["parity"]["violations"] == 0
+    for name, dtype in (("scores", np.float32), ("indices", np.float64)):
+        a, b = np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")
+        assert a.dtype == dtype and a.shape == (16, 10) and np.array_equal(a, b), name
+    idx = np.load(tmp_path / "plain" / "indices.npy")
+    assert idx.min() >= 0 and idx.max() < 300000 and np.all(idx == np.round(idx))
+
+    doc = run(["--workload", "c1"], tmp_path / "c1_plain")
+    assert doc["steps"] == 3 and doc["full"] is False and doc["parity"] is None and doc["cpu_baseline"] is None
+    full = run(["--workload", "c1", "--full"], tmp_path / "c1_full")
+    assert full["parity"]["violations"] == 0
+    got = np.load(tmp_path / "c1_plain" / "metrics.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, np.load(tmp_path / "c1_full" / "metrics.npy"))
+    assert np.array_equal(got, np.array(list(full["parity"]["metrics"].values())))
 
 
 def test_pgvector_search_with_a_where_mask():
@@ -677,7 +719,7 @@ def test_bench_under_torch_distributed_run_with_two_ranks_sharing_the_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--rows", "600000",
-           "--nq", "64", "--steps", "3", "--warmup", "1", "--sustained-steps", "4"]
+           "--nq", "64", "--steps", "3", "--warmup", "1", "--sustained-steps", "4", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=400, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]
@@ -700,7 +742,7 @@ def test_bench_starts_its_own_ranks_when_no_launcher_is_around():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k_: v for k_, v in os.environ.items() if k_ not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--share-gpu", "--rows", "800000", "--nq", "64",
-           "--steps", "3", "--warmup", "1", "--sustained-steps", "4"]
+           "--steps", "3", "--warmup", "1", "--sustained-steps", "4", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]

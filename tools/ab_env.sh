@@ -13,7 +13,7 @@ for r in $(seq 1 "$REPS"); do
     envs=""
     [ "$s" != "-" ] && envs="$(echo "$s" | tr ',' ' ')"
     args="${AB_ARGS:---workload c3 --rows ${AB_ROWS:-1250000} --force-dist --steps ${AB_STEPS:-2000} --warmup 200 --sustained-steps 300}"
-    line=$(env $envs timeout -k 10 300 python3 "$R/bench.py" $args --no-cpu-baseline --no-recall --no-ceiling 2> "$OUT/ab.log" | tail -1)
+    line=$(env $envs timeout -k 10 300 python3 "$R/bench.py" --full $args --no-cpu-baseline --no-recall --no-ceiling 2> "$OUT/ab.log" | tail -1)
     echo "$line" >> "$OUT/ab_${s//[^A-Za-z0-9_=,-]/_}.jsonl"
     python3 -c "import json,sys; d=json.loads(sys.argv[1]); print('round $r', sys.argv[2], 'ms_per_step', d['ms_per_step'], 'kernel_ms', d['roofline']['kernel_ms'], 'step-kernel us', round(1e3*(d['ms_per_step']-d['roofline']['kernel_ms']),1))" "$line" "$s"
   done

@@ -88,13 +88,13 @@ def main(src, tag):
             if kernels[0][1] in r["Kernel_Name"]:
                 tot.setdefault(r["Counter_Name"], []).append(float(r["Counter_Value"]))
         with open(os.path.join(out, f"{tag}_c3_sq_counters_raw.txt"), "w") as f:
-            f.write("rocprofv3 --kernel-trace --pmc SQ_* (its own pass), bench.py --workload c3 --steps 3 --warmup 1: per launch of the full pass\n")
+            f.write("rocprofv3 --kernel-trace --pmc SQ_* (its own pass), bench.py --full --workload c3 --steps 3 --warmup 1: per launch of the full pass\n")
             for k_, v in sorted(tot.items()):
                 f.write(f"{k_}: launches {len(v)}, mean {sum(v) / len(v):.6g}, min {min(v):.6g}, max {max(v):.6g}\n")
     json.dump(traffic, open(tpath, "w"), indent=1)
     with open(os.path.join(out, f"{tag}_traffic_notes.txt"), "w") as f:
         f.write("HBM traffic per launch of the dominant kernel, rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes),\n"
-                "command: python3 bench.py --workload <w> --steps 3 --warmup 1 --no-cpu-baseline --no-recall\n")
+                "command: python3 bench.py --full --workload <w> --steps 3 --warmup 1 --no-cpu-baseline --no-recall\n")
         f.write("\n".join(notes) + "\n")
     print("\n".join(notes))
 

@@ -9,9 +9,9 @@ set -e
 R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 OUT="$R/gpurun_out/${1:-shards}"
 mkdir -p "$OUT"
-timeout -k 10 300 python3 "$R/bench.py" --workload c3 --no-cpu-baseline --no-recall --no-ceiling > "$OUT/steps_10000000.json" 2> "$OUT/steps_10000000.log"
+timeout -k 10 300 python3 "$R/bench.py" --full --workload c3 --no-cpu-baseline --no-recall --no-ceiling > "$OUT/steps_10000000.json" 2> "$OUT/steps_10000000.log"
 for n in 5000000 2500000 1250000; do
-  timeout -k 10 200 python3 "$R/bench.py" --workload c3 --rows $n --force-dist --no-cpu-baseline --no-recall --no-ceiling --steps ${SHARD_STEPS:-1000} --warmup ${SHARD_WARMUP:-100} > "$OUT/steps_$n.json" 2> "$OUT/steps_$n.log"
+  timeout -k 10 200 python3 "$R/bench.py" --full --workload c3 --rows $n --force-dist --no-cpu-baseline --no-recall --no-ceiling --steps ${SHARD_STEPS:-1000} --warmup ${SHARD_WARMUP:-100} > "$OUT/steps_$n.json" 2> "$OUT/steps_$n.log"
 done
 python3 - "$OUT" <<'PY'
 import json, sys
