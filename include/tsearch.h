@@ -239,6 +239,21 @@ int ts_search_biased(ts_index *ix, const void *queries, int q_dtype, int q_on_de
 int ts_rank_of(ts_index *ix, const void *queries, int q_dtype, int q_on_device, int32_t nq, const int64_t *target_rows,
                int64_t *out_rank, float *out_score, void *stream);
 
+/* Ranks of many target rows per query in the same canonical order (score descending, global row ascending): the number of
+ * rows whose (score, -row) beats the target's.  Query i's targets are target_rows[target_offsets[i] .. target_offsets[i+1]).
+ * out_rank / out_score are aligned with target_rows; -1 / NaN for rows outside this index or with a NaN score.
+ * A list may be empty and may repeat a row (repeats share one rank).  Target rows are global ids (row_offset applies);
+ * subset indexes are refused.  Queries are prepared as ts_search prepares them.  Host pointers; out_score may be NULL.
+ * bf16 and fp32 indexes at d = 384, 512, 768, 1024: one matrix pass over the corpus per block of 256 queries and per 16
+ * targets of the longest list (a gather launch computes the targets' scores by the same arithmetic first).  Other widths:
+ * one ts_rank_of pass per target column - correct and slow.
+ * Arithmetic contract: the ranks are consistent with the scores returned here (distinct targets of one query have
+ * distinct ranks, ordered by (score, -row)).  Where the fp64 truth cannot separate a target from its neighbours, a rank may
+ * differ from ts_rank_of's and from the search paths' positions by the count of those neighbours. */
+int ts_rank_many(ts_index *ix, const void *queries, int q_dtype, int q_on_device, int32_t nq,
+                 const int64_t *target_offsets, const int64_t *target_rows,
+                 int64_t *out_rank, float *out_score, void *stream);
+
 /* The sharded form of ts_rank_of: how many rows of THIS index rank before a document with the given score and global id
  * (score descending, global id ascending), wherever that document lives.  The shard that holds the document gets its
  * score from ts_rank_of; the sum of ts_count_above over all shards is the document's rank in the whole corpus (the

@@ -49,8 +49,9 @@ def rank_concepts(sim_matrix):
 class IndexRanking:
     """Stands in for the ``[Q x N]`` similarity matrix when the corpus lives in a `TheoremIndex` and the matrix
     would not fit (10M slogans x 1k queries = 40 GB): the metric functions below only ever need the k best docs
-    per query (``index.search``) or the position of one relevant doc in the full ranking (``index.rank_of``, a
-    counting pass), never the matrix itself.  Pass it wherever they take ``sim_matrix`` / ``ranked``."""
+    per query (``index.search``), the position of one relevant doc in the full ranking (``index.rank_of``, a
+    counting pass) or, past the top-k depth (k=None or k > 256), the positions of every graded doc
+    (``index.rank_many``, one matrix pass), never the matrix itself.  Pass it wherever they take ``sim_matrix`` / ``ranked``."""
 
     def __init__(self, index, query_emb):
         self.index = index
@@ -69,6 +70,27 @@ class IndexRanking:
 
     def rank_of(self, docs):
         return self.index.rank_of(self.query_emb, docs)[0]
+
+    def ranks_of_graded(self, qrels):
+        """Per query, ``(ranks, grades, docs)`` of its docs with a non-zero grade that are rows of the index, in rank order: one
+        `rank_many` call for all of them (cached per qrels dict).  Grade-0 docs and docs outside the index occupy no
+        position that changes a metric, so the graded metrics at any depth follow from these positions alone."""
+        hit = self._cache.get(("graded", id(qrels)))
+        if hit is not None and hit[0] is qrels:
+            return hit[1]
+        docs, grades = [], []
+        for q in range(self.shape[0]):
+            items = [(int(d), float(g)) for d, g in (qrels.get(q) or {}).items() if g != 0]
+            docs.append([d for d, _ in items])
+            grades.append(np.array([g for _, g in items], dtype=float))
+        ranks = self.index.rank_many(self.query_emb, docs)[0]
+        out = []
+        for r, g, d in zip(ranks, grades, docs):
+            keep = r >= 0
+            order = np.argsort(r[keep], kind="stable")
+            out.append((r[keep][order], g[keep][order], np.asarray(d, dtype=np.int64)[keep][order]))
+        self._cache[("graded", id(qrels))] = (qrels, out)
+        return out
 
 
 class _SharedRanking(np.ndarray):
@@ -164,13 +186,117 @@ def _exact_docs(qrels, nq):
     return np.array([_exact_doc(qrels[q]) for q in range(nq)])
 
 
+# --- rank-based forms on an IndexRanking past the depth its top-k serves (k=None or k > 256) -----------------------------
+# A position that holds no graded doc adds +0.0 to the DCG and Q-measure sums and multiplies ERR's running product by 1.0,
+# so the metrics follow from the positions of the graded docs (IndexRanking.ranks_of_graded) and equal the matrix forms
+# bit for bit when the rankings agree: the running sums and products below are taken in rank order, as the matrix forms'
+# accumulates are; the DCG's np.sum (pairwise summation) is taken of the same dense row of discounted gains.
+def _rank_based(ranked, k):
+    return isinstance(ranked, IndexRanking) and (k is None or k > 256)
+
+
+def _depth(ranked, k):
+    return ranked.shape[1] if k is None else min(int(k), ranked.shape[1])
+
+
+def _exact_hits(ranked, qrels, k):
+    """Whether each query's exact doc (grade 1) is among the ``k`` best: P@k and H@k past the top-k depth."""
+    exact = _exact_docs(qrels, ranked.shape[0])
+    kk = _depth(ranked, k)
+    hit = np.zeros(exact.shape[0], dtype=bool)
+    for q, (r, _, docs) in enumerate(ranked.ranks_of_graded(qrels)):
+        at = np.flatnonzero(docs == exact[q])
+        hit[q] = at.size > 0 and r[at[0]] < kk
+    return hit
+
+
+def _dcg_sparse(r, g, kk, gain, buf, stacked):
+    """DCG over the first ``kk`` positions of a ranking whose graded docs sit at positions ``r`` (sorted) with grades ``g``:
+    the np.sum of `_dcg_from_rels` (``stacked=False``) or of ndcg_at_k's row-wise form, taken of the same dense row."""
+    keep = r < kk
+    r, g = r[keep], g[keep]
+    vals = _gains(g, gain) * (1.0 / np.log2(r + 2))
+    if vals.size == 0:
+        return 0.0
+    if vals.size == 1:
+        return float(vals[0])                     # x plus any number of +0.0 terms is x
+    row = buf[:kk]
+    row[r] = vals
+    out = float(np.sum(row[None, :], axis=1)[0] if stacked else np.sum(row))
+    row[r] = 0.0
+    return out
+
+
+def _ndcg_ranks(ranked, qrels, k, gain):
+    nq = ranked.shape[0]
+    kk = _depth(ranked, k)
+    dicts = [qrels.get(q, {}) for q in range(nq)]
+    graded = ranked.ranks_of_graded(qrels)
+    buf = np.zeros(kk) if any(int(np.count_nonzero(r < kk)) > 1 for r, _, _ in graded) else None
+    if kk == 0 or not all(dicts):
+        # the per-query form of ndcg_at_k, "TOO SMALL" lines included
+        out = []
+        for q in range(nq):
+            if kk == 0:
+                dcg = _dcg_from_rels(np.zeros(0), gain=gain)
+            else:
+                dcg = _dcg_sparse(graded[q][0], graded[q][1], kk, gain, buf, False)
+            ideal = np.sort(np.array(list(dicts[q].values()), dtype=float))[::-1]
+            idcg = _dcg_from_rels(ideal if k is None else ideal[:k], gain=gain)
+            out.append(0.0 if idcg == 0.0 else dcg / idcg)
+        return float(np.mean(out))
+    dcg = np.array([_dcg_sparse(r, g, kk, gain, buf, True) for r, g, _ in graded], dtype=float)
+    ideals = [np.sort(np.array(list(d.values()), dtype=float))[::-1][:k] for d in dicts]
+    idcg = _per_query(ideals, lambda a: np.sum(_gains(a, gain) * (1.0 / np.log2(np.arange(2, a.shape[1] + 2))), axis=1))
+    return float(np.mean(np.divide(dcg, idcg, out=np.zeros(nq), where=idcg != 0.0)))
+
+
+def _err_ranks(ranked, qrels, kk, denom):
+    """ERR's cascade (err_at_k) over the graded positions in rank order."""
+    out = np.zeros(ranked.shape[0])
+    for q, (r, g, _) in enumerate(ranked.ranks_of_graded(qrels)):
+        p = (np.exp2(g) - 1.0) / denom
+        before, total = 1.0, 0.0
+        for pos, pq in zip(r.tolist(), p.tolist()):
+            if pos >= kk:
+                break
+            after = before * (1.0 - pq)
+            if pq > 0.0:
+                total = total + before * pq * (1.0 / (pos + 1))
+                if after <= 1e-12:
+                    break
+            before = after
+        out[q] = total
+    return out
+
+
+def _q_measure_ranks(ranked, qrels, kk, denom):
+    """Q-measure's running sums (q_measure_at_k) over the graded positions in rank order."""
+    out = np.zeros(ranked.shape[0])
+    for q, (r, g, _) in enumerate(ranked.ranks_of_graded(qrels)):
+        gains = (np.exp2(g) - 1.0) / denom
+        cum, total = 0.0, 0.0
+        for pos, gq in zip(r.tolist(), gains.tolist()):
+            if pos >= kk:
+                break
+            if gq > 0.0:
+                cum = cum + gq
+                total = total + gq * (cum / (pos + 1))
+        out[q] = total
+    return out
+
+
 def precision_at_k(sim_matrix, qrels, k=5):
+    if _rank_based(sim_matrix, k):
+        return float(np.mean(_exact_hits(sim_matrix, qrels, k) / k))
     top = _top(sim_matrix, k)
     hit = (top == _exact_docs(qrels, top.shape[0])[:, None]).any(axis=1)
     return float(np.mean(hit / k))
 
 
 def hit_at_k(sim_matrix, qrels, k=5):
+    if _rank_based(sim_matrix, k):
+        return float(np.mean(_exact_hits(sim_matrix, qrels, k).astype(float)))
     top = _top(sim_matrix, k)
     hit = (top == _exact_docs(qrels, top.shape[0])[:, None]).any(axis=1)
     return float(np.mean(hit.astype(float)))
@@ -247,6 +373,8 @@ def _gains(rels, gain):
 
 
 def ndcg_at_k(ranked, qrels, k=10, gain="exp"):
+    if _rank_based(ranked, k):
+        return _ndcg_ranks(ranked, qrels, k, gain)
     top = _top(ranked, k)
     nq, kk = top.shape
     dicts = [qrels.get(q, {}) for q in range(nq)]
@@ -275,18 +403,21 @@ def _max_grade(qrels):
 
 
 def err_at_k(ranked, qrels, k=10, max_rel=None):
-    top = _top(ranked, k)
+    rank_based = _rank_based(ranked, k)
+    top = None if rank_based else _top(ranked, k)
     if max_rel is None:
         max_rel = _max_grade(qrels)
         if max_rel <= 0.0:
             return 0.0
     denom = 2.0 ** max_rel
-    nq, kk = top.shape
+    nq, kk = (ranked.shape[0], _depth(ranked, k)) if rank_based else top.shape
     if nq == 0:
         return 0.0
     judged = np.array([bool(qrels.get(q, None)) for q in range(nq)])
     if kk == 0:
         return float(np.mean(np.zeros(nq)))
+    if rank_based:
+        return float(np.mean(np.where(judged, _err_ranks(ranked, qrels, kk, denom), 0.0)))
     # the cascade of reference lines 295-307 for every query at once: `going` before rank i is the running product of
     # (1 - p) over the ranks above it (accumulated in rank order, as the loop does), a query stops counting behind the first
     # rank that leaves going <= 1e-12, and the terms are added in rank order
@@ -300,13 +431,14 @@ def err_at_k(ranked, qrels, k=10, max_rel=None):
 
 
 def q_measure_at_k(ranked, qrels, k=10, max_rel=None):
-    top = _top(ranked, k)
+    rank_based = _rank_based(ranked, k)
+    top = None if rank_based else _top(ranked, k)
     if max_rel is None:
         max_rel = _max_grade(qrels)
         if max_rel <= 0.0:
             return 0.0
     denom = 2.0 ** max_rel
-    nq, kk = top.shape
+    nq, kk = (ranked.shape[0], _depth(ranked, k)) if rank_based else top.shape
     if nq == 0:
         return 0.0
     dicts = [qrels.get(q, None) or {} for q in range(nq)]
@@ -314,6 +446,9 @@ def q_measure_at_k(ranked, qrels, k=10, max_rel=None):
                             lambda a: ((np.exp2(a) - 1.0) / denom).sum(axis=1))
     if kk == 0:
         return float(np.mean(np.zeros(nq)))
+    if rank_based:
+        total = _q_measure_ranks(ranked, qrels, kk, denom)
+        return float(np.mean(np.divide(total, ideal_gain, out=np.zeros(nq), where=ideal_gain > 0.0)))
     # reference lines 347-369 for every query at once: the cumulated gain and the total are running sums in rank order
     gains = (np.exp2(_grade_matrix(top, qrels)) - 1.0) / denom
     pos = gains > 0.0

@@ -121,6 +121,7 @@ struct ts_index {
     ts_index* parent = nullptr;                              // a view: the handle that owns the rows
     std::atomic<int> nviews{0};                              // live views of this handle (it cannot grow meanwhile)
     void* rank_buf = nullptr;   size_t rank_bytes = 0;       // ts_rank_of: targets | counts | target scores, one query block
+    void* rank_many_buf = nullptr; size_t rank_many_bytes = 0;  // ts_rank_many: slots | keys | counts of one pass of one query block
     const u32* active_mask = nullptr;                        // bitmask of the search in progress (under `mu`)
     int64_t active_allowed = 0;                              // rows that bitmask allows (host masks: counted; else n)
     bool attr_done = false;

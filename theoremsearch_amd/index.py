@@ -302,6 +302,28 @@ class TheoremIndex:
                                         _ffi.as_ptr(ranks), _ffi.as_ptr(scores), None))
         return ranks, scores
 
+    def rank_many(self, queries, targets):
+        """Ranks of several rows per query in one matrix pass per block of 256 queries: ``targets`` holds one integer
+        sequence per query (ragged, possibly empty, repeats allowed).  Returns ``(ranks, scores)``, lists of per-query
+        int64 / float32 arrays aligned with ``targets``; ``-1`` / NaN for rows not in the index or with a NaN score.
+        The ranks are consistent with the returned scores (score descending, row ascending); where the fp64 truth cannot
+        separate a target from its neighbours they may differ from `rank_of` by the count of those neighbours."""
+        q = _host_rows(queries)
+        if q.shape[1] != self.d:
+            raise ValueError(f"queries have d={q.shape[1]}, index has d={self.d}")
+        lists = [np.asarray(t, dtype=np.int64).reshape(-1) for t in targets]
+        if len(lists) != q.shape[0]:
+            raise ValueError(f"{len(lists)} target lists for {q.shape[0]} queries")
+        offsets = np.zeros(q.shape[0] + 1, dtype=np.int64)
+        np.cumsum([t.shape[0] for t in lists], out=offsets[1:])
+        rows = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, dtype=np.int64))
+        ranks = np.empty(max(1, rows.shape[0]), dtype=np.int64)
+        scores = np.empty(max(1, rows.shape[0]), dtype=np.float32)
+        _ffi.check(self._lib.ts_rank_many(self._h, _ffi.as_ptr(q), _ffi.np_dtype_code(q), 0, q.shape[0], _ffi.as_ptr(offsets),
+                                          _ffi.as_ptr(rows), _ffi.as_ptr(ranks), _ffi.as_ptr(scores), None))
+        return ([ranks[offsets[i]:offsets[i + 1]] for i in range(q.shape[0])],
+                [scores[offsets[i]:offsets[i + 1]] for i in range(q.shape[0])])
+
     def count_above(self, queries, target_scores, target_ids) -> np.ndarray:
         """Rows of this index that rank before a document with the given score and GLOBAL id (it may live on another
         shard); summed over the shards of a corpus this is the document's rank (`rank_of` for one index)."""
