@@ -122,7 +122,8 @@ extern "C" int ts_index_destroy(ts_index* ix) {
     }
     if (ix->attached) ix->rows = nullptr;
     void* ptrs[] = {ix->rows,  ix->stage,   ix->qstore,   ix->qf32,     ix->cand,       ix->count,  ix->thr, ix->priv, ix->pcount, ix->sample, ix->mask_dev, ix->bias_dev, ix->rank_buf, ix->rank_many_buf, ix->id_map,
-                    ix->fb_list, ix->fb_count, ix->stat, ix->partial, ix->partial2, ix->res_scores, ix->res_idx, ix->dbg, ix->part, ix->wg_ticks, ix->pair_pos};
+                    ix->fb_list, ix->fb_count, ix->stat, ix->partial, ix->partial2, ix->res_scores, ix->res_idx, ix->dbg, ix->part, ix->wg_ticks, ix->pair_pos,
+                    ix->scr_rows, ix->scr_tile, ix->scr_q, ix->scr_qmeta, ix->scr_cand, ix->scr_count};
     for (void* p : ptrs)
         if (p) hipFree(p);
     for (hipEvent_t e : ix->ev_pool) hipEventDestroy(e);
@@ -305,6 +306,7 @@ static int upload_device_locked(ts_index* ix, const void* dev_rows, int src_dtyp
     StreamScope scope;
     TS_TRY(enter_stream(ix, stream, &st, &scope));
     char* dst = (char*)ix->rows + (size_t)row0 * ix->ld * ix->elem();
+    screen_touch(ix, row0, row0 + nrows);
     return prep_dispatch(src_dtype, ix->dtype, ix->metric == TS_METRIC_COS, dev_rows, src_ld, dst, nullptr, ix->ld, ix->d,
                          nrows, nrows, st);
 }
@@ -318,6 +320,7 @@ static int upload_host_locked(ts_index* ix, const void* host_rows, int src_dtype
     hipStream_t own;
     StreamScope scope;
     TS_TRY(enter_stream(ix, nullptr, &own, &scope));   // rows / the stage buffer may still feed a call enqueued on a caller's stream
+    screen_touch(ix, row0, row0 + nrows);
     if (src_dtype == ix->dtype && ix->metric == TS_METRIC_IP && ix->ld == ix->d) {
         // stored as given: straight copy into place
         HIP_TRY(hipMemcpyAsync((char*)ix->rows + (size_t)row0 * src_row, host_rows, (size_t)nrows * src_row, hipMemcpyHostToDevice, own));

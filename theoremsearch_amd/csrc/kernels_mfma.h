@@ -107,6 +107,9 @@ struct MfmaArgs {
     // and the time each workgroup took (100 MHz ticks) - the final select moves the boundaries for the next search
     const int64_t* part;
     unsigned* wg_ticks;
+    // int8 screen (kernels_screen8.h): per tile {1 / s_t, coefficient of |q|, coefficient of |e_q|, 0}, per query {1 / s_q, |e_q|, |q|, 0}
+    const float4* scr_tile;
+    const float4* scr_q;
     // full pass of the 16x16 kernel, d = 1024 at more than 192 queries: PAIRS of workgroups share a tile range, each half of
     // the pair holding 64 * NB of the queries (workgroups w and w + 8 of a group of 16: the same XCD under round-robin
     // dispatch, so the second reader of a tile finds it in that XCD's L2 / the memory-side cache); part / wg_ticks are

@@ -53,6 +53,9 @@ constexpr int kMfma16StageBytes = 4 * kMfma16StageCap * 16 + 16;     // + one co
 // paired full pass: 64 dwords behind the staged candidates, where the partner workgroup's position lands (one LDS-DMA dword
 // per lane of wave 0, all from the same address)
 constexpr int kMfma16PaceBytes = 256;
+// int8 screen (I8, kernels_screen8.h): the same LDS bytes hold 8-byte entries (row, query), twice as many per wave - a screened
+// wave expects ~125 of them against ~40 exact candidates of the bf16 pass
+constexpr int kScreenStageCap = 2 * kMfma16StageCap;
 
 // MFMA statements with pinned register classes: accumulator and corpus fragment in VGPRs, query fragment in a VGPR
 // ("v" forms) or an AGPR ("a" forms) quadruple.  No pads inside: the A fragment comes from a ds_read behind the k-step's
@@ -69,6 +72,19 @@ __device__ __forceinline__ void mfma16_a_first(f32x4& acc, const frag16& a, cons
 }
 __device__ __forceinline__ void mfma16_a(f32x4& acc, const frag16& a, const bf16x8& b) {
     asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "a"(b));
+}
+// int8 screen (I8): v_mfma_i32_16x16x64_i8, 64 bytes of K per 16-byte operand; the accumulator registers hold i32 bits
+__device__ __forceinline__ void mfma8_v_first(f32x4& acc, const frag16& a, const bf16x8& b) {
+    asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b));
+}
+__device__ __forceinline__ void mfma8_v(f32x4& acc, const frag16& a, const bf16x8& b) {
+    asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
+}
+__device__ __forceinline__ void mfma8_a_first(f32x4& acc, const frag16& a, const bf16x8& b) {
+    asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "a"(b));
+}
+__device__ __forceinline__ void mfma8_a(f32x4& acc, const frag16& a, const bf16x8& b) {
+    asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "a"(b));
 }
 // fp32 rows (F32): v_mfma_f32_16x16x4_f32, one float of the corpus chunk x one float of the query chunk per instruction
 __device__ __forceinline__ void mfma16f_v_first(f32x4& acc, float a, float b) {
@@ -176,6 +192,33 @@ __device__ __forceinline__ void ksplit_test_c(u64& mask, float m, float thr) {
     asm volatile("v_cmp_ge_f32 %0, %1, %2" : "=s"(mask) : "v"(m), "v"(thr));
 }
 
+// The same test on the i32 dot products of the int8 screen against the block's integer threshold of the tile.
+__device__ __forceinline__ u64 mfma8_block_test(const f32x4& a0, const f32x4& a1, int thr, int& m) {
+    u64 mask;
+    asm volatile(
+        "v_max3_i32 %0, %2, %3, %4\n\t"
+        "v_max3_i32 %0, %0, %5, %6\n\t"
+        "v_max3_i32 %0, %0, %7, %8\n\t"
+        "v_max_i32 %0, %0, %9\n\t"
+        "v_cmp_ge_i32 %1, %0, %10"
+        : "=&v"(m), "=s"(mask)
+        : "v"(a0[0]), "v"(a0[1]), "v"(a0[2]), "v"(a0[3]), "v"(a1[0]), "v"(a1[1]), "v"(a1[2]), "v"(a1[3]), "v"(thr));
+    return mask;
+}
+
+// Integer threshold of one (tile, query) pair of the int8 screen (kernels_screen8.h has the derivation): every row of the tile
+// whose exact fp32 score can reach `thr` has an int8 dot product >= the returned value.  tm = the tile's scalars (1 / s_t,
+// coefficient of |q|, coefficient of |e_q|; 1 / s_t = NaN: the tile holds a non-finite value), qm = the query's (1 / s_q,
+// |e_q|, |q|; 1 / s_q = NaN: the query holds one); athr = |thr|, or 0 where thr is infinite.  Every step rounds towards
+// admitting more rows; NaN -> INT_MIN (every row of the tile is a candidate; the exact rescore decides).  No branch: the clamp
+// is two v_max / v_min (maxNum: a NaN operand yields the other one).
+__device__ __forceinline__ int screen_int_thr(float tx, float ty, float tz, float thr, float athr, float rq, float eq, float qn) {
+    const float sub = fmaf(ty, qn, tz * eq);
+    const float mag = athr + sub;
+    const float v = (thr - sub - mag * 0x1p-18f) * tx * rq;
+    return (int)floorf(fminf(fmaxf(v - 1.0f, -0x1p31f), 0x1p30f));
+}
+
 // Append the passing scores of one query block (rare path: entered for a block only when some lane passed).  Written
 // for few instructions when ONE lane holds ONE passing score - the usual case: a slow wave holds up the other three
 // at the next barrier, so this path is paid four-fold.  STAGED: into the wave's LDS list (stage / stage_cnt); else into
@@ -208,6 +251,30 @@ __device__ __forceinline__ void mfma16_append_block(const f32x4& a0, const f32x4
                             if (pos < (u32)a.cap) a.cand[(int64_t)qid * a.cap + pos] = key;
                         }
                         ++cnt;
+                    }
+                }
+            }
+        }
+    }
+}
+
+// The int8 screen's form of the rare path: (row, query) pairs whose dot product reaches the tile's integer threshold, staged
+// as 8-byte entries; the row mask and the padding rows are tested here, the exact score by the rescore.
+__device__ __forceinline__ void mfma8_append_block(const f32x4& a0, const f32x4& a1, int thr, int m, int qid, int64_t row_base,
+                                                   const MfmaArgs& a, uint2* stage, u32* stage_cnt) {
+    if (m >= thr && qid < a.nq_real) {
+#pragma unroll
+        for (int g = 0; g < 8; ++g) {
+            const int s = __builtin_bit_cast(int, (g < 4) ? a0[g & 3] : a1[g & 3]);
+            if (s >= thr) {
+                const int64_t row = row_base + (g & 3) + 16 * (g >> 2);
+                if (row < a.n && (!a.row_mask || ((a.row_mask[row >> 5] >> (row & 31)) & 1u))) {
+                    const u32 at = atomicAdd(stage_cnt, 1u);
+                    if (at < (u32)kScreenStageCap) {
+                        stage[at] = make_uint2((u32)row, (u32)qid);
+                    } else {                                                       // list full: straight to the query's list
+                        const u32 pos = atomicAdd(&a.count[qid], 1u);
+                        if (pos < (u32)a.cap) a.cand[(int64_t)qid * a.cap + pos] = (u64)row;
                     }
                 }
             }
@@ -250,6 +317,7 @@ __device__ __forceinline__ void pair_read_word(unsigned& dst, unsigned lds_word)
 // SHARES, not the length).  3 = product + clock probe: s_memtime / s_memrealtime around the tile loop into a.dbg
 // (4 words per workgroup: shader cycles, 100 MHz ticks, units, 0) - MI355X_MICROARCH.md "DVFS give-back" item 6.
 // 6 = product + s_sleep of ~256 cycles per unit (how much of an added idle cycle shows up as time under the power cap).
+// 8 = the int8 screen (below, I8).
 // SPARSE only changes the symbol (sample levels show up under their own name in kernel traces).
 //
 // F32: the same kernel over an fp32 index (exact fp32: v_mfma_f32_16x16x4_f32, bit for bit an fmaf chain).  A row of D
@@ -276,9 +344,16 @@ __device__ __forceinline__ void pair_read_word(unsigned& dst, unsigned lds_word)
 // two masks.  So a tile's candidates are appended one tile late, the last tile's after the loop (one more barrier).
 // Registers: 24 query fragments in VGPRs, 40 in AGPRs.  (With 32 in VGPRs hipcc parked two in AGPRs and copied them back one
 // instruction ahead of their MFMA - asm text, no hazard padding: wrong k-steps.  tools/audit_ring.py reports that pattern.)
+// VARIANT 8 (I8): the int8 screen of the d = 768 bf16 full pass (kernels_screen8.h).  A row of 768 int8 values has the bytes of a d = 384
+// bf16 row, so it runs as D = 384 - the same ring, swizzle, fragment reads and query fragments (bytes 64 ks + 16 kq of the row
+// at both operands: whatever k order the i8 instruction gives the bytes of a lane, both operands share it and the integer dot
+// product is exact) - with the i8 MFMA, an integer threshold per (tile, query) from the tile's scalars and (row, query) pairs
+// as candidates (MfmaArgs::cand / count / cap: the screen's lists).
 template <int D, int NB, int VARIANT, bool SPARSE, bool F32 = false, bool PAIR = false, bool KSPLIT = false>
 __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a) {
     static_assert(!PAIR || (!SPARSE && !F32), "pairs exist for the bf16 full pass");
+    constexpr bool I8 = VARIANT == 8;
+    static_assert(!I8 || (D == 384 && !SPARSE && !F32 && !PAIR), "the screen is the full pass over 768-byte int8 rows");
     static_assert(!KSPLIT || (PAIR && NB == 4 && (VARIANT == 0 || VARIANT == 1 || VARIANT == 2 || VARIANT == 7) && D == 1024), "the k-split is the paired pass of d = 1024 with four query blocks per wave");
     constexpr int Deq = F32 ? 2 * D : D;                 // row length in 2-byte elements
     using dims = typename std::conditional<KSPLIT, MfmaDims<Deq, MfmaGeomKsplit<Deq>>, Mfma16Dims<Deq>>::type;
@@ -331,6 +406,8 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
 
     mfma_level_begin(a);
     uint4* stage = (uint4*)(smem + dims::kLds) + wave * kMfma16StageCap;          // this wave's staged candidates
+    uint2* stage8 = (uint2*)(smem + dims::kLds) + wave * kScreenStageCap;         // (I8: the same bytes, 8-byte entries)
+    static_assert(kScreenStageCap * 8 == kMfma16StageCap * 16, "the screen's entries fill the same LDS");
     u32* stage_cnt = (u32*)(smem + dims::kLds + 4 * kMfma16StageCap * 16) + wave;
     if (kStaged && lane == 0) *stage_cnt = 0;
     // k-split: the partial sums a wave hands to its partner, [wave][4][lane] x 16 bytes = 16 KB behind the pair's word; written
@@ -423,6 +500,19 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     float thr[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) thr[b] = mfma_level_thr(a, qid[b]);
+    // I8: the query's scalars (1 / s_q, |e_q|, |q|) and |thr| (0 where thr is infinite: an infinite threshold gives an infinite
+    // integer bound of the right sign)
+    float qs_r[I8 ? NB : 1], qs_e[I8 ? NB : 1], qs_n[I8 ? NB : 1], athr[I8 ? NB : 1];
+    if constexpr (I8) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const float4 m4 = a.scr_q[qid[b]];
+            qs_r[b] = m4.x;
+            qs_e[b] = m4.y;
+            qs_n[b] = m4.z;
+            athr[b] = __builtin_isinf(thr[b]) ? 0.0f : fabsf(thr[b]);
+        }
+    }
     // pin: the loads above complete here, outside the unit loop, in the register class the MFMA statements want
 #pragma unroll
     for (int f = 0; f < kFrags; ++f) {
@@ -431,6 +521,10 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     }
 #pragma unroll
     for (int b = 0; b < NB; ++b) asm volatile("" : "+v"(thr[b]));
+    if constexpr (I8) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) asm volatile("" : "+v"(qs_r[b]), "+v"(qs_e[b]), "+v"(qs_n[b]), "+v"(athr[b]));
+    }
 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -475,7 +569,12 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
 #define TS16_MMA(RB_, B_, KS_, AF_)                                                                        \
     do {                                                                                                   \
         constexpr int f_ = (B_) * kSteps + (KS_);                                                          \
-        if constexpr ((KS_) == 0) {                                                                        \
+        if constexpr (I8) {                                                                                \
+            if constexpr ((KS_) == 0 && f_ < kQV) mfma8_v_first(acc[RB_][B_], AF_, qv[f_ < kQV ? f_ : 0]);  \
+            else if constexpr ((KS_) == 0) mfma8_a_first(acc[RB_][B_], AF_, qa[f_ >= kQV ? f_ - kQV : 0]); \
+            else if constexpr (f_ < kQV) mfma8_v(acc[RB_][B_], AF_, qv[f_ < kQV ? f_ : 0]);                \
+            else mfma8_a(acc[RB_][B_], AF_, qa[f_ >= kQV ? f_ - kQV : 0]);                                 \
+        } else if constexpr ((KS_) == 0) {                                                                 \
             if constexpr (f_ < kQV) mfma16_v_first(TS16_ACC(RB_, B_), AF_, qv[f_ < kQV ? f_ : 0]);         \
             else mfma16_a_first(TS16_ACC(RB_, B_), AF_, qa[f_ >= kQV ? f_ - kQV : 0]);                     \
         } else {                                                                                           \
@@ -715,6 +814,19 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     u64 hit_[2] = {};
     // One tile.  (k-split: PAR = the tile's parity - the kept blocks of a tile stay where they are, in accK[PAR], while the next
     // tile's sums grow in accK[PAR ^ 1], instead of being copied: the loop below runs two tiles per trip.)
+    // I8: the scalars of the tile the loop is on, read for tile t + 1 behind the epilogue of tile t (scalar loads: they join no
+    // vector-memory count of the ring, and land long before the next epilogue)
+    // (through the constant address space: the kernel's own stores could alias a global pointer, and hipcc would make it a
+    // vector load - whose wait, vmcnt(0), drains the DMA ring at every tile)
+    typedef const __attribute__((address_space(4))) float* tile_scalars_ptr;
+    const tile_scalars_ptr scr_tile = (tile_scalars_ptr)a.scr_tile;
+    float4 tm = {0.0f, 0.0f, 0.0f, 0.0f};
+    auto tile_scalars = [&](int64_t lt) __attribute__((always_inline)) {
+        tm.x = scr_tile[4 * lt];
+        tm.y = scr_tile[4 * lt + 1];
+        tm.z = scr_tile[4 * lt + 2];
+    };
+    if constexpr (I8) tile_scalars(t0);
     auto tile = [&](auto par_c, const int t) __attribute__((always_inline)) {
         constexpr int par_ = decltype(par_c)::value;
         (void)par_;
@@ -782,6 +894,24 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
         if constexpr (kNoEpi) {
 #pragma unroll
             for (int b = 0; b < NB; ++b) asm volatile("" ::"v"(acc[0][b]), "v"(acc[1][b]));
+            return;
+        }
+        if constexpr (I8) {
+            int ithr[NB], ibest[NB];
+            u64 ihit[NB], iany = 0;
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                ithr[b] = screen_int_thr(tm.x, tm.y, tm.z, thr[b], athr[b], qs_r[b], qs_e[b], qs_n[b]);
+                ihit[b] = mfma8_block_test(acc[0][b], acc[1][b], ithr[b], ibest[b]);
+                iany |= ihit[b];
+            }
+            if (__builtin_expect(iany != 0, 0)) {
+                const int64_t row_base = (t0 + t) * kTileRows + 4 * kq;     // the screen runs over every tile (run 1, stride 1)
+#pragma unroll
+                for (int b = 0; b < NB; ++b)
+                    if (ihit[b] != 0) mfma8_append_block(acc[0][b], acc[1][b], ithr[b], ibest[b], qid[b], row_base, a, stage8, stage_cnt);
+            }
+            if (t + 1 < nt) tile_scalars(t0 + t + 1);
             return;
         }
         // lane holds rows 4 kq + {0..3} of both row blocks for query qid[b]
@@ -852,7 +982,14 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
 #undef TS16_FILL
 #undef TS16_PIECE
 #undef TS16_ISSUED
-    if (kStaged) {
+    if (I8) {
+        const u32 n = min(*stage_cnt, (u32)kScreenStageCap);
+        for (u32 e = lane; e < n; e += 64) {
+            const uint2 v = stage8[e];
+            const u32 pos = atomicAdd(&a.count[v.y], 1u);
+            if (pos < (u32)a.cap) a.cand[(int64_t)v.y * a.cap + pos] = (u64)v.x;
+        }
+    } else if (kStaged) {
         // the tile loop is over (no DMA in flight that a counted wait still watches): staged candidates -> shared lists
         const u32 n = min(*stage_cnt, (u32)kMfma16StageCap);
         for (u32 e = lane; e < n; e += 64) {

@@ -1,0 +1,194 @@
+// The int8 screen of the d = 768 bf16 full pass: every (row, query) pair is first scored with
+// v_mfma_i32_16x16x64_i8 on an int8 image of the corpus (half the bytes, half the matrix cycles of the bf16 pass), and only
+// the pairs whose certified upper bound reaches the query's threshold are rescored exactly, from the bf16 rows, with the
+// MFMA chain of the bf16 pass.  The pass still only has to guarantee that no row with exact score >= thr is dropped
+// (the "estimate, then verify" protocol of search_mfma.hip): the answers are bit for bit those of the unscreened pass.
+//
+// Quantisation (tile t = 32 rows, one scale; query q, one scale):
+//   s_t = max |x| / 127 over the tile, x~ = rint(x / s_t) in [-127, 127], e_x = x - s_t x~   (x = the stored bf16 values)
+//   s_q = max |q| / 127,               q~ = rint(q / s_q),                 e_q = q - s_q q~
+// so  x.q = s_t s_q (x~.q~) + s_t x~.e_q + e_x.q  and  |x.q - s_t s_q (x~.q~)| <= |s_t x~| |e_q| + |e_x| |q|.
+// The fp32 score S of the bf16 pass (exact bf16 products, 768 fp32 additions) is within g = 768 2^-22 |x| |q| of x.q
+// (four times the classic (n - 1) u bound on |x| |q| >= sum |x_i q_i|), and |x| <= |s_t x~| + |e_x|.  Hence
+//   S >= thr  =>  x~.q~ >= (thr - E_t |q| - X_t |e_q|) / (s_t s_q),   E_t = max|e_x| + 768 2^-22 (X_t + max|e_x|), X_t = max|s_t x~|
+// over the rows of the tile.  The tile scalars are computed in fp64 and rounded up; the integer threshold takes a relative
+// slack of 2^-18 of the terms' magnitude and one more unit (screen_int_thr, kernels_mfma16.h), far above the few fp32
+// roundings it is computed with.  A tile with a NaN / Inf value, or a query with one, has threshold INT_MIN: all of its
+// pairs are candidates and the exact rescore treats them as the bf16 pass does (a NaN score is never a candidate).
+#pragma once
+#include "kernels_mfma16.h"
+
+namespace ts {
+
+constexpr int kScreenD = 768;        // the width the screen serves (one int8 row = the bytes of a d = 384 bf16 row)
+constexpr int kScreenCap = 65536;    // screen candidates per query (~490 expected on Gaussian rows at 10M; 8 x the exact lists; more = exact re-run)
+constexpr float kScreenGamma = 768.0f * 0x1p-22f;   // bound of the bf16 pass's fp32 summation, relative to |x| |q|
+
+// fp64 -> fp32, never below the value (non-negative bounds that must not shrink)
+__device__ __forceinline__ float f32_up(double v) {
+    const float f = (float)v;
+    return (double)f >= v ? f : __uint_as_float(__float_as_uint(f) + 1u);
+}
+
+// One workgroup (4 waves) per tile: wave w quantises rows 8 w .. 8 w + 7, lane l elements l + 64 j of a row.
+// img: [tiles x 32 x 768] int8; meta: [tiles] {1 / s_t (NaN: non-finite value in the tile), E_t, X_t, 0}.
+__global__ void __launch_bounds__(256) quantize_tiles_kernel(const unsigned short* __restrict__ rows, signed char* __restrict__ img,
+                                                             float4* __restrict__ meta, int64_t tile0) {
+    __shared__ float red_max[4];
+    __shared__ int red_bad[4];
+    __shared__ double red_e[4], red_x[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t t = tile0 + blockIdx.x;
+    const unsigned short* src = rows + t * kTileRows * kScreenD;
+    float amax = 0.0f;
+    int bad = 0;
+    for (int r = 8 * wave; r < 8 * wave + 8; ++r)
+        for (int j = 0; j < kScreenD / 64; ++j) {
+            const float x = bf16_to_f32(src[r * kScreenD + lane + 64 * j]);
+            if (!(fabsf(x) <= 3.4028235e38f)) bad = 1;
+            else amax = fmaxf(amax, fabsf(x));
+        }
+    for (int o = 32; o > 0; o >>= 1) {
+        amax = fmaxf(amax, __shfl_xor(amax, o));
+        bad |= __shfl_xor(bad, o);
+    }
+    if (lane == 0) { red_max[wave] = amax; red_bad[wave] = bad; }
+    __syncthreads();
+    amax = fmaxf(fmaxf(red_max[0], red_max[1]), fmaxf(red_max[2], red_max[3]));
+    bad = red_bad[0] | red_bad[1] | red_bad[2] | red_bad[3];
+    const float s = amax > 0.0f ? amax / 127.0f : 1.0f;
+    double emax = 0.0, xmax = 0.0;
+    for (int r = 8 * wave; r < 8 * wave + 8; ++r) {
+        double ee = 0.0, xx = 0.0;
+        for (int j = 0; j < kScreenD / 64; ++j) {
+            const int c = lane + 64 * j;
+            const float x = bf16_to_f32(src[r * kScreenD + c]);
+            float qx = 0.0f;
+            if (fabsf(x) <= 3.4028235e38f) qx = fminf(127.0f, fmaxf(-127.0f, rintf(x / s)));
+            img[(t * kTileRows + r) * kScreenD + c] = (signed char)(int)qx;
+            const double sx = (double)s * (double)qx;
+            const double e = (double)x - sx;
+            ee += e * e;
+            xx += sx * sx;
+        }
+        ee = wave_sum_f64(ee);
+        xx = wave_sum_f64(xx);
+        emax = fmax(emax, sqrt(ee));
+        xmax = fmax(xmax, sqrt(xx));
+    }
+    if (lane == 0) { red_e[wave] = emax; red_x[wave] = xmax; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        emax = fmax(fmax(red_e[0], red_e[1]), fmax(red_e[2], red_e[3])) * (1.0 + 0x1p-40);
+        xmax = fmax(fmax(red_x[0], red_x[1]), fmax(red_x[2], red_x[3])) * (1.0 + 0x1p-40);
+        const float rs = bad ? __builtin_nanf("") : 1.0f / s;
+        meta[t] = make_float4(rs, f32_up(emax + (double)kScreenGamma * (xmax + emax) * (1.0 + 0x1p-20)), f32_up(xmax), 0.0f);
+    }
+}
+
+// One wave per query of the launch (256 workgroups): rows < nrows of q [nrows x 768] bf16 -> img [256 x 768] int8 and
+// meta {1 / s_q (NaN: non-finite value), |e_q|, |q|, 0}; zero rows past nrows.  Also empties the screen's lists.
+__global__ void __launch_bounds__(64) quantize_queries_kernel(const unsigned short* __restrict__ q, int nrows,
+                                                              signed char* __restrict__ img, float4* __restrict__ meta,
+                                                              u32* __restrict__ scount) {
+    const int lane = threadIdx.x, r = blockIdx.x;
+    float v[kScreenD / 64];
+    float amax = 0.0f;
+    int bad = 0;
+#pragma unroll
+    for (int j = 0; j < kScreenD / 64; ++j) {
+        v[j] = r < nrows ? bf16_to_f32(q[(int64_t)r * kScreenD + lane + 64 * j]) : 0.0f;
+        if (!(fabsf(v[j]) <= 3.4028235e38f)) bad = 1;
+        else amax = fmaxf(amax, fabsf(v[j]));
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        amax = fmaxf(amax, __shfl_xor(amax, o));
+        bad |= __shfl_xor(bad, o);
+    }
+    const float s = amax > 0.0f ? amax / 127.0f : 1.0f;
+    double ee = 0.0, qq = 0.0;
+#pragma unroll
+    for (int j = 0; j < kScreenD / 64; ++j) {
+        float qx = 0.0f;
+        if (fabsf(v[j]) <= 3.4028235e38f) qx = fminf(127.0f, fmaxf(-127.0f, rintf(v[j] / s)));
+        img[(int64_t)r * kScreenD + lane + 64 * j] = (signed char)(int)qx;
+        const double e = (double)v[j] - (double)s * (double)qx;
+        ee += e * e;
+        qq += (double)v[j] * (double)v[j];
+    }
+    ee = wave_sum_f64(ee);
+    qq = wave_sum_f64(qq);
+    if (lane == 0) {
+        meta[r] = make_float4(bad ? __builtin_nanf("") : 1.0f / s, f32_up(sqrt(ee) * (1.0 + 0x1p-40)), f32_up(sqrt(qq) * (1.0 + 0x1p-40)), 0.0f);
+        scount[r] = 0;
+    }
+}
+
+// Exact rescore of the screen's pairs.  Workgroup (q, y): its four waves take chunks of 16 of query q's screened rows in turn
+// (chunk 4 y + wave, then every 4 gridDim.y).  A chunk is the A operand of the bf16 pass's MFMA chain - 24 k-steps of
+// v_mfma_f32_16x16x32_bf16, k-step ks = elements 32 ks + 8 (lane >> 4) of row (lane & 15), the first with a zero accumulator -
+// against the query's own block of 16 queries as B, the query in column q & 15: the same operands at the same lanes as in
+// mfma16_topk_kernel<768, .>, so every score is bit-identical to the one the unscreened pass computes for that row.  Scores >= thr
+// go into the query's list of the final select.  A query whose screen list overflowed gets a count past `cap`: the select
+// sends it to the exact re-run.
+struct ScreenRescoreArgs {
+    const unsigned short* rows;   // bf16 [n_pad x 768]
+    const unsigned short* q;      // bf16 queries [>= 16 * ceil(nq / 16) x 768], as the pass multiplies them
+    const float* thr;             // [nq]
+    const u64* scand;             // [256][kScreenCap] screened rows
+    const u32* scount;            // [256]
+    u64* cand;                    // [256][cap] the final select's lists
+    u32* count;                   // [256]
+    int cap;
+};
+
+constexpr int kRescoreY = 8;      // workgroups per query
+
+__global__ void __launch_bounds__(256) screen_rescore_kernel(ScreenRescoreArgs a) {
+    const int q = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u32 raw = a.scount[q];
+    if (raw > (u32)kScreenCap) {
+        if (blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(&a.count[q], (u32)a.cap + 1u);
+        return;
+    }
+    const int m = (int)raw;
+    const int nchunks = (m + 15) >> 4;
+    int c = blockIdx.y * 4 + wave;
+    if (c >= nchunks) return;
+    const int r16 = lane & 15, kq = lane >> 4;
+    const float thr = a.thr[q];
+    constexpr int kSteps = kScreenD / 32;
+    bf16x8 qf[kSteps];
+    const bf16x8* pq = (const bf16x8*)(a.q + (int64_t)((q & ~15) + r16) * kScreenD + 8 * kq);
+#pragma unroll
+    for (int ks = 0; ks < kSteps; ++ks) qf[ks] = pq[4 * ks];
+    for (; c < nchunks; c += gridDim.y * 4) {
+        const int e = 16 * c + r16;
+        const u32 row = e < m ? (u32)a.scand[(int64_t)q * kScreenCap + e] : 0u;
+        const frag16* pr = (const frag16*)(a.rows + (int64_t)row * kScreenD + 8 * kq);
+        frag16 rf[kSteps];
+#pragma unroll
+        for (int ks = 0; ks < kSteps; ++ks) rf[ks] = pr[4 * ks];
+        f32x4 acc;
+        mfma16_v_first(acc, rf[0], qf[0]);
+#pragma unroll
+        for (int ks = 1; ks < kSteps; ++ks) mfma16_v(acc, rf[ks], qf[ks]);
+        asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc));   // wait states: MFMA result -> VALU reader
+        u32 rr[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rr[i] = (u32)__shfl((int)row, 4 * kq + i);
+        if (r16 == (q & 15)) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float s = acc[i];
+                if (16 * c + 4 * kq + i < m && s >= thr) {
+                    const u32 pos = atomicAdd(&a.count[q], 1u);
+                    if (pos < (u32)a.cap) a.cand[(int64_t)q * a.cap + pos] = make_key(s, rr[i]);
+                }
+            }
+        }
+    }
+}
+
+}  // namespace ts

@@ -202,6 +202,11 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
         HIP_TRY(hipStreamSynchronize(st));          // `equal` is a local; this happens once per (grid, size)
         ix->part_ntiles = full_tiles;
     }
+    // bf16 at d = 768 behind a threshold: the full pass runs as the int8 screen + exact rescore (kernels_screen8.h), the
+    // same candidates >= thr for the final select
+    const bool screen = shape16 && !pair && variant == 0 && lv.size() >= 2 && lv.back().stride == 1 && lv.back().run == 1 &&
+                        screen_usable(ix);
+    if (screen) TS_TRY(screen_prepare(ix, qmat, mfma_block_queries(ix, nq), st));
     for (size_t i = 0; i < lv.size(); ++i) {
         const bool full_pass = (i + 1 == lv.size());
         if (i == 0 && !full_pass && dense_sample && lv[0].ntiles * kTileRows <= kLevelSortMax) {
@@ -304,6 +309,8 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
             a.pair_lag = ix->knobs.get(K_MFMA_PAIR_LAG, 1);
         }
         a.dbg = nullptr;
+        a.scr_tile = nullptr;
+        a.scr_q = nullptr;
 #ifdef TS_DIAG
         if (variant >= 3) {
             if (!ix->dbg) HIP_TRY(hipMalloc((void**)&ix->dbg, 2048 * 4 * 4 * 8));
@@ -312,7 +319,8 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
 #endif
         hipEvent_t stop = full_pass ? prof_begin(ix, st, ix->n) : nullptr;  // only the full pass is bracketed
         int rc;
-        if (ix->dtype == TS_F32 && shape16) rc = launch_pass_mfma16_f32(ix->d, nb16, full_pass, grid, st, a);
+        if (screen && full_pass) rc = screen_full_pass(ix, nb16, nq, grid, st, a);
+        else if (ix->dtype == TS_F32 && shape16) rc = launch_pass_mfma16_f32(ix->d, nb16, full_pass, grid, st, a);
         else if (ix->dtype == TS_F32) rc = launch_pass_mfma32_f32(full_pass, variant, grid, st, a);
         else if (shape16) rc = launch_pass_mfma16(ix->d, nb16, full_pass, variant, grid, st, a);
         else rc = launch_pass_mfma32(ix->d, groups, full_pass, variant, grid, st, a);
