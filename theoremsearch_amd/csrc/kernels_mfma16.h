@@ -206,17 +206,40 @@ __device__ __forceinline__ u64 mfma8_block_test(const f32x4& a0, const f32x4& a1
     return mask;
 }
 
-// Integer threshold of one (tile, query) pair of the int8 screen (kernels_screen8.h has the derivation): every row of the tile
-// whose exact fp32 score can reach `thr` has an int8 dot product >= the returned value.  tm = the tile's scalars (1 / s_t,
-// coefficient of |q|, coefficient of |e_q|; 1 / s_t = NaN: the tile holds a non-finite value), qm = the query's (1 / s_q,
-// |e_q|, |q|; 1 / s_q = NaN: the query holds one); athr = |thr|, or 0 where thr is infinite.  Every step rounds towards
-// admitting more rows; NaN -> INT_MIN (every row of the tile is a candidate; the exact rescore decides).  No branch: the clamp
-// is two v_max / v_min (maxNum: a NaN operand yields the other one).
-__device__ __forceinline__ int screen_int_thr(float tx, float ty, float tz, float thr, float athr, float rq, float eq, float qn) {
-    const float sub = fmaf(ty, qn, tz * eq);
-    const float mag = athr + sub;
-    const float v = (thr - sub - mag * 0x1p-18f) * tx * rq;
-    return (int)floorf(fminf(fmaxf(v - 1.0f, -0x1p31f), 0x1p30f));
+// Integer thresholds of the int8 screen (kernels_screen8.h has the derivation and the rounding argument): every row of a tile
+// whose exact fp32 score can reach the query's `thr` has an int8 dot product >= the (tile, query) threshold.  The query's side
+// is folded once per launch: with rq = 1 / s_q, eq = |e_q|, qn = |q| (rq = NaN: the query holds a non-finite value) and
+// athr = |thr| (0 where thr is infinite),
+//   q1 = rq (thr - athr 2^-18),  q2 = rq qn (1 + 2^-18),  q3 = rq eq (1 + 2^-18)
+// in fp64, rounded to fp32 on the admitting side (q1 down, q2 and q3 up).
+__device__ __forceinline__ void screen_fold_query(float thr, float rq, float eq, float qn, float& q1, float& q2, float& q3) {
+    const double athr = __builtin_isinf(thr) ? 0.0 : fabs((double)thr);
+    const double v1 = (double)rq * ((double)thr - athr * 0x1p-18);
+    const double v2 = (double)rq * (double)qn * (1.0 + 0x1p-18);
+    const double v3 = (double)rq * (double)eq * (1.0 + 0x1p-18);
+    q1 = (float)v1;
+    q2 = (float)v2;
+    q3 = (float)v3;
+    if ((double)q1 > v1) q1 = nextafterf(q1, -__builtin_inff());      // (NaN compares false and stays NaN)
+    if ((double)q2 < v2) q2 = nextafterf(q2, __builtin_inff());
+    if ((double)q3 < v3) q3 = nextafterf(q3, __builtin_inff());
+}
+// The threshold of (tile, query) from the tile's scalars tm = (tx = 1 / s_t, ty = coefficient of |q|, tz = coefficient of
+// |e_q|; tx = NaN: the tile holds a non-finite value): floor(clamp(fma(tx, fma(-tz, q3, fma(-ty, q2, q1)), -1))), in four
+// pieces of at most two VALU instructions with fixed places between the MFMAs of the tile (TS16_THR8): none of it reads an
+// accumulator.  The clamp is v_max / v_min (maxNum: a NaN yields the other operand, so NaN -> INT_MIN: every row of the tile is
+// a candidate, the exact rescore decides); the literals are -2^31 and 2^30.
+template <int P>
+__device__ __forceinline__ void screen_thr_piece(int& t, const f32x4& tm, float q1, float q2, float q3) {
+    static_assert(P >= 0 && P < 4, "four pieces");
+    if constexpr (P == 0)
+        asm volatile("v_fma_f32 %0, -%1, %2, %3\n\tv_fma_f32 %0, -%4, %5, %0" : "=&v"(t) : "s"(tm[1]), "v"(q2), "v"(q1), "s"(tm[2]), "v"(q3));
+    else if constexpr (P == 1)
+        asm volatile("v_fma_f32 %0, %1, %0, -1.0\n\tv_max_f32 %0, 0xcf000000, %0" : "+v"(t) : "s"(tm[0]));
+    else if constexpr (P == 2)
+        asm volatile("v_min_f32 %0, 0x4e800000, %0\n\tv_floor_f32 %0, %0" : "+v"(t));
+    else
+        asm volatile("v_cvt_i32_f32 %0, %0" : "+v"(t));
 }
 
 // Append the passing scores of one query block (rare path: entered for a block only when some lane passed).  Written
@@ -317,7 +340,9 @@ __device__ __forceinline__ void pair_read_word(unsigned& dst, unsigned lds_word)
 // SHARES, not the length).  3 = product + clock probe: s_memtime / s_memrealtime around the tile loop into a.dbg
 // (4 words per workgroup: shader cycles, 100 MHz ticks, units, 0) - MI355X_MICROARCH.md "DVFS give-back" item 6.
 // 6 = product + s_sleep of ~256 cycles per unit (how much of an added idle cycle shows up as time under the power cap).
-// 8 = the int8 screen (below, I8).
+// 8 = the int8 screen (below, I8).  Its timing-only forms (the diagnostic build, I8 as well): 9 = no epilogue, 10 = cycle
+// stamps around the vmcnt wait, the barrier and the tile tail (the drain to the end of the epilogue; a.dbg as 5, the tail in
+// place of the DMA issue), 11 = clock probe (as 3), 12 = DMA stream only.
 // SPARSE only changes the symbol (sample levels show up under their own name in kernel traces).
 //
 // F32: the same kernel over an fp32 index (exact fp32: v_mfma_f32_16x16x4_f32, bit for bit an fmaf chain).  A row of D
@@ -352,14 +377,16 @@ __device__ __forceinline__ void pair_read_word(unsigned& dst, unsigned lds_word)
 template <int D, int NB, int VARIANT, bool SPARSE, bool F32 = false, bool PAIR = false, bool KSPLIT = false>
 __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a) {
     static_assert(!PAIR || (!SPARSE && !F32), "pairs exist for the bf16 full pass");
-    constexpr bool I8 = VARIANT == 8;
+    constexpr bool I8 = VARIANT >= 8 && VARIANT <= 12;
     static_assert(!I8 || (D == 384 && !SPARSE && !F32 && !PAIR), "the screen is the full pass over 768-byte int8 rows");
     static_assert(!KSPLIT || (PAIR && NB == 4 && (VARIANT == 0 || VARIANT == 1 || VARIANT == 2 || VARIANT == 7) && D == 1024), "the k-split is the paired pass of d = 1024 with four query blocks per wave");
     constexpr int Deq = F32 ? 2 * D : D;                 // row length in 2-byte elements
     using dims = typename std::conditional<KSPLIT, MfmaDims<Deq, MfmaGeomKsplit<Deq>>, Mfma16Dims<Deq>>::type;
-    constexpr bool kNoEpi = VARIANT == 1 || VARIANT == 7;
+    constexpr bool kNoEpi = VARIANT == 1 || VARIANT == 7 || VARIANT == 9;
     constexpr bool kNoDma = VARIANT == 7;
-    constexpr bool kNoMma = VARIANT == 2;
+    constexpr bool kNoMma = VARIANT == 2 || VARIANT == 12;
+    constexpr bool kStamps = VARIANT == 5 || VARIANT == 10;   // cycle stamps (general units only)
+    constexpr bool kProbe = VARIANT == 3 || VARIANT == 11;    // clock probe
     constexpr int kStepsAll = Deq / 32;                  // k-steps (16-byte chunks per lane) per tile
     constexpr int kUnitStepsAll = dims::kUnitK / 32;     // k-steps per unit
     constexpr int kSteps = KSPLIT ? kStepsAll / 2 : kStepsAll;               // ... of them, this wave's
@@ -500,17 +527,13 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     float thr[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) thr[b] = mfma_level_thr(a, qid[b]);
-    // I8: the query's scalars (1 / s_q, |e_q|, |q|) and |thr| (0 where thr is infinite: an infinite threshold gives an infinite
-    // integer bound of the right sign)
-    float qs_r[I8 ? NB : 1], qs_e[I8 ? NB : 1], qs_n[I8 ? NB : 1], athr[I8 ? NB : 1];
+    // I8: the query's side of the tile thresholds, folded once per launch from its scalars (1 / s_q, |e_q|, |q|) and thr
+    float fq1[I8 ? NB : 1], fq2[I8 ? NB : 1], fq3[I8 ? NB : 1];
     if constexpr (I8) {
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
             const float4 m4 = a.scr_q[qid[b]];
-            qs_r[b] = m4.x;
-            qs_e[b] = m4.y;
-            qs_n[b] = m4.z;
-            athr[b] = __builtin_isinf(thr[b]) ? 0.0f : fabsf(thr[b]);
+            screen_fold_query(thr[b], m4.x, m4.y, m4.z, fq1[b], fq2[b], fq3[b]);
         }
     }
     // pin: the loads above complete here, outside the unit loop, in the register class the MFMA statements want
@@ -523,7 +546,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     for (int b = 0; b < NB; ++b) asm volatile("" : "+v"(thr[b]));
     if constexpr (I8) {
 #pragma unroll
-        for (int b = 0; b < NB; ++b) asm volatile("" : "+v"(qs_r[b]), "+v"(qs_e[b]), "+v"(qs_n[b]), "+v"(athr[b]));
+        for (int b = 0; b < NB; ++b) asm volatile("" : "+v"(fq1[b]), "+v"(fq2[b]), "+v"(fq3[b]));
     }
 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -555,9 +578,10 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     for (int b = 0; b < NB; ++b) cnt[b] = 0;
     int slot = 0, u = 0;
     unsigned long long t_vm = 0, t_bar = 0, t_dma = 0, t_all0 = 0;   // VARIANT 5: cycle sums of the waits / DMA issue
-    if (VARIANT == 5) t_all0 = cycle_stamp();
+    unsigned long long t_tail = 0;                                   // VARIANT 10: cycles of the tile tails
+    if (kStamps) t_all0 = cycle_stamp();
     unsigned long long c_begin = 0, r_begin = 0;
-    if (VARIANT == 3) {
+    if (kProbe) {
         c_begin = __builtin_amdgcn_s_memtime();
         r_begin = __builtin_amdgcn_s_memrealtime();
         __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -637,6 +661,19 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
             if constexpr (fi_ == 9) ksplit_test_c(hit_[1], best_[1], thr[1]);                              \
         }                                                                                                  \
     } while (0)
+    // I8: piece P_ = 4 b + p of the NB thresholds of this tile (screen_thr_piece) in gap G_ of an even k-step (no DMA piece
+    // there): gaps behind the MFMAs of query blocks 1 and 2 (NB >= 3: four per k-step), of block 1 (NB = 2: two), or behind the
+    // two fragment reads (NB = 1, G_ = -2, -1) - k-steps 0 .. 6, 0 .. 4, 0 .. 6, 0 .. 2 at NB = 4, 3, 2, 1.
+#define TS16_THR8(KS_, G_)                                                                                 \
+    do {                                                                                                   \
+        if constexpr (I8 && !kNoEpi) {                                                                     \
+            constexpr int gpk_ = NB >= 3 ? 4 : 2;                                                          \
+            constexpr int g_ = NB == 1 ? (G_) + 2 : (G_);                                                  \
+            constexpr int P_ = ((KS_) / 2) * gpk_ + g_;                                                    \
+            if constexpr ((KS_) % 2 == 0 && g_ >= 0 && g_ < gpk_ && (NB == 1) == ((G_) < 0) && P_ < 4 * NB) \
+                screen_thr_piece<P_ & 3>(ithr[P_ >> 2], tmc, fq1[P_ >> 2], fq2[P_ >> 2], fq3[P_ >> 2]);       \
+        }                                                                                                  \
+    } while (0)
 #ifndef TS16_ORDER_A
 #define TS16_BF16_ORDER(KS_, R0_, N_, S_)                                                                  \
     do {                                                                                                   \
@@ -651,11 +688,17 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
             TS16_MMA(1, 1, KS_, af[R0_ + 1]); TS16_FILL(KS_, 3);                                           \
             break;                                                                                         \
         }                                                                                                  \
-        TS16_MMA(0, 0, KS_, af[R0_]); TS16_LOAD(0, N_);                                                    \
-        TS16_MMA(1, 0, KS_, af[R0_ + 1]); TS16_LOAD(1, N_);                                                \
-        if constexpr (NB > 1) { TS16_MMA(0, 1, KS_, af[R0_]); TS16_MMA(1, 1, KS_, af[R0_ + 1]); }          \
+        TS16_MMA(0, 0, KS_, af[R0_]); TS16_LOAD(0, N_); TS16_THR8(KS_, -2);                                \
+        TS16_MMA(1, 0, KS_, af[R0_ + 1]); TS16_LOAD(1, N_); TS16_THR8(KS_, -1);                            \
+        if constexpr (NB > 1) {                                                                            \
+            TS16_MMA(0, 1, KS_, af[R0_]); TS16_THR8(KS_, 0);                                               \
+            TS16_MMA(1, 1, KS_, af[R0_ + 1]); TS16_THR8(KS_, 1);                                           \
+        }                                                                                                  \
         TS16_PIECE(S_);                                                                                    \
-        if constexpr (NB > 2) { TS16_MMA(0, 2, KS_, af[R0_]); TS16_MMA(1, 2, KS_, af[R0_ + 1]); }          \
+        if constexpr (NB > 2) {                                                                            \
+            TS16_MMA(0, 2, KS_, af[R0_]); TS16_THR8(KS_, 2);                                               \
+            TS16_MMA(1, 2, KS_, af[R0_ + 1]); TS16_THR8(KS_, 3);                                           \
+        }                                                                                                  \
         if constexpr (NB > 3) { TS16_MMA(0, 3, KS_, af[R0_]); TS16_MMA(1, 3, KS_, af[R0_ + 1]); }          \
     } while (0)
 #else   /* A/B build: row-block major - the corpus fragment stays put for NB consecutive MFMAs */
@@ -763,13 +806,13 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
         na[0] = lds_base + nslot * kUnitBytes + xo[0] + koff; na[1] = lds_base + nslot * kUnitBytes + xo[1] + koff; \
         /* certify unit u + 1 (own pieces, then everyone's); every wave is past unit u - 1: its slot is free */ \
         unsigned long long s0_ = 0, s1_ = 0;                                                               \
-        if (VARIANT == 5) s0_ = cycle_stamp();                                                             \
+        if (kStamps) s0_ = cycle_stamp();                                                                  \
         if (u + 1 < nu && !kNoDma) wait_keep_units<kPieces>(issue_u - (u + 2));                            \
-        if (VARIANT == 5) s1_ = cycle_stamp();                                                             \
+        if (kStamps) s1_ = cycle_stamp();                                                                  \
         __builtin_amdgcn_s_barrier();                                                                      \
         asm volatile("" ::: "memory");                                                                     \
         if constexpr (KSPLIT && (UI) == 2) TS16_KSPLIT_FETCH();                                            \
-        if (VARIANT == 5) { t_vm += s1_ - s0_; t_bar += cycle_stamp() - s1_; }                             \
+        if (kStamps) { t_vm += s1_ - s0_; t_bar += cycle_stamp() - s1_; }                                  \
         if (VARIANT == 6) __builtin_amdgcn_s_sleep(4);   /* ~256 idle cycles per unit: elasticity of time to cycles */ \
         const bool do_issue = issue_u < nu && !kNoDma;                                                     \
         constexpr bool steady_ = false;                                                                    \
@@ -802,7 +845,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     static_assert(kSlots >= 3, "the steady part keeps kSlots - 3 units in flight behind its wait");
     // Steady tiles: every unit of the tile still has a unit to issue kSlots - 1 ahead.  (Runs of tiles, a shallower
     // ring and the stamped build go through the general units below.)
-    const int nt_steady = (a.run == 1 && ahead == kSlots - 1 && VARIANT != 5 && nu > ahead) ? (nu - ahead) / kUnits : 0;
+    const int nt_steady = (a.run == 1 && ahead == kSlots - 1 && !kStamps && nu > ahead) ? (nu - ahead) / kUnits : 0;
     const int64_t steady_jump = tile_bytes * a.tile_stride;
     unsigned soff = 0, poff = (unsigned)(kSlots - 1) * kUnitBytes;
     // the steady part addresses the stream as (uniform tile base in SGPRs) + (this lane's offset inside a tile); the
@@ -814,22 +857,30 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     u64 hit_[2] = {};
     // One tile.  (k-split: PAR = the tile's parity - the kept blocks of a tile stay where they are, in accK[PAR], while the next
     // tile's sums grow in accK[PAR ^ 1], instead of being copied: the loop below runs two tiles per trip.)
-    // I8: the scalars of the tile the loop is on, read for tile t + 1 behind the epilogue of tile t (scalar loads: they join no
-    // vector-memory count of the ring, and land long before the next epilogue)
+    // I8: the scalars of tile t (tmc: read by the threshold pieces among tile t's MFMAs) and of tile t + 1 (tmn), read two tiles
+    // ahead: the load of tile t + 2 goes out at the end of tile t and is pinned behind the ring's drain at the end of tile t + 1,
+    // where hipcc's own lgkmcnt(0) for it finds nothing left to wait for.  (Scalar loads join no vector-memory count of the ring;
+    // in flight they make the ring's counted lgkmcnt waits stricter, never looser.)
     // (through the constant address space: the kernel's own stores could alias a global pointer, and hipcc would make it a
     // vector load - whose wait, vmcnt(0), drains the DMA ring at every tile)
-    typedef const __attribute__((address_space(4))) float* tile_scalars_ptr;
+    // (one 16-byte load into one SGPR quadruple: loads of separate words get merged into pairs that the loop-carried registers
+    // do not line up with, and hipcc copies them - behind a wait for the load it has just issued)
+    typedef const __attribute__((address_space(4))) f32x4* tile_scalars_ptr;
     const tile_scalars_ptr scr_tile = (tile_scalars_ptr)a.scr_tile;
-    float4 tm = {0.0f, 0.0f, 0.0f, 0.0f};
-    auto tile_scalars = [&](int64_t lt) __attribute__((always_inline)) {
-        tm.x = scr_tile[4 * lt];
-        tm.y = scr_tile[4 * lt + 1];
-        tm.z = scr_tile[4 * lt + 2];
-    };
-    if constexpr (I8) tile_scalars(t0);
+    f32x4 tmc = {0.0f, 0.0f, 0.0f, 0.0f}, tmn = {0.0f, 0.0f, 0.0f, 0.0f};
+    auto tile_scalars = [&](f32x4& tm, int64_t lt) __attribute__((always_inline)) { tm = scr_tile[lt]; };
+    // I8: this tile's integer thresholds, computed among its MFMAs (piece 0 writes them; no initialisation: a loop of one
+    // trip here changes the code hipcc makes for the other instantiations)
+    int ithr[I8 ? NB : 1];
+    if constexpr (I8) {
+        tile_scalars(tmc, t0);
+        tile_scalars(tmn, t0 + (nt > 1 ? 1 : 0));
+        asm volatile("" : "+s"(tmc), "+s"(tmn));
+    }
     auto tile = [&](auto par_c, const int t) __attribute__((always_inline)) {
         constexpr int par_ = decltype(par_c)::value;
         (void)par_;
+        unsigned long long tail0 = 0;
         if (t < nt_steady) {
             TS16_UNIT_S(0);
             if constexpr (kUnits >= 2) TS16_UNIT_S(1 % kUnits);
@@ -867,6 +918,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
                 TS16_UNIT(6 % kUnits);
                 TS16_UNIT(7 % kUnits);
             }
+            if (VARIANT == 10) tail0 = cycle_stamp();
             if constexpr (!kNoMma) lds_ring_landed(af);
         }
         if constexpr (kNoMma) return;
@@ -897,11 +949,12 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
             return;
         }
         if constexpr (I8) {
-            int ithr[NB], ibest[NB];
+            // tile t + 1's scalars: landed behind the drain above
+            asm volatile("" : "+s"(tmn));
+            int ibest[NB];
             u64 ihit[NB], iany = 0;
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
-                ithr[b] = screen_int_thr(tm.x, tm.y, tm.z, thr[b], athr[b], qs_r[b], qs_e[b], qs_n[b]);
                 ihit[b] = mfma8_block_test(acc[0][b], acc[1][b], ithr[b], ibest[b]);
                 iany |= ihit[b];
             }
@@ -911,7 +964,9 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
                 for (int b = 0; b < NB; ++b)
                     if (ihit[b] != 0) mfma8_append_block(acc[0][b], acc[1][b], ithr[b], ibest[b], qid[b], row_base, a, stage8, stage_cnt);
             }
-            if (t + 1 < nt) tile_scalars(t0 + t + 1);
+            if (VARIANT == 10) t_tail += cycle_stamp() - tail0;
+            tmc = tmn;
+            tile_scalars(tmn, t0 + (t + 2 < nt ? t + 2 : nt - 1));
             return;
         }
         // lane holds rows 4 kq + {0..3} of both row blocks for query qid[b]
@@ -980,6 +1035,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
 #undef TS16_LOAD
 #undef TS16_BF16_ORDER
 #undef TS16_FILL
+#undef TS16_THR8
 #undef TS16_PIECE
 #undef TS16_ISSUED
     if (I8) {
@@ -1003,14 +1059,14 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     }
     if (!SPARSE && a.wg_ticks && threadIdx.x == 0 && qhalf == 0)
         a.wg_ticks[wg] = (unsigned)(__builtin_amdgcn_s_memrealtime() - wg_start);
-    if (VARIANT == 5 && a.dbg && lane == 0) {
+    if (kStamps && a.dbg && lane == 0) {
         unsigned long long* d = a.dbg + ((size_t)blockIdx.x * 4 + wave) * 4;
         d[0] = cycle_stamp() - t_all0;
         d[1] = t_vm;
         d[2] = t_bar;
-        d[3] = t_dma;
+        d[3] = VARIANT == 10 ? t_tail : t_dma;
     }
-    if (VARIANT == 3 && a.dbg && threadIdx.x == 0) {
+    if (kProbe && a.dbg && threadIdx.x == 0) {
         const unsigned long long c_end = __builtin_amdgcn_s_memtime();
         const unsigned long long r_end = __builtin_amdgcn_s_memrealtime();
         unsigned long long* d = a.dbg + (size_t)blockIdx.x * 4;

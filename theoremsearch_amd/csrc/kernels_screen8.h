@@ -11,10 +11,23 @@
 // The fp32 score S of the bf16 pass (exact bf16 products, 768 fp32 additions) is within g = 768 2^-22 |x| |q| of x.q
 // (four times the classic (n - 1) u bound on |x| |q| >= sum |x_i q_i|), and |x| <= |s_t x~| + |e_x|.  Hence
 //   S >= thr  =>  x~.q~ >= (thr - E_t |q| - X_t |e_q|) / (s_t s_q),   E_t = max|e_x| + 768 2^-22 (X_t + max|e_x|), X_t = max|s_t x~|
-// over the rows of the tile.  The tile scalars are computed in fp64 and rounded up; the integer threshold takes a relative
-// slack of 2^-18 of the terms' magnitude and one more unit (screen_int_thr, kernels_mfma16.h), far above the few fp32
-// roundings it is computed with.  A tile with a NaN / Inf value, or a query with one, has threshold INT_MIN: all of its
-// pairs are candidates and the exact rescore treats them as the bf16 pass does (a NaN score is never a candidate).
+// over the rows of the tile.  The tile scalars are computed in fp64 and rounded up (tx = 1 / s_t, ty = E_t, tz = X_t).
+//
+// The integer threshold (kernels_mfma16.h) takes a relative slack of 2^-18 of M = athr + ty qn + tz eq (athr = |thr|, 0 where
+// thr is infinite; qn = |q|, eq = |e_q|, rq = 1 / s_q) and one more unit:
+//   floor(tx (thr - athr 2^-18 - (ty qn + tz eq)(1 + 2^-18)) rq - 1) = floor(tx (Q1 - ty Q2 - tz Q3) - 1)
+// with the query's side folded once per launch (screen_fold_query): Q1 = rq (thr - athr 2^-18), Q2 = rq qn (1 + 2^-18),
+// Q3 = rq eq (1 + 2^-18), in fp64 and rounded to fp32 on the admitting side (Q1 down, Q2 and Q3 up).  Per (tile, query) there
+// are three fp32 FMAs, fma(-ty, Q2, Q1), fma(-tz, Q3, .), fma(tx, ., -1), each rounded to nearest.  Every operand and partial
+// result of the first two is bounded by R = rq M (1 + 2^-17), so each of them is off by at most 2^-24 R; the third adds at most
+// 2^-24 (tx R + 1).  Together with the fp32 reciprocals tx and rq (2^-24 each, relative) that is below 6 2^-24 tx R + 2^-24,
+// against the slack 2^-18 tx R = 64 2^-24 tx R plus the unit: the computed value stays below the certified bound, and floor
+// keeps it there.  (The replaced order, (thr - sub - (athr + sub) 2^-18) tx rq - 1 with sub in fp32, rounded about as often;
+// its thresholds and the folded ones differ by at most one unit - tests/test_screen8_fold_cpu.py.)
+//
+// A tile with a NaN / Inf value, or a query with one, has threshold INT_MIN (tx or rq is NaN; the clamp's maxNum turns the NaN
+// into -2^31): all of its pairs are candidates and the exact rescore treats them as the bf16 pass does (a NaN score is never a
+// candidate).  An infinite thr gives 2^30 (+inf: nothing passes) or INT_MIN (-inf: everything does).
 #pragma once
 #include "kernels_mfma16.h"
 

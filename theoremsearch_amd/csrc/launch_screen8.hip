@@ -11,8 +11,13 @@ bool screen_usable(const ts_index* ix) {
 }
 
 template <int NB>
-static int launch_screen8(int grid, hipStream_t st, const MfmaArgs& a) {
+static int launch_screen8(int grid, int variant, hipStream_t st, const MfmaArgs& a) {
     constexpr int lds = Mfma16Dims<384>::kLds + kMfma16StageBytes;
+#ifdef TS_DIAG
+    constexpr bool kDiag = NB == 4;     // the timing-only forms (VARIANT 9 .. 12) exist for the headline batch only
+#else
+    constexpr bool kDiag = false;       // ... and in the diagnostic build only (make diag)
+#endif
     static_assert(lds <= 160 * 1024, "DMA ring + staged candidates must fit the CU's LDS");
     static std::atomic<unsigned long long> attr_done{0};
     int dev = 0;
@@ -21,9 +26,24 @@ static int launch_screen8(int grid, hipStream_t st, const MfmaArgs& a) {
     if (!(attr_done.load(std::memory_order_acquire) & bit)) {
         HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<384, NB, 8, false>,
                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        if constexpr (kDiag) {
+            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<384, NB, 9, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<384, NB, 10, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<384, NB, 11, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<384, NB, 12, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        }
         attr_done.fetch_or(bit, std::memory_order_release);
     }
-    mfma16_topk_kernel<384, NB, 8, false><<<grid, kMfmaThreads, lds, st>>>(a);
+    if constexpr (kDiag) {
+        if (variant == 9) mfma16_topk_kernel<384, NB, 9, false><<<grid, kMfmaThreads, lds, st>>>(a);
+        else if (variant == 10) mfma16_topk_kernel<384, NB, 10, false><<<grid, kMfmaThreads, lds, st>>>(a);
+        else if (variant == 11) mfma16_topk_kernel<384, NB, 11, false><<<grid, kMfmaThreads, lds, st>>>(a);
+        else if (variant == 12) mfma16_topk_kernel<384, NB, 12, false><<<grid, kMfmaThreads, lds, st>>>(a);
+        else mfma16_topk_kernel<384, NB, 8, false><<<grid, kMfmaThreads, lds, st>>>(a);
+    } else {
+        (void)variant;
+        mfma16_topk_kernel<384, NB, 8, false><<<grid, kMfmaThreads, lds, st>>>(a);
+    }
     HIP_TRY(hipGetLastError());
     return TS_OK;
 }
@@ -65,7 +85,8 @@ int screen_prepare(ts_index* ix, const void* qmat, int nq_launch, hipStream_t st
 }
 
 // The full pass, screened: `a` is the bf16 pass's argument block (thresholds, row mask, tile table, the final select's lists).
-int screen_full_pass(ts_index* ix, int nb, int nq, int grid, hipStream_t st, const MfmaArgs& a) {
+// variant 9 .. 12: a timing-only form of the screen (diagnostic build; wrong results), 0: the product.
+int screen_full_pass(ts_index* ix, int nb, int nq, int grid, int variant, hipStream_t st, const MfmaArgs& a) {
     MfmaArgs s = a;
     s.corpus = (const unsigned short*)ix->scr_rows;
     s.q = (const unsigned short*)ix->scr_q;
@@ -76,10 +97,10 @@ int screen_full_pass(ts_index* ix, int nb, int nq, int grid, hipStream_t st, con
     s.scr_q = (const float4*)ix->scr_qmeta;
     int rc;
     switch (nb) {
-        case 1: rc = launch_screen8<1>(grid, st, s); break;
-        case 2: rc = launch_screen8<2>(grid, st, s); break;
-        case 3: rc = launch_screen8<3>(grid, st, s); break;
-        case 4: rc = launch_screen8<4>(grid, st, s); break;
+        case 1: rc = launch_screen8<1>(grid, variant, st, s); break;
+        case 2: rc = launch_screen8<2>(grid, variant, st, s); break;
+        case 3: rc = launch_screen8<3>(grid, variant, st, s); break;
+        case 4: rc = launch_screen8<4>(grid, variant, st, s); break;
         default: return fail(TS_ERR_INTERNAL, "no int8 screen with %d query blocks per wave", nb);
     }
     TS_TRY(rc);

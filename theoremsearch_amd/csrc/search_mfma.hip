@@ -184,8 +184,14 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
     // equal finishing times for the next search (kernels_select.h, rebalance_tiles).  The table starts as equal shares and
     // is re-made whenever the grid or the number of tiles changes.
     const int64_t full_tiles = lv.back().ntiles;
+    // TS_MFMA_VARIANT 9 .. 12: the timing-only forms of the int8 screen (diagnostic build only; launch_screen8.hip)
+#ifdef TS_DIAG
+    const bool screen_diag = variant >= 9 && variant <= 12;
+#else
+    const bool screen_diag = false;
+#endif
     const bool balance = shape16 && ix->knobs.get(K_MFMA_BALANCE, 1) != 0 && wgs >= 8 && wgs <= 256 && lv.back().stride == 1 &&
-                         lv.back().run == 1 && full_tiles >= 32 * (int64_t)wgs && (variant == 0 || variant == 3);
+                         lv.back().run == 1 && full_tiles >= 32 * (int64_t)wgs && (variant == 0 || variant == 3 || screen_diag);
     if (balance && (ix->part_g != wgs || ix->part_ntiles != full_tiles)) {
         if (ix->part_g != wgs) {
             if (ix->part) HIP_TRY(hipFree(ix->part));
@@ -204,7 +210,7 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
     }
     // bf16 at d = 768 behind a threshold: the full pass runs as the int8 screen + exact rescore (kernels_screen8.h), the
     // same candidates >= thr for the final select
-    const bool screen = shape16 && !pair && variant == 0 && lv.size() >= 2 && lv.back().stride == 1 && lv.back().run == 1 &&
+    const bool screen = shape16 && !pair && (variant == 0 || screen_diag) && lv.size() >= 2 && lv.back().stride == 1 && lv.back().run == 1 &&
                         screen_usable(ix);
     if (screen) TS_TRY(screen_prepare(ix, qmat, mfma_block_queries(ix, nq), st));
     for (size_t i = 0; i < lv.size(); ++i) {
@@ -319,7 +325,7 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
 #endif
         hipEvent_t stop = full_pass ? prof_begin(ix, st, ix->n) : nullptr;  // only the full pass is bracketed
         int rc;
-        if (screen && full_pass) rc = screen_full_pass(ix, nb16, nq, grid, st, a);
+        if (screen && full_pass) rc = screen_full_pass(ix, nb16, nq, grid, screen_diag ? variant : 0, st, a);
         else if (ix->dtype == TS_F32 && shape16) rc = launch_pass_mfma16_f32(ix->d, nb16, full_pass, grid, st, a);
         else if (ix->dtype == TS_F32) rc = launch_pass_mfma32_f32(full_pass, variant, grid, st, a);
         else if (shape16) rc = launch_pass_mfma16(ix->d, nb16, full_pass, variant, grid, st, a);
@@ -327,7 +333,7 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
         prof_end(stop, st);
         TS_TRY(rc);
 #ifdef TS_DIAG
-        if (a.dbg && full_pass && shape16 && variant == 3) {
+        if (a.dbg && full_pass && shape16 && (variant == 3 || (screen && variant == 11))) {
             // clock probe (MI355X_MICROARCH.md "DVFS give-back" item 6): shader cycles / 100 MHz ticks around the tile loop,
             // median over workgroups
             std::vector<unsigned long long> h((size_t)grid * 4);
@@ -363,16 +369,20 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
                     fprintf(stderr, "\n");
                 }
             }
-        } else if (a.dbg && full_pass && shape16 && variant == 5) {
+        } else if (a.dbg && full_pass && shape16 && (variant == 5 || (screen && variant == 10))) {
             std::vector<unsigned long long> h((size_t)grid * 16);
             HIP_TRY(hipStreamSynchronize(st));
             HIP_TRY(hipMemcpy(h.data(), a.dbg, h.size() * 8, hipMemcpyDeviceToHost));
-            const double units = (double)(lv.back().ntiles * MfmaDims<768>::kUnits) / grid;
+            const double units = (double)(lv.back().ntiles * (variant == 10 ? Mfma16Dims<384>::kUnits : MfmaDims<768>::kUnits)) / grid;
             for (int wv = 0; wv < 4; ++wv) {
                 double tot = 0, vm = 0, bar = 0, dma = 0;
                 for (int w = wv; w < grid * 4; w += 4) { tot += h[w * 4]; vm += h[w * 4 + 1]; bar += h[w * 4 + 2]; dma += h[w * 4 + 3]; }
-                fprintf(stderr, "[tsearch stamps16] wave %d per unit: total %.0f cycles, vmcnt wait %.0f, barrier wait %.0f, DMA issue %.0f (6 pieces; stamp cost ~40 each included)\n",
-                        wv, tot / grid / units, vm / grid / units, bar / grid / units, dma / grid / units);
+                if (variant == 10)
+                    fprintf(stderr, "[tsearch stamps8] wave %d per tile: total %.0f cycles, vmcnt wait %.0f, barrier wait %.0f, tile tail %.0f (drain to end of epilogue; stamp cost ~40 each included)\n",
+                            wv, tot / grid / units, vm / grid / units, bar / grid / units, dma / grid / units);
+                else
+                    fprintf(stderr, "[tsearch stamps16] wave %d per unit: total %.0f cycles, vmcnt wait %.0f, barrier wait %.0f, DMA issue %.0f (6 pieces; stamp cost ~40 each included)\n",
+                            wv, tot / grid / units, vm / grid / units, bar / grid / units, dma / grid / units);
             }
         } else if (a.dbg && full_pass && !shape16) {
             std::vector<unsigned long long> h((size_t)grid * 16);

@@ -90,7 +90,7 @@ def main():
             if ref is None:
                 ref = got
             same = bool(np.array_equal(ref, got))
-            pr = ix.probe_read() if kn.get("TS_MFMA_VARIANT") == 3 else None
+            pr = ix.probe_read() if kn.get("TS_MFMA_VARIANT") in (3, 11) else None   # 11: the int8 screen's probe
             if pr and pr["ghz"] > 0:
                 res[name]["probe"] = pr
                 print(f"   clock probe: {pr}", flush=True)
