@@ -310,7 +310,7 @@ int launch_pass_mfma16(int d, int nb, bool full_pass, int variant, int grid, hip
 int launch_pass_mfma16_f32(int d, int nb, bool full_pass, int grid, hipStream_t st, const ts::MfmaArgs& a);
 // the int8 screen + exact rescore in place of the bf16 full pass (launch_screen8.hip): screen_usable = this index, this launch
 bool screen_usable(const ts_index* ix);
-int screen_prepare(ts_index* ix, const void* qmat, int nq_launch, hipStream_t st);
+int screen_prepare(ts_index* ix, const void* qmat, int nq_launch, bool quantize_queries, hipStream_t st);
 int screen_full_pass(ts_index* ix, int nb, int nq, int grid, int variant, hipStream_t st, const ts::MfmaArgs& a);
 int launch_pass_mfma32(int d, int groups, bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);
 int launch_pass_mfma32_f32(bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);

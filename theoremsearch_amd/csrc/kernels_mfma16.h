@@ -56,6 +56,7 @@ constexpr int kMfma16PaceBytes = 256;
 // int8 screen (I8, kernels_screen8.h): the same LDS bytes hold 8-byte entries (row, query), twice as many per wave - a screened
 // wave expects ~125 of them against ~40 exact candidates of the bf16 pass
 constexpr int kScreenStageCap = 2 * kMfma16StageCap;
+constexpr int kScreenListCap = 65536;   // entries of a query's global list of screened rows (kScreenCap, kernels_screen8.h)
 
 // MFMA statements with pinned register classes: accumulator and corpus fragment in VGPRs, query fragment in a VGPR
 // ("v" forms) or an AGPR ("a" forms) quadruple.  No pads inside: the A fragment comes from a ds_read behind the k-step's
@@ -224,6 +225,50 @@ __device__ __forceinline__ void screen_fold_query(float thr, float rq, float eq,
     if ((double)q2 < v2) q2 = nextafterf(q2, __builtin_inff());
     if ((double)q3 < v3) q3 = nextafterf(q3, __builtin_inff());
 }
+// fp64 -> fp32, never below the value (non-negative bounds that must not shrink)
+__device__ __forceinline__ float f32_up(double v) {
+    const float f = (float)v;
+    return (double)f >= v ? f : __uint_as_float(__float_as_uint(f) + 1u);
+}
+// The screen's image of one query, by one wave (kernels_screen8.h has the quantisation): row r of q [nrows x 768] bf16 -> row r
+// of img [256 x 768] int8 and meta[r] = {1 / s_q (NaN: non-finite value), |e_q|, |q|, 0}; a zero row past nrows.  Also empties
+// the query's list of screened rows.  Needs nothing but the prepared queries, so it rides in whatever launch comes before the
+// screen: the extra workgroup row of the threshold sample (kernels_sample.h), or quantize_queries_kernel.
+__device__ __forceinline__ void screen_quantize_query(const unsigned short* __restrict__ q, int nrows, int r, int lane,
+                                                      signed char* __restrict__ img, float4* __restrict__ meta, u32* __restrict__ scount) {
+    constexpr int kD = 768;
+    float v[kD / 64];
+    float amax = 0.0f;
+    int bad = 0;
+#pragma unroll
+    for (int j = 0; j < kD / 64; ++j) {
+        v[j] = r < nrows ? bf16_to_f32(q[(int64_t)r * kD + lane + 64 * j]) : 0.0f;
+        if (!(fabsf(v[j]) <= 3.4028235e38f)) bad = 1;
+        else amax = fmaxf(amax, fabsf(v[j]));
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        amax = fmaxf(amax, __shfl_xor(amax, o));
+        bad |= __shfl_xor(bad, o);
+    }
+    const float s = amax > 0.0f ? amax / 127.0f : 1.0f;
+    double ee = 0.0, qq = 0.0;
+#pragma unroll
+    for (int j = 0; j < kD / 64; ++j) {
+        float qx = 0.0f;
+        if (fabsf(v[j]) <= 3.4028235e38f) qx = fminf(127.0f, fmaxf(-127.0f, rintf(v[j] / s)));
+        img[(int64_t)r * kD + lane + 64 * j] = (signed char)(int)qx;
+        const double e = (double)v[j] - (double)s * (double)qx;
+        ee += e * e;
+        qq += (double)v[j] * (double)v[j];
+    }
+    ee = wave_sum_f64(ee);
+    qq = wave_sum_f64(qq);
+    if (lane == 0) {
+        meta[r] = make_float4(bad ? __builtin_nanf("") : 1.0f / s, f32_up(sqrt(ee) * (1.0 + 0x1p-40)), f32_up(sqrt(qq) * (1.0 + 0x1p-40)), 0.0f);
+        scount[r] = 0;
+    }
+}
+
 // The threshold of (tile, query) from the tile's scalars tm = (tx = 1 / s_t, ty = coefficient of |q|, tz = coefficient of
 // |e_q|; tx = NaN: the tile holds a non-finite value): floor(clamp(fma(tx, fma(-tz, q3, fma(-ty, q2, q1)), -1))), in four
 // pieces of at most two VALU instructions with fixed places between the MFMAs of the tile (TS16_THR8): none of it reads an
@@ -281,27 +326,57 @@ __device__ __forceinline__ void mfma16_append_block(const f32x4& a0, const f32x4
     }
 }
 
-// The int8 screen's form of the rare path: (row, query) pairs whose dot product reaches the tile's integer threshold, staged
-// as 8-byte entries; the row mask and the padding rows are tested here, the exact score by the rescore.
-__device__ __forceinline__ void mfma8_append_block(const f32x4& a0, const f32x4& a1, int thr, int m, int qid, int64_t row_base,
-                                                   const MfmaArgs& a, uint2* stage, u32* stage_cnt) {
-    if (m >= thr && qid < a.nq_real) {
+// The int8 screen's form of the rare path: (row, query) pairs whose dot product reaches the tile's integer threshold, staged as
+// 8-byte entries (row, query) in the wave's own LDS list; the exact score is the rescore's business.  The screen admits eight
+// times the pairs of the bf16 pass, and a wave on this path holds up the other three at the next barrier, so it waits for
+// nothing: the list belongs to one wave, hence an entry's place is a wave-uniform fill count (`scnt`, an SGPR that lives through
+// the whole tile loop; no LDS counter, no atomic) plus the lane's rank among the passing lanes.  Per accumulator value: one
+// compare into a lane mask, a scalar branch over the (usual) empty mask, v_mbcnt, one ds_write_b64, scnt += popcount.  The
+// ds_write stays in flight - nobody reads the list before the flush behind the tile loop - and an LDS operation in flight only
+// makes the fragment ring's counted lgkmcnt waits stricter, never looser (LDS returns in order: "at most N outstanding" then
+// certifies the ring's reads and this write), the argument the tile-scalar load already relies on.
+// CHECKED: the tile may hold rows >= n (the corpus's last tile) or the search has a row mask (tested before an entry is
+// staged: masked-off rows would fill the list up to ten times faster); everything else takes the unchecked form.  A tile is one
+// word of the row mask, so the caller reads it once per tile with a SCALAR load (no vector-memory operation: the DMA ring's
+// vmcnt queue is left alone), clears the bits of rows >= n and hands every lane its eight bits: `live` bit (g & 3) + 16 (g >> 2)
+// = row g of this lane.  A value is looked up there only once some lane's score has passed.
+// Padding queries (qid >= nq_real) have threshold 2^30 except in a tile with a non-finite value (INT_MIN): no dot product of
+// 768 int8 pairs reaches INT_MAX, which is what they are compared with here.
+// A full list sends the wave's further pairs straight to the queries' global lists (vector memory: the DMA ring's counted
+// waits see two operations more and wait longer - slow, rare, exact).
+// (The pointers are spelled as global-memory pointers: they come out of pinned SGPRs, where hipcc no longer sees that they were
+// kernel arguments and would fall back to flat instructions, which count in both wait queues.)
+typedef __attribute__((address_space(1))) u32* screen_u32_gptr;
+typedef __attribute__((address_space(1))) u64* screen_u64_gptr;
+typedef const __attribute__((address_space(4))) u32* screen_mask_cptr;   // (constant address space: a scalar load)
+template <bool CHECKED>
+__device__ __forceinline__ void mfma8_append_block(const f32x4& a0, const f32x4& a1, int thr, int qid, u32 row_base, u32& scnt,
+                                                   uint2* stage, u32 live, u32 nq_real, screen_u32_gptr count, screen_u64_gptr cand) {
+    const int thr_q = (u32)qid < nq_real ? thr : 0x7fffffff;
 #pragma unroll
-        for (int g = 0; g < 8; ++g) {
-            const int s = __builtin_bit_cast(int, (g < 4) ? a0[g & 3] : a1[g & 3]);
-            if (s >= thr) {
-                const int64_t row = row_base + (g & 3) + 16 * (g >> 2);
-                if (row < a.n && (!a.row_mask || ((a.row_mask[row >> 5] >> (row & 31)) & 1u))) {
-                    const u32 at = atomicAdd(stage_cnt, 1u);
-                    if (at < (u32)kScreenStageCap) {
-                        stage[at] = make_uint2((u32)row, (u32)qid);
-                    } else {                                                       // list full: straight to the query's list
-                        const u32 pos = atomicAdd(&a.count[qid], 1u);
-                        if (pos < (u32)a.cap) a.cand[(int64_t)qid * a.cap + pos] = (u64)row;
-                    }
-                }
+    for (int g = 0; g < 8; ++g) {
+        const int s = __builtin_bit_cast(int, (g < 4) ? a0[g & 3] : a1[g & 3]);
+        const u32 row = row_base + (g & 3) + 16 * (g >> 2);
+        bool pass = s >= thr_q;
+        if constexpr (CHECKED) {
+            if (__builtin_amdgcn_ballot_w64(pass) == 0) continue;
+            pass = pass && ((live >> ((g & 3) + 16 * (g >> 2))) & 1u) != 0;
+        }
+        const u64 m = __builtin_amdgcn_ballot_w64(pass);
+        if (m == 0) continue;
+        const u32 at = scnt + __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u));
+        const u32 np = (u32)__builtin_popcountll(m);
+        if (__builtin_expect(scnt + np <= (u32)kScreenStageCap, 1)) {
+            if (pass) stage[at] = make_uint2(row, (u32)qid);
+        } else if (pass) {
+            if (at < (u32)kScreenStageCap) {
+                stage[at] = make_uint2(row, (u32)qid);
+            } else {                                                           // list full: straight to the query's list
+                const u32 pos = __hip_atomic_fetch_add(&count[qid], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (pos < (u32)kScreenListCap) cand[(int64_t)qid * kScreenListCap + pos] = (u64)row;
             }
         }
+        scnt += np;
     }
 }
 
@@ -342,7 +417,10 @@ __device__ __forceinline__ void pair_read_word(unsigned& dst, unsigned lds_word)
 // 6 = product + s_sleep of ~256 cycles per unit (how much of an added idle cycle shows up as time under the power cap).
 // 8 = the int8 screen (below, I8).  Its timing-only forms (the diagnostic build, I8 as well): 9 = no epilogue, 10 = cycle
 // stamps around the vmcnt wait, the barrier and the tile tail (the drain to the end of the epilogue; a.dbg as 5, the tail in
-// place of the DMA issue), 11 = clock probe (as 3), 12 = DMA stream only.
+// place of the DMA issue), 11 = clock probe (as 3), 12 = DMA stream only, 13 = the block test without the append path and the
+// flush (the screen's form of 4: product - 13 = what the admitted pairs cost inside the launch, 13 - 9 = the fall-through tail).
+// 14 = the screen of a search with a row mask (a product kernel): 8 holds no code that reads MfmaArgs::row_mask; 14 and the
+// product-with-instruments forms 10, 11 test the mask (when there is one) before a pair is staged.
 // SPARSE only changes the symbol (sample levels show up under their own name in kernel traces).
 //
 // F32: the same kernel over an fp32 index (exact fp32: v_mfma_f32_16x16x4_f32, bit for bit an fmaf chain).  A row of D
@@ -377,7 +455,8 @@ __device__ __forceinline__ void pair_read_word(unsigned& dst, unsigned lds_word)
 template <int D, int NB, int VARIANT, bool SPARSE, bool F32 = false, bool PAIR = false, bool KSPLIT = false>
 __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a) {
     static_assert(!PAIR || (!SPARSE && !F32), "pairs exist for the bf16 full pass");
-    constexpr bool I8 = VARIANT >= 8 && VARIANT <= 12;
+    constexpr bool I8 = VARIANT >= 8 && VARIANT <= 14;
+    constexpr bool kMasked8 = I8 && VARIANT != 8;           // the row mask is looked at (8: the unmasked product)
     static_assert(!I8 || (D == 384 && !SPARSE && !F32 && !PAIR), "the screen is the full pass over 768-byte int8 rows");
     static_assert(!KSPLIT || (PAIR && NB == 4 && (VARIANT == 0 || VARIANT == 1 || VARIANT == 2 || VARIANT == 7) && D == 1024), "the k-split is the paired pass of d = 1024 with four query blocks per wave");
     constexpr int Deq = F32 ? 2 * D : D;                 // row length in 2-byte elements
@@ -436,7 +515,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     uint2* stage8 = (uint2*)(smem + dims::kLds) + wave * kScreenStageCap;         // (I8: the same bytes, 8-byte entries)
     static_assert(kScreenStageCap * 8 == kMfma16StageCap * 16, "the screen's entries fill the same LDS");
     u32* stage_cnt = (u32*)(smem + dims::kLds + 4 * kMfma16StageCap * 16) + wave;
-    if (kStaged && lane == 0) *stage_cnt = 0;
+    if (kStaged && !I8 && lane == 0) *stage_cnt = 0;       // (I8: the fill count lives in an SGPR, see mfma8_append_block)
     // k-split: the partial sums a wave hands to its partner, [wave][4][lane] x 16 bytes = 16 KB behind the pair's word; written
     // at the end of a tile, fetched by the partner behind the third unit barrier of the next tile (into `got`: an asynchronous
     // read like the ring's, long landed when the tile ends) - a barrier between every write and its read, and one between
@@ -872,10 +951,29 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     // I8: this tile's integer thresholds, computed among its MFMAs (piece 0 writes them; no initialisation: a loop of one
     // trip here changes the code hipcc makes for the other instantiations)
     int ithr[I8 ? NB : 1];
+    // I8: what the append path needs, wave-uniform and in SGPRs from here to the flush - no kernel argument is read again
+    // inside the tile loop.  scnt = entries in this wave's list; tiles >= t_chk of this workgroup may hold rows >= n (the
+    // corpus's last tile) and take the checked form of the path; rows are 32-bit here (n_pad < 2^32).
+    u32 scnt = 0, s_n = 0, s_nq = 0;
+    int t_chk = 0;
+    screen_u32_gptr s_count = nullptr;
+    screen_u64_gptr s_cand = nullptr;
+    screen_mask_cptr s_mask = nullptr;
     if constexpr (I8) {
         tile_scalars(tmc, t0);
         tile_scalars(tmn, t0 + (nt > 1 ? 1 : 0));
         asm volatile("" : "+s"(tmc), "+s"(tmn));
+        const int64_t whole = a.n / kTileRows - t0;      // this workgroup's tiles in front of the first one with padding rows
+        t_chk = whole < (int64_t)nt ? (whole > 0 ? (int)whole : 0) : nt;
+        s_n = (u32)a.n;
+        s_nq = (u32)a.nq_real;
+        s_count = (screen_u32_gptr)a.count;
+        s_cand = (screen_u64_gptr)a.cand;
+        asm volatile("" : "+s"(scnt), "+s"(t_chk), "+s"(s_n), "+s"(s_nq), "+s"(s_count), "+s"(s_cand));
+        if constexpr (kMasked8) {
+            s_mask = (screen_mask_cptr)a.row_mask;
+            asm volatile("" : "+s"(s_mask));
+        }
     }
     auto tile = [&](auto par_c, const int t) __attribute__((always_inline)) {
         constexpr int par_ = decltype(par_c)::value;
@@ -958,11 +1056,28 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
                 ihit[b] = mfma8_block_test(acc[0][b], acc[1][b], ithr[b], ibest[b]);
                 iany |= ihit[b];
             }
-            if (__builtin_expect(iany != 0, 0)) {
-                const int64_t row_base = (t0 + t) * kTileRows + 4 * kq;     // the screen runs over every tile (run 1, stride 1)
+            if constexpr (VARIANT == 13) {           // diagnostic: the test without the append path
+                asm volatile("" ::"s"(iany));
+            } else if (__builtin_expect(iany != 0, 0)) {
+                const u32 row_base = ((u32)t0 + (u32)t) * kTileRows + 4 * kq;   // the screen runs over every tile (run 1, stride 1)
+                if (kMasked8 || t >= t_chk) {
+                    // the tile's rows that may be returned: its word of the row mask (all of them without a mask), less rows >= n
+                    const u32 tile_row = ((u32)t0 + (u32)t) * kTileRows;
+                    u32 word = 0xffffffffu;
+                    if (tile_row >= s_n) word = 0u;
+                    else if (kMasked8 && s_mask != nullptr) word = s_mask[tile_row >> 5];
+                    if (tile_row < s_n && s_n - tile_row < (u32)kTileRows) word &= (1u << (s_n - tile_row)) - 1u;
+                    const u32 live = word >> (4 * kq);
 #pragma unroll
-                for (int b = 0; b < NB; ++b)
-                    if (ihit[b] != 0) mfma8_append_block(acc[0][b], acc[1][b], ithr[b], ibest[b], qid[b], row_base, a, stage8, stage_cnt);
+                    for (int b = 0; b < NB; ++b)
+                        if (ihit[b] != 0)
+                            mfma8_append_block<true>(acc[0][b], acc[1][b], ithr[b], qid[b], row_base, scnt, stage8, live, s_nq, s_count, s_cand);
+                } else {
+#pragma unroll
+                    for (int b = 0; b < NB; ++b)
+                        if (ihit[b] != 0)
+                            mfma8_append_block<false>(acc[0][b], acc[1][b], ithr[b], qid[b], row_base, scnt, stage8, 0u, s_nq, s_count, s_cand);
+                }
             }
             if (VARIANT == 10) t_tail += cycle_stamp() - tail0;
             tmc = tmn;
@@ -1038,14 +1153,15 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
 #undef TS16_THR8
 #undef TS16_PIECE
 #undef TS16_ISSUED
-    if (I8) {
-        const u32 n = min(*stage_cnt, (u32)kScreenStageCap);
+    if (I8 && VARIANT != 13) {
+        // (this wave's own writes, read back by the wave that made them: LDS works them off in order)
+        const u32 n = min(scnt, (u32)kScreenStageCap);
         for (u32 e = lane; e < n; e += 64) {
             const uint2 v = stage8[e];
-            const u32 pos = atomicAdd(&a.count[v.y], 1u);
-            if (pos < (u32)a.cap) a.cand[(int64_t)v.y * a.cap + pos] = (u64)v.x;
+            const u32 pos = __hip_atomic_fetch_add(&s_count[v.y], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (pos < (u32)kScreenListCap) s_cand[(int64_t)v.y * kScreenListCap + pos] = (u64)v.x;
         }
-    } else if (kStaged) {
+    } else if (kStaged && !I8) {
         // the tile loop is over (no DMA in flight that a counted wait still watches): staged candidates -> shared lists
         const u32 n = min(*stage_cnt, (u32)kMfma16StageCap);
         for (u32 e = lane; e < n; e += 64) {

@@ -43,15 +43,23 @@ struct SampleArgs {
     const unsigned* wg_ticks;
     int part_g;
     float part_gain;
+    // optional: the int8 screen's image of this launch's queries (screen_quantize_query, kernels_mfma16.h; bf16 at d = 768),
+    // made by the workgroups of the extra row (grid.y = chunks + 1 then) - it needs only `q`, and the screen runs behind the
+    // select that follows this launch
+    signed char* scr_qimg;
+    float4* scr_qmeta;
+    u32* scr_count;
+    int scr_nrows;            // rows of q that are queries of the launch (the image has kMfmaQ rows, zero past them)
 };
 
 constexpr int kSampleRowPad = 16;                                   // bytes: rows land 4 banks apart, the 16-row reads spread out
 constexpr int sample_lds_bytes(int rows, int row_bytes) { return rows * (row_bytes + kSampleRowPad); }
 
 // RB = row blocks of 16 per workgroup (2: 32 rows).  grid = (row_stride / (16 RB), query chunks of 64 [+ 1]), 256 threads,
-// dynamic LDS = sample_lds_bytes(16 RB, ld * elem).  Row y = chunks of the grid exists when `part` is set: its first
-// workgroup moves the tile boundaries of the PREVIOUS search's full pass (rebalance_tiles, common.h) while the others score
-// - the job used to ride on the empty re-run launch behind the pass, where it was that launch's whole duration.
+// dynamic LDS = sample_lds_bytes(16 RB, ld * elem).  Row y = chunks of the grid exists when `part` or `scr_qimg` is set: its
+// first workgroup moves the tile boundaries of the PREVIOUS search's full pass (rebalance_tiles, common.h) while the others
+// score - the job used to ride on the empty re-run launch behind the pass, where it was that launch's whole duration - and
+// all of its workgroups share out the queries of the int8 screen's image, a wave per query (a launch of its own before).
 template <bool F32, int RB>
 __global__ void __launch_bounds__(256) sample_scores_kernel(SampleArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char srows[];
@@ -61,6 +69,11 @@ __global__ void __launch_bounds__(256) sample_scores_kernel(SampleArgs a) {
     const int nchunks = (a.nq + 63) / 64;
     if ((int)blockIdx.y >= nchunks) {
         if (blockIdx.x == 0 && a.part) rebalance_tiles(a.part, a.wg_ticks, a.part_g, a.part_gain, (double*)srows);
+        if constexpr (!F32) {
+            if (a.scr_qimg)
+                for (int r = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6); r < kMfmaQ; r += (int)gridDim.x * 4)
+                    screen_quantize_query((const unsigned short*)a.q, a.scr_nrows, r, (int)(threadIdx.x & 63), a.scr_qimg, a.scr_qmeta, a.scr_count);
+        }
         return;
     }
     constexpr int kRows = 16 * RB;

@@ -34,14 +34,8 @@
 namespace ts {
 
 constexpr int kScreenD = 768;        // the width the screen serves (one int8 row = the bytes of a d = 384 bf16 row)
-constexpr int kScreenCap = 65536;    // screen candidates per query (~490 expected on Gaussian rows at 10M; 8 x the exact lists; more = exact re-run)
+constexpr int kScreenCap = kScreenListCap;   // screen candidates per query (~490 expected on Gaussian rows at 10M; 8 x the exact lists; more = exact re-run)
 constexpr float kScreenGamma = 768.0f * 0x1p-22f;   // bound of the bf16 pass's fp32 summation, relative to |x| |q|
-
-// fp64 -> fp32, never below the value (non-negative bounds that must not shrink)
-__device__ __forceinline__ float f32_up(double v) {
-    const float f = (float)v;
-    return (double)f >= v ? f : __uint_as_float(__float_as_uint(f) + 1u);
-}
 
 // One workgroup (4 waves) per tile: wave w quantises rows 8 w .. 8 w + 7, lane l elements l + 64 j of a row.
 // img: [tiles x 32 x 768] int8; meta: [tiles] {1 / s_t (NaN: non-finite value in the tile), E_t, X_t, 0}.
@@ -99,51 +93,24 @@ __global__ void __launch_bounds__(256) quantize_tiles_kernel(const unsigned shor
     }
 }
 
-// One wave per query of the launch (256 workgroups): rows < nrows of q [nrows x 768] bf16 -> img [256 x 768] int8 and
-// meta {1 / s_q (NaN: non-finite value), |e_q|, |q|, 0}; zero rows past nrows.  Also empties the screen's lists.
+// One wave per query of the launch (256 workgroups): screen_quantize_query (kernels_mfma16.h) as a launch of its own - for
+// searches whose threshold does not come from the dense sample, whose launch carries this work otherwise (kernels_sample.h).
 __global__ void __launch_bounds__(64) quantize_queries_kernel(const unsigned short* __restrict__ q, int nrows,
                                                               signed char* __restrict__ img, float4* __restrict__ meta,
                                                               u32* __restrict__ scount) {
-    const int lane = threadIdx.x, r = blockIdx.x;
-    float v[kScreenD / 64];
-    float amax = 0.0f;
-    int bad = 0;
-#pragma unroll
-    for (int j = 0; j < kScreenD / 64; ++j) {
-        v[j] = r < nrows ? bf16_to_f32(q[(int64_t)r * kScreenD + lane + 64 * j]) : 0.0f;
-        if (!(fabsf(v[j]) <= 3.4028235e38f)) bad = 1;
-        else amax = fmaxf(amax, fabsf(v[j]));
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        amax = fmaxf(amax, __shfl_xor(amax, o));
-        bad |= __shfl_xor(bad, o);
-    }
-    const float s = amax > 0.0f ? amax / 127.0f : 1.0f;
-    double ee = 0.0, qq = 0.0;
-#pragma unroll
-    for (int j = 0; j < kScreenD / 64; ++j) {
-        float qx = 0.0f;
-        if (fabsf(v[j]) <= 3.4028235e38f) qx = fminf(127.0f, fmaxf(-127.0f, rintf(v[j] / s)));
-        img[(int64_t)r * kScreenD + lane + 64 * j] = (signed char)(int)qx;
-        const double e = (double)v[j] - (double)s * (double)qx;
-        ee += e * e;
-        qq += (double)v[j] * (double)v[j];
-    }
-    ee = wave_sum_f64(ee);
-    qq = wave_sum_f64(qq);
-    if (lane == 0) {
-        meta[r] = make_float4(bad ? __builtin_nanf("") : 1.0f / s, f32_up(sqrt(ee) * (1.0 + 0x1p-40)), f32_up(sqrt(qq) * (1.0 + 0x1p-40)), 0.0f);
-        scount[r] = 0;
-    }
+    screen_quantize_query(q, nrows, (int)blockIdx.x, (int)threadIdx.x, img, meta, scount);
 }
 
 // Exact rescore of the screen's pairs.  Workgroup (q, y): its four waves take chunks of 16 of query q's screened rows in turn
 // (chunk 4 y + wave, then every 4 gridDim.y).  A chunk is the A operand of the bf16 pass's MFMA chain - 24 k-steps of
 // v_mfma_f32_16x16x32_bf16, k-step ks = elements 32 ks + 8 (lane >> 4) of row (lane & 15), the first with a zero accumulator -
-// against the query's own block of 16 queries as B, the query in column q & 15: the same operands at the same lanes as in
-// mfma16_topk_kernel<768, .>, so every score is bit-identical to the one the unscreened pass computes for that row.  Scores >= thr
-// go into the query's list of the final select.  A query whose screen list overflowed gets a count past `cap`: the select
-// sends it to the exact re-run.
+// against the query as B, read from column q & 15 as in its own block of 16 queries: for that column the same operands at the
+// same lanes as in mfma16_topk_kernel<768, .>, so every score is bit-identical to the one the unscreened pass computes for that
+// row.  (A column of D depends on its own column of B only, so the other fifteen columns hold the query too instead of its
+// block's other queries: 1.5 KB of query per wave from one cache line set instead of 24 KB - most waves multiply one chunk,
+// and the query block was as many bytes as the rows.)  The chunk's entries and row gathers - the long way, to HBM - go out
+// before the query's fragments.  Scores >= thr go into the query's list of the final select.  A query whose screen list
+// overflowed gets a count past `cap`: the select sends it to the exact re-run.
 struct ScreenRescoreArgs {
     const unsigned short* rows;   // bf16 [n_pad x 768]
     const unsigned short* q;      // bf16 queries [>= 16 * ceil(nq / 16) x 768], as the pass multiplies them
@@ -170,19 +137,27 @@ __global__ void __launch_bounds__(256) screen_rescore_kernel(ScreenRescoreArgs a
     int c = blockIdx.y * 4 + wave;
     if (c >= nchunks) return;
     const int r16 = lane & 15, kq = lane >> 4;
-    const float thr = a.thr[q];
     constexpr int kSteps = kScreenD / 32;
-    bf16x8 qf[kSteps];
-    const bf16x8* pq = (const bf16x8*)(a.q + (int64_t)((q & ~15) + r16) * kScreenD + 8 * kq);
-#pragma unroll
-    for (int ks = 0; ks < kSteps; ++ks) qf[ks] = pq[4 * ks];
-    for (; c < nchunks; c += gridDim.y * 4) {
-        const int e = 16 * c + r16;
-        const u32 row = e < m ? (u32)a.scand[(int64_t)q * kScreenCap + e] : 0u;
+    auto entry = [&](int cc) { const int e = 16 * cc + r16; return e < m ? (u32)a.scand[(int64_t)q * kScreenCap + e] : 0u; };
+    u32 row = entry(c);
+    frag16 rf[kSteps];
+    {
         const frag16* pr = (const frag16*)(a.rows + (int64_t)row * kScreenD + 8 * kq);
-        frag16 rf[kSteps];
 #pragma unroll
         for (int ks = 0; ks < kSteps; ++ks) rf[ks] = pr[4 * ks];
+    }
+    const float thr = a.thr[q];
+    bf16x8 qf[kSteps];
+    const bf16x8* pq = (const bf16x8*)(a.q + (int64_t)q * kScreenD + 8 * kq);
+#pragma unroll
+    for (int ks = 0; ks < kSteps; ++ks) qf[ks] = pq[4 * ks];
+    for (bool first = true; c < nchunks; c += gridDim.y * 4, first = false) {
+        if (!first) {
+            row = entry(c);
+            const frag16* pr = (const frag16*)(a.rows + (int64_t)row * kScreenD + 8 * kq);
+#pragma unroll
+            for (int ks = 0; ks < kSteps; ++ks) rf[ks] = pr[4 * ks];
+        }
         f32x4 acc;
         mfma16_v_first(acc, rf[0], qf[0]);
 #pragma unroll

@@ -14,11 +14,13 @@ template <int NB>
 static int launch_screen8(int grid, int variant, hipStream_t st, const MfmaArgs& a) {
     constexpr int lds = Mfma16Dims<384>::kLds + kMfma16StageBytes;
 #ifdef TS_DIAG
-    constexpr bool kDiag = NB == 4;     // the timing-only forms (VARIANT 9 .. 12) exist for the headline batch only
+    constexpr bool kDiag = NB == 4;     // the timing-only forms (VARIANT 9 .. 13) exist for the headline batch only
 #else
     constexpr bool kDiag = false;       // ... and in the diagnostic build only (make diag)
 #endif
     static_assert(lds <= 160 * 1024, "DMA ring + staged candidates must fit the CU's LDS");
+    // a search with a row mask runs the form of the kernel that tests it (VARIANT 14); the unmasked product (8) has no such code
+    const bool masked = a.row_mask != nullptr;
     static std::atomic<unsigned long long> attr_done{0};
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
@@ -26,11 +28,14 @@ static int launch_screen8(int grid, int variant, hipStream_t st, const MfmaArgs&
     if (!(attr_done.load(std::memory_order_acquire) & bit)) {
         HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<384, NB, 8, false>,
                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<384, NB, 14, false>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         if constexpr (kDiag) {
             HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<384, NB, 9, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
             HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<384, NB, 10, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
             HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<384, NB, 11, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
             HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<384, NB, 12, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<384, NB, 13, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         }
         attr_done.fetch_or(bit, std::memory_order_release);
     }
@@ -39,18 +44,22 @@ static int launch_screen8(int grid, int variant, hipStream_t st, const MfmaArgs&
         else if (variant == 10) mfma16_topk_kernel<384, NB, 10, false><<<grid, kMfmaThreads, lds, st>>>(a);
         else if (variant == 11) mfma16_topk_kernel<384, NB, 11, false><<<grid, kMfmaThreads, lds, st>>>(a);
         else if (variant == 12) mfma16_topk_kernel<384, NB, 12, false><<<grid, kMfmaThreads, lds, st>>>(a);
+        else if (variant == 13) mfma16_topk_kernel<384, NB, 13, false><<<grid, kMfmaThreads, lds, st>>>(a);
+        else if (masked) mfma16_topk_kernel<384, NB, 14, false><<<grid, kMfmaThreads, lds, st>>>(a);
         else mfma16_topk_kernel<384, NB, 8, false><<<grid, kMfmaThreads, lds, st>>>(a);
     } else {
         (void)variant;
-        mfma16_topk_kernel<384, NB, 8, false><<<grid, kMfmaThreads, lds, st>>>(a);
+        if (masked) mfma16_topk_kernel<384, NB, 14, false><<<grid, kMfmaThreads, lds, st>>>(a);
+        else mfma16_topk_kernel<384, NB, 8, false><<<grid, kMfmaThreads, lds, st>>>(a);
     }
     HIP_TRY(hipGetLastError());
     return TS_OK;
 }
 
 // Before the search's first launch: the image covers every row written so far (allocated with the rows' capacity, made anew
-// when an append has grown it), the launch's queries are quantised and the screen's lists emptied.
-int screen_prepare(ts_index* ix, const void* qmat, int nq_launch, hipStream_t st) {
+// when an append has grown it), the launch's queries are quantised and the screen's lists emptied - here (quantize_queries),
+// or by the caller's threshold sample, whose launch has room for it (SampleArgs::scr_qimg).
+int screen_prepare(ts_index* ix, const void* qmat, int nq_launch, bool quantize_queries, hipStream_t st) {
     const int64_t tiles = ix->n_pad / kTileRows;
     if (ix->scr_pad != ix->n_pad) {
         if (ix->scr_rows) HIP_TRY(hipFree(ix->scr_rows));
@@ -78,14 +87,16 @@ int screen_prepare(ts_index* ix, const void* qmat, int nq_launch, hipStream_t st
     if (!ix->scr_qmeta) HIP_TRY(hipMalloc((void**)&ix->scr_qmeta, (size_t)kMfmaQ * 16));
     if (!ix->scr_cand) HIP_TRY(hipMalloc((void**)&ix->scr_cand, (size_t)kMfmaQ * kScreenCap * 8));
     if (!ix->scr_count) HIP_TRY(hipMalloc((void**)&ix->scr_count, (size_t)kMfmaQ * 4));
-    quantize_queries_kernel<<<kMfmaQ, 64, 0, st>>>((const unsigned short*)qmat, std::min(nq_launch, kMfmaQ), (signed char*)ix->scr_q,
-                                                   (float4*)ix->scr_qmeta, ix->scr_count);
-    HIP_TRY(hipGetLastError());
+    if (quantize_queries) {
+        quantize_queries_kernel<<<kMfmaQ, 64, 0, st>>>((const unsigned short*)qmat, std::min(nq_launch, kMfmaQ), (signed char*)ix->scr_q,
+                                                       (float4*)ix->scr_qmeta, ix->scr_count);
+        HIP_TRY(hipGetLastError());
+    }
     return TS_OK;
 }
 
 // The full pass, screened: `a` is the bf16 pass's argument block (thresholds, row mask, tile table, the final select's lists).
-// variant 9 .. 12: a timing-only form of the screen (diagnostic build; wrong results), 0: the product.
+// variant 9 .. 13: a timing-only form of the screen (diagnostic build; wrong results), 0: the product.
 int screen_full_pass(ts_index* ix, int nb, int nq, int grid, int variant, hipStream_t st, const MfmaArgs& a) {
     MfmaArgs s = a;
     s.corpus = (const unsigned short*)ix->scr_rows;

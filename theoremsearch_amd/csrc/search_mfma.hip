@@ -184,9 +184,9 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
     // equal finishing times for the next search (kernels_select.h, rebalance_tiles).  The table starts as equal shares and
     // is re-made whenever the grid or the number of tiles changes.
     const int64_t full_tiles = lv.back().ntiles;
-    // TS_MFMA_VARIANT 9 .. 12: the timing-only forms of the int8 screen (diagnostic build only; launch_screen8.hip)
+    // TS_MFMA_VARIANT 9 .. 13: the timing-only forms of the int8 screen (diagnostic build only; launch_screen8.hip)
 #ifdef TS_DIAG
-    const bool screen_diag = variant >= 9 && variant <= 12;
+    const bool screen_diag = variant >= 9 && variant <= 13;
 #else
     const bool screen_diag = false;
 #endif
@@ -212,7 +212,9 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
     // same candidates >= thr for the final select
     const bool screen = shape16 && !pair && (variant == 0 || screen_diag) && lv.size() >= 2 && lv.back().stride == 1 && lv.back().run == 1 &&
                         screen_usable(ix);
-    if (screen) TS_TRY(screen_prepare(ix, qmat, mfma_block_queries(ix, nq), st));
+    // the sparsest level as the dense sample (below): its launch also makes the screen's image of the queries
+    const bool dense0 = lv.size() >= 2 && dense_sample && lv[0].ntiles * kTileRows <= kLevelSortMax;
+    if (screen) TS_TRY(screen_prepare(ix, qmat, mfma_block_queries(ix, nq), !dense0, st));
     for (size_t i = 0; i < lv.size(); ++i) {
         const bool full_pass = (i + 1 == lv.size());
         if (i == 0 && !full_pass && dense_sample && lv[0].ntiles * kTileRows <= kLevelSortMax) {
@@ -246,7 +248,13 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
                 sa.part_gain = (b >= 2 && b <= 10) ? 0.1f * (float)b : 0.7f;
             }
             ix->rebalance_pending = false;
-            const dim3 sgrid((unsigned)(sa.row_stride / wg_rows), (unsigned)(nchunks + (sa.part ? 1 : 0)));
+            if (screen) {
+                sa.scr_qimg = (signed char*)ix->scr_q;
+                sa.scr_qmeta = (float4*)ix->scr_qmeta;
+                sa.scr_count = ix->scr_count;
+                sa.scr_nrows = std::min(mfma_block_queries(ix, nq), kMfmaQ);
+            }
+            const dim3 sgrid((unsigned)(sa.row_stride / wg_rows), (unsigned)(nchunks + ((sa.part || sa.scr_qimg) ? 1 : 0)));
             const int slds = sample_lds_bytes(wg_rows, (int)(ix->ld * ix->elem()));
             constexpr int kSampleLdsMax = 144 * 1024;   // dynamic part; the kernel also has a few hundred static bytes (rebalance_tiles)
             if (slds > kSampleLdsMax) return fail(TS_ERR_INTERNAL, "threshold sample: rows of %lld bytes do not fit the LDS", (long long)(ix->ld * ix->elem()));
