@@ -77,7 +77,7 @@ typedef struct ts_search_stats {
     int32_t algo;            /* TS_ALGO_SCAN or TS_ALGO_MFMA actually used */
     int32_t levels;          /* MFMA path: number of threshold levels run */
     int32_t fallback_queries; /* MFMA path: queries re-run through the scan (candidate overflow); -1 = not read back */
-    int32_t reserved;
+    int32_t screened;        /* MFMA path: 1 = the full pass ran as the int8 screen + exact rescore (same answers, bit for bit), else 0 */
     int64_t candidates;      /* MFMA path: candidates appended in the last level; -1 = not read back */
 } ts_search_stats;
 
@@ -129,7 +129,14 @@ int ts_index_info(const ts_index *ix, int64_t *n, int32_t *d, int32_t *dtype, in
 
 /* Tuning / diagnostic options of one handle (the TS_* knobs of DESIGN.md section 8, e.g. "TS_MFMA_FIRST_ROWS").  Their
  * initial values are read from the environment once, when the handle is created; afterwards only these calls change
- * them (the search path never calls getenv).  reset = back to the built-in default.  The reference has no counterpart. */
+ * them (the search path never calls getenv).  reset = back to the built-in default.  The reference has no counterpart.
+ * "TS_MFMA_SCREEN" (default 1): the thresholded full pass of a bf16 d = 768 index that owns its rows runs as an int8 screen
+ * (an int8 image of the rows, 768 bytes per row more) followed by an exact rescore of the screened rows from the bf16 rows.
+ * "TS_MFMA_SCREEN_WIDE" (default 0): the same for bf16 d = 1024 indexes - opt-in because the image costs 1,024 bytes per row
+ * (10.24 GB at 10M rows; allocated and filled on the first screened search, kept up to date lazily after uploads / appends).
+ * Contract of both: ids and score bits of every search are identical with the option on and off, for every batch size and
+ * whichever form the unscreened d = 1024 pass would take (TS_MFMA_PAIR, TS_MFMA_GRID); views and attached rows are never
+ * screened.  ts_search_stats.screened tells which pass a call ran. */
 int ts_index_set_option(ts_index *ix, const char *name, int32_t value);
 int ts_index_reset_option(ts_index *ix, const char *name);
 

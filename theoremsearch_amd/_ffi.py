@@ -32,7 +32,7 @@ class TSearchError(RuntimeError):
 
 class SearchStats(C.Structure):
     _fields_ = [("algo", C.c_int32), ("levels", C.c_int32), ("fallback_queries", C.c_int32),
-                ("reserved", C.c_int32), ("candidates", C.c_int64)]
+                ("screened", C.c_int32), ("candidates", C.c_int64)]
 
 
 # name -> (restype, argtypes); kept in one table so tests can check it against the header

@@ -55,14 +55,14 @@ enum Knob {
     K_MFMA_MIN_RANK, K_MFMA_VARIANT, K_MFMA_GROUPS, K_MFMA_GRID, K_MFMA_STAT, K_MFMA_STAT_CANDS, K_MFMA_TAIL_FIT,
     K_MFMA_NO_IDLE, K_MFMA_AHEAD, K_MFMA_TARGET_CANDS, K_MFMA_FIRST_ROWS, K_MFMA_TARGET_SPARSE, K_MFMA_RUN,
     K_MFMA_MIN_ROWS, K_MFMA_SHAPE, K_MFMA_F32, K_SCAN_GENERIC, K_SCAN_MAX_QUERIES, K_MFMA_BALANCE, K_PROBE_SPREAD, K_MFMA_SAMPLE,
-    K_MFMA_PAIR, K_MFMA_PAIR_LAG, K_MFMA_SCREEN, K_COUNT
+    K_MFMA_PAIR, K_MFMA_PAIR_LAG, K_MFMA_SCREEN, K_MFMA_SCREEN_WIDE, K_COUNT
 };
 inline const char* const kKnobNames[K_COUNT] = {
     "TS_MFMA_MIN_RANK", "TS_MFMA_VARIANT", "TS_MFMA_GROUPS", "TS_MFMA_GRID", "TS_MFMA_STAT", "TS_MFMA_STAT_CANDS",
     "TS_MFMA_TAIL_FIT", "TS_MFMA_NO_IDLE", "TS_MFMA_AHEAD", "TS_MFMA_TARGET_CANDS", "TS_MFMA_FIRST_ROWS",
     "TS_MFMA_TARGET_SPARSE", "TS_MFMA_RUN", "TS_MFMA_MIN_ROWS", "TS_MFMA_SHAPE", "TS_MFMA_F32", "TS_SCAN_GENERIC",
     "TS_SCAN_MAX_QUERIES", "TS_MFMA_BALANCE", "TS_PROBE_SPREAD", "TS_MFMA_SAMPLE", "TS_MFMA_PAIR", "TS_MFMA_PAIR_LAG",
-    "TS_MFMA_SCREEN"};
+    "TS_MFMA_SCREEN", "TS_MFMA_SCREEN_WIDE"};
 struct Knobs {
     int v[K_COUNT];
     bool set[K_COUNT];
@@ -133,11 +133,11 @@ struct ts_index {
     bool ordered = false;                                    //   next call behind it (`ordered`: recorded at least once)
     int64_t* part = nullptr;    unsigned* wg_ticks = nullptr;    // full pass of the 16x16 kernel: tile boundaries per workgroup, their times
     int part_g = 0;             int64_t part_ntiles = -1;        // ... the grid and tile count the table was made for
-    // int8 screen of the d = 768 bf16 full pass (kernels_screen8.h): the image [scr_pad x 768] int8 + [scr_pad / 32] tile scalars,
+    // int8 screen of the d = 768 (or, opt-in, 1024) bf16 full pass (kernels_screen8.h): the image [scr_pad x d] int8 + [scr_pad / 32] tile scalars,
     // brought up to date before a screened pass for the rows written since (scr_lo .. scr_hi, marked by every upload / append)
     void* scr_rows = nullptr;   float* scr_tile = nullptr;   int64_t scr_pad = 0;
     int64_t scr_lo = 0, scr_hi = 0;
-    void* scr_q = nullptr;      float* scr_qmeta = nullptr;      // the launch's queries in int8 [256 x 768] + their scalars
+    void* scr_q = nullptr;      float* scr_qmeta = nullptr;      // the launch's queries in int8 [256 x d] + their scalars
     u64* scr_cand = nullptr;    u32* scr_count = nullptr;        // the screen's lists [256][kScreenCap] + counts
     unsigned* pair_pos = nullptr;                            // paired full pass: the tile each workgroup has reached (one word per workgroup of the largest grid)
     unsigned long long* dbg = nullptr;                       // TS_MFMA_VARIANT=3: per-wave cycle sums / clock probe
@@ -308,9 +308,13 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
 // launch_mfma16.hip / launch_mfma16_f32.hip / launch_mfma32.hip: one launch of a matrix kernel (a full pass or a sparse level)
 int launch_pass_mfma16(int d, int nb, bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);
 int launch_pass_mfma16_f32(int d, int nb, bool full_pass, int grid, hipStream_t st, const ts::MfmaArgs& a);
-// the int8 screen + exact rescore in place of the bf16 full pass (launch_screen8.hip): screen_usable = this index, this launch
+// the int8 screen + exact rescore in place of the bf16 full pass (launch_screen8.hip): screen_usable = this index, this launch;
+// ksplit = the rescore takes the k-split form of the d = 1024 pass (the form the call's unscreened pass would have taken)
 bool screen_usable(const ts_index* ix);
 int screen_prepare(ts_index* ix, const void* qmat, int nq_launch, bool quantize_queries, hipStream_t st);
-int screen_full_pass(ts_index* ix, int nb, int nq, int grid, int variant, hipStream_t st, const ts::MfmaArgs& a);
+int screen_full_pass(ts_index* ix, int nb, int nq, int grid, int variant, bool ksplit, hipStream_t st, const ts::MfmaArgs& a);
+// ... their d = 1024 halves (launch_screen8_wide.hip)
+int screen_prepare_wide(ts_index* ix, const void* qmat, int nq_launch, bool quantize_queries, hipStream_t st);
+int screen_full_pass_wide(ts_index* ix, int nb, int nq, int grid, int variant, bool ksplit, hipStream_t st, const ts::MfmaArgs& a);
 int launch_pass_mfma32(int d, int groups, bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);
 int launch_pass_mfma32_f32(bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);

@@ -230,13 +230,14 @@ __device__ __forceinline__ float f32_up(double v) {
     const float f = (float)v;
     return (double)f >= v ? f : __uint_as_float(__float_as_uint(f) + 1u);
 }
-// The screen's image of one query, by one wave (kernels_screen8.h has the quantisation): row r of q [nrows x 768] bf16 -> row r
-// of img [256 x 768] int8 and meta[r] = {1 / s_q (NaN: non-finite value), |e_q|, |q|, 0}; a zero row past nrows.  Also empties
+// The screen's image of one query, by one wave (kernels_screen8.h has the quantisation; kD = the screen's width, 768 or 1024):
+// row r of q [nrows x kD] bf16 -> row r of img [256 x kD] int8 and meta[r] = {1 / s_q (NaN: non-finite value), |e_q|, |q|, 0}; a zero row past nrows.  Also empties
 // the query's list of screened rows.  Needs nothing but the prepared queries, so it rides in whatever launch comes before the
 // screen: the extra workgroup row of the threshold sample (kernels_sample.h), or quantize_queries_kernel.
+template <int kD>
 __device__ __forceinline__ void screen_quantize_query(const unsigned short* __restrict__ q, int nrows, int r, int lane,
                                                       signed char* __restrict__ img, float4* __restrict__ meta, u32* __restrict__ scount) {
-    constexpr int kD = 768;
+    static_assert(kD == 768 || kD == 1024, "widths the int8 screen serves");
     float v[kD / 64];
     float amax = 0.0f;
     int bad = 0;
@@ -341,7 +342,7 @@ __device__ __forceinline__ void mfma16_append_block(const f32x4& a0, const f32x4
 // vmcnt queue is left alone), clears the bits of rows >= n and hands every lane its eight bits: `live` bit (g & 3) + 16 (g >> 2)
 // = row g of this lane.  A value is looked up there only once some lane's score has passed.
 // Padding queries (qid >= nq_real) have threshold 2^30 except in a tile with a non-finite value (INT_MIN): no dot product of
-// 768 int8 pairs reaches INT_MAX, which is what they are compared with here.
+// 768 or 1,024 int8 pairs reaches INT_MAX, which is what they are compared with here.
 // A full list sends the wave's further pairs straight to the queries' global lists (vector memory: the DMA ring's counted
 // waits see two operations more and wait longer - slow, rare, exact).
 // (The pointers are spelled as global-memory pointers: they come out of pinned SGPRs, where hipcc no longer sees that they were
@@ -447,8 +448,8 @@ __device__ __forceinline__ void pair_read_word(unsigned& dst, unsigned lds_word)
 // two masks.  So a tile's candidates are appended one tile late, the last tile's after the loop (one more barrier).
 // Registers: 24 query fragments in VGPRs, 40 in AGPRs.  (With 32 in VGPRs hipcc parked two in AGPRs and copied them back one
 // instruction ahead of their MFMA - asm text, no hazard padding: wrong k-steps.  tools/audit_ring.py reports that pattern.)
-// VARIANT 8 (I8): the int8 screen of the d = 768 bf16 full pass (kernels_screen8.h).  A row of 768 int8 values has the bytes of a d = 384
-// bf16 row, so it runs as D = 384 - the same ring, swizzle, fragment reads and query fragments (bytes 64 ks + 16 kq of the row
+// VARIANT 8 (I8): the int8 screen of the d = 768 / 1024 bf16 full pass (kernels_screen8.h).  A row of 768 int8 values has the bytes of a
+// d = 384 bf16 row, one of 1,024 those of a d = 512 row, so it runs as D = 384 or D = 512 - the same ring, swizzle, fragment reads and query fragments (bytes 64 ks + 16 kq of the row
 // at both operands: whatever k order the i8 instruction gives the bytes of a lane, both operands share it and the integer dot
 // product is exact) - with the i8 MFMA, an integer threshold per (tile, query) from the tile's scalars and (row, query) pairs
 // as candidates (MfmaArgs::cand / count / cap: the screen's lists).
@@ -457,7 +458,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     static_assert(!PAIR || (!SPARSE && !F32), "pairs exist for the bf16 full pass");
     constexpr bool I8 = VARIANT >= 8 && VARIANT <= 14;
     constexpr bool kMasked8 = I8 && VARIANT != 8;           // the row mask is looked at (8: the unmasked product)
-    static_assert(!I8 || (D == 384 && !SPARSE && !F32 && !PAIR), "the screen is the full pass over 768-byte int8 rows");
+    static_assert(!I8 || ((D == 384 || D == 512) && !SPARSE && !F32 && !PAIR), "the screen is the full pass over 768- or 1,024-byte int8 rows");
     static_assert(!KSPLIT || (PAIR && NB == 4 && (VARIANT == 0 || VARIANT == 1 || VARIANT == 2 || VARIANT == 7) && D == 1024), "the k-split is the paired pass of d = 1024 with four query blocks per wave");
     constexpr int Deq = F32 ? 2 * D : D;                 // row length in 2-byte elements
     using dims = typename std::conditional<KSPLIT, MfmaDims<Deq, MfmaGeomKsplit<Deq>>, Mfma16Dims<Deq>>::type;

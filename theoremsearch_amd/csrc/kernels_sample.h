@@ -43,7 +43,7 @@ struct SampleArgs {
     const unsigned* wg_ticks;
     int part_g;
     float part_gain;
-    // optional: the int8 screen's image of this launch's queries (screen_quantize_query, kernels_mfma16.h; bf16 at d = 768),
+    // optional: the int8 screen's image of this launch's queries (screen_quantize_query, kernels_mfma16.h; bf16 at d = 768 or 1024),
     // made by the workgroups of the extra row (grid.y = chunks + 1 then) - it needs only `q`, and the screen runs behind the
     // select that follows this launch
     signed char* scr_qimg;
@@ -71,8 +71,11 @@ __global__ void __launch_bounds__(256) sample_scores_kernel(SampleArgs a) {
         if (blockIdx.x == 0 && a.part) rebalance_tiles(a.part, a.wg_ticks, a.part_g, a.part_gain, (double*)srows);
         if constexpr (!F32) {
             if (a.scr_qimg)
-                for (int r = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6); r < kMfmaQ; r += (int)gridDim.x * 4)
-                    screen_quantize_query((const unsigned short*)a.q, a.scr_nrows, r, (int)(threadIdx.x & 63), a.scr_qimg, a.scr_qmeta, a.scr_count);
+                for (int r = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6); r < kMfmaQ; r += (int)gridDim.x * 4) {
+                    // (the screen's width is the row length: it serves ld = d = 768 and 1024)
+                    if (a.ld == 1024) screen_quantize_query<1024>((const unsigned short*)a.q, a.scr_nrows, r, (int)(threadIdx.x & 63), a.scr_qimg, a.scr_qmeta, a.scr_count);
+                    else screen_quantize_query<768>((const unsigned short*)a.q, a.scr_nrows, r, (int)(threadIdx.x & 63), a.scr_qimg, a.scr_qmeta, a.scr_count);
+                }
         }
         return;
     }

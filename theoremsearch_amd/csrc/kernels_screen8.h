@@ -1,4 +1,5 @@
-// The int8 screen of the d = 768 bf16 full pass: every (row, query) pair is first scored with
+// The int8 screen of the d = 768 bf16 full pass - and, opt-in (TS_MFMA_SCREEN_WIDE), of the d = 1024 one - (DESIGN.md section
+// 3.2): every (row, query) pair is first scored with
 // v_mfma_i32_16x16x64_i8 on an int8 image of the corpus (half the bytes, half the matrix cycles of the bf16 pass), and only
 // the pairs whose certified upper bound reaches the query's threshold are rescored exactly, from the bf16 rows, with the
 // MFMA chain of the bf16 pass.  The pass still only has to guarantee that no row with exact score >= thr is dropped
@@ -25,6 +26,20 @@
 // keeps it there.  (The replaced order, (thr - sub - (athr + sub) 2^-18) tx rq - 1 with sub in fp32, rounded about as often;
 // its thresholds and the folded ones differ by at most one unit - tests/test_screen8_fold_cpu.py.)
 //
+// d = 1024 (W = the screen's width, a template parameter of everything below; the text above reads with 768 -> W):
+//   * the i32 accumulator: |x~.q~| <= 1024 127^2 = 16,516,096 < 2^24, far inside i32 (and every partial sum with it), so the
+//     integer dot product is exact at either width, whatever order the instruction adds the bytes in;
+//   * the summation term: the bf16 products are exact in fp32, and a sum of n fp32 terms added in ANY order (a chain, two
+//     half-chains added, the instruction's own tree inside a k-step) is within gamma_(n-1) sum |x_i q_i| of the exact sum,
+//     gamma_(n-1) = (n - 1) u / (1 - (n - 1) u) with u = 2^-24: 1023 2^-24 (1 + 2^-14) at n = 1024.  g = 1024 2^-22 is four
+//     times that, the same factor as at 768 (it covers a matrix pipe that does not round every addition to nearest);
+//   * both forms of the d = 1024 pass are such sums of the same 1024 products - the plain form one chain of 32 k-steps from a
+//     zero accumulator, the k-split form two chains of 16 k-steps (k-steps 8 u + 4 h .. 8 u + 4 h + 3 of every unit u, h = 0, 1)
+//     added once - so the one bound holds for the score of either, and the rescore below reproduces whichever the call's
+//     unscreened pass would have computed (KSPLIT);
+//   * nothing else in the derivation knows the width: the tile and query scalars are norms in fp64, the fold and its rounding
+//     argument are per (tile, query).
+//
 // A tile with a NaN / Inf value, or a query with one, has threshold INT_MIN (tx or rq is NaN; the clamp's maxNum turns the NaN
 // into -2^31): all of its pairs are candidates and the exact rescore treats them as the bf16 pass does (a NaN score is never a
 // candidate).  An infinite thr gives 2^30 (+inf: nothing passes) or INT_MIN (-inf: everything does).
@@ -33,14 +48,18 @@
 
 namespace ts {
 
-constexpr int kScreenD = 768;        // the width the screen serves (one int8 row = the bytes of a d = 384 bf16 row)
+// widths the screen serves: one int8 row has the bytes of a d = W / 2 bf16 row (384: the d = 768 index; 512: d = 1024)
+constexpr bool screen_width(int w) { return w == 768 || w == 1024; }
 constexpr int kScreenCap = kScreenListCap;   // screen candidates per query (~490 expected on Gaussian rows at 10M; 8 x the exact lists; more = exact re-run)
-constexpr float kScreenGamma = 768.0f * 0x1p-22f;   // bound of the bf16 pass's fp32 summation, relative to |x| |q|
+template <int W> constexpr float kScreenGamma = (float)W * 0x1p-22f;   // bound of the bf16 pass's fp32 summation, relative to |x| |q|
 
 // One workgroup (4 waves) per tile: wave w quantises rows 8 w .. 8 w + 7, lane l elements l + 64 j of a row.
-// img: [tiles x 32 x 768] int8; meta: [tiles] {1 / s_t (NaN: non-finite value in the tile), E_t, X_t, 0}.
+// img: [tiles x 32 x W] int8; meta: [tiles] {1 / s_t (NaN: non-finite value in the tile), E_t, X_t, 0}.
+template <int W>
 __global__ void __launch_bounds__(256) quantize_tiles_kernel(const unsigned short* __restrict__ rows, signed char* __restrict__ img,
                                                              float4* __restrict__ meta, int64_t tile0) {
+    static_assert(screen_width(W), "widths the int8 screen serves");
+    constexpr int kScreenD = W;
     __shared__ float red_max[4];
     __shared__ int red_bad[4];
     __shared__ double red_e[4], red_x[4];
@@ -89,31 +108,38 @@ __global__ void __launch_bounds__(256) quantize_tiles_kernel(const unsigned shor
         emax = fmax(fmax(red_e[0], red_e[1]), fmax(red_e[2], red_e[3])) * (1.0 + 0x1p-40);
         xmax = fmax(fmax(red_x[0], red_x[1]), fmax(red_x[2], red_x[3])) * (1.0 + 0x1p-40);
         const float rs = bad ? __builtin_nanf("") : 1.0f / s;
-        meta[t] = make_float4(rs, f32_up(emax + (double)kScreenGamma * (xmax + emax) * (1.0 + 0x1p-20)), f32_up(xmax), 0.0f);
+        meta[t] = make_float4(rs, f32_up(emax + (double)kScreenGamma<W> * (xmax + emax) * (1.0 + 0x1p-20)), f32_up(xmax), 0.0f);
     }
 }
 
 // One wave per query of the launch (256 workgroups): screen_quantize_query (kernels_mfma16.h) as a launch of its own - for
 // searches whose threshold does not come from the dense sample, whose launch carries this work otherwise (kernels_sample.h).
+template <int W>
 __global__ void __launch_bounds__(64) quantize_queries_kernel(const unsigned short* __restrict__ q, int nrows,
                                                               signed char* __restrict__ img, float4* __restrict__ meta,
                                                               u32* __restrict__ scount) {
-    screen_quantize_query(q, nrows, (int)blockIdx.x, (int)threadIdx.x, img, meta, scount);
+    screen_quantize_query<W>(q, nrows, (int)blockIdx.x, (int)threadIdx.x, img, meta, scount);
 }
 
 // Exact rescore of the screen's pairs.  Workgroup (q, y): its four waves take chunks of 16 of query q's screened rows in turn
-// (chunk 4 y + wave, then every 4 gridDim.y).  A chunk is the A operand of the bf16 pass's MFMA chain - 24 k-steps of
+// (chunk 4 y + wave, then every 4 gridDim.y).  A chunk is the A operand of the bf16 pass's MFMA chain - W / 32 k-steps of
 // v_mfma_f32_16x16x32_bf16, k-step ks = elements 32 ks + 8 (lane >> 4) of row (lane & 15), the first with a zero accumulator -
 // against the query as B, read from column q & 15 as in its own block of 16 queries: for that column the same operands at the
-// same lanes as in mfma16_topk_kernel<768, .>, so every score is bit-identical to the one the unscreened pass computes for that
+// same lanes as in mfma16_topk_kernel<W, .>, so every score is bit-identical to the one the unscreened pass computes for that
 // row.  (A column of D depends on its own column of B only, so the other fifteen columns hold the query too instead of its
 // block's other queries: 1.5 KB of query per wave from one cache line set instead of 24 KB - most waves multiply one chunk,
 // and the query block was as many bytes as the rows.)  The chunk's entries and row gathers - the long way, to HBM - go out
 // before the query's fragments.  Scores >= thr go into the query's list of the final select.  A query whose screen list
 // overflowed gets a count past `cap`: the select sends it to the exact re-run.
+// W = 1024: the row's 32 fragments fill 128 VGPRs, so the query's 32 sit in AGPRs (the B operand may, as in the pass), and the
+// unscreened pass has two arithmetic forms (kernels_mfma16.h; search_mfma.hip picks one per call, and the host passes the same
+// choice here).  KSPLIT = false: the plain form, one chain over k-steps 0 .. 31 from a zero accumulator.  KSPLIT = true: the
+// paired k-split form - half h of a workgroup's waves multiplies k-steps 8 u + 4 h .. 8 u + 4 h + 3 of every unit u = 0 .. 3 in
+// ascending order from a zero accumulator, and the two half sums are added once (ksplit_add4: v_pk_add_f32, one fp32 addition
+// per score, commutative - which wave kept and which handed over does not matter).
 struct ScreenRescoreArgs {
-    const unsigned short* rows;   // bf16 [n_pad x 768]
-    const unsigned short* q;      // bf16 queries [>= 16 * ceil(nq / 16) x 768], as the pass multiplies them
+    const unsigned short* rows;   // bf16 [n_pad x W]
+    const unsigned short* q;      // bf16 queries [>= 16 * ceil(nq / 16) x W], as the pass multiplies them
     const float* thr;             // [nq]
     const u64* scand;             // [256][kScreenCap] screened rows
     const u32* scount;            // [256]
@@ -124,7 +150,11 @@ struct ScreenRescoreArgs {
 
 constexpr int kRescoreY = 8;      // workgroups per query
 
+template <int W, bool KSPLIT>
 __global__ void __launch_bounds__(256) screen_rescore_kernel(ScreenRescoreArgs a) {
+    static_assert(screen_width(W) && (!KSPLIT || W == 1024), "the k-split is a form of the d = 1024 pass");
+    constexpr int kScreenD = W;
+    constexpr bool kQueryInAgprs = W == 1024;
     const int q = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const u32 raw = a.scount[q];
@@ -151,6 +181,10 @@ __global__ void __launch_bounds__(256) screen_rescore_kernel(ScreenRescoreArgs a
     const bf16x8* pq = (const bf16x8*)(a.q + (int64_t)q * kScreenD + 8 * kq);
 #pragma unroll
     for (int ks = 0; ks < kSteps; ++ks) qf[ks] = pq[4 * ks];
+    if constexpr (kQueryInAgprs) {
+#pragma unroll
+        for (int ks = 0; ks < kSteps; ++ks) asm volatile("" : "+a"(qf[ks]));
+    }
     for (bool first = true; c < nchunks; c += gridDim.y * 4, first = false) {
         if (!first) {
             row = entry(c);
@@ -159,10 +193,28 @@ __global__ void __launch_bounds__(256) screen_rescore_kernel(ScreenRescoreArgs a
             for (int ks = 0; ks < kSteps; ++ks) rf[ks] = pr[4 * ks];
         }
         f32x4 acc;
-        mfma16_v_first(acc, rf[0], qf[0]);
+        if constexpr (KSPLIT) {
+            f32x4 half[2];
 #pragma unroll
-        for (int ks = 1; ks < kSteps; ++ks) mfma16_v(acc, rf[ks], qf[ks]);
-        asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc));   // wait states: MFMA result -> VALU reader
+            for (int ks = 0; ks < kSteps; ++ks) {
+                constexpr int kUnitSteps = 8;            // k-steps of a unit of the d = 1024 pass: each half of the waves takes four
+                const int h = (ks % kUnitSteps) / (kUnitSteps / 2);
+                if (ks < kUnitSteps && ks % (kUnitSteps / 2) == 0) mfma16_a_first(half[h], rf[ks], qf[ks]);
+                else mfma16_a(half[h], rf[ks], qf[ks]);
+            }
+            asm volatile("s_nop 15\n\ts_nop 3" : "+v"(half[0]), "+v"(half[1]));   // wait states: MFMA result -> VALU reader
+            ksplit_add4(acc, half[0], half[1]);
+        } else if constexpr (kQueryInAgprs) {
+            mfma16_a_first(acc, rf[0], qf[0]);
+#pragma unroll
+            for (int ks = 1; ks < kSteps; ++ks) mfma16_a(acc, rf[ks], qf[ks]);
+            asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc));
+        } else {
+            mfma16_v_first(acc, rf[0], qf[0]);
+#pragma unroll
+            for (int ks = 1; ks < kSteps; ++ks) mfma16_v(acc, rf[ks], qf[ks]);
+            asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc));   // wait states: MFMA result -> VALU reader
+        }
         u32 rr[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) rr[i] = (u32)__shfl((int)row, 4 * kq + i);

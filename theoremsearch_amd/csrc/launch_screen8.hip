@@ -1,130 +1,23 @@
-// The int8 screen of the d = 768 bf16 full pass (kernels_screen8.h): image upkeep, query quantisation, the screen launch
-// (mfma16_topk_kernel over 768-byte int8 rows, VARIANT 8) and the exact rescore.
-#include "host.h"
-#include "kernels_screen8.h"
+// The int8 screen of the bf16 full pass (kernels_screen8.h): image upkeep, query quantisation, the screen launch
+// (mfma16_topk_kernel over int8 rows, VARIANT 8) and the exact rescore.  This unit holds the kernels of width 768; the opt-in
+// width 1024 (TS_MFMA_SCREEN_WIDE) has its own, launch_screen8_wide.hip.
+#include "launch_screen8_impl.h"
 
 // Indexes whose rows the library owns (not a view of another handle's rows, not rows attached from the caller - those may
-// change behind the library and leave the image stale), bf16 at d = 768 on the 16x16 kernel; TS_MFMA_SCREEN=0 switches it off.
+// change behind the library and leave the image stale), bf16 on the 16x16 kernel, at d = 768 - or at d = 1024 when
+// TS_MFMA_SCREEN_WIDE is set (default 0: the image costs 1,024 bytes per row); TS_MFMA_SCREEN=0 switches both off.
 bool screen_usable(const ts_index* ix) {
-    return ix->dtype == TS_BF16 && ix->d == kScreenD && ix->ld == kScreenD && use_shape16(ix) && !ix->borrowed && !ix->attached &&
+    const bool width = ix->d == 768 || (ix->d == 1024 && ix->knobs.get(K_MFMA_SCREEN_WIDE, 0) != 0);
+    return ix->dtype == TS_BF16 && width && ix->ld == ix->d && use_shape16(ix) && !ix->borrowed && !ix->attached &&
            ix->knobs.get(K_MFMA_SCREEN, 1) != 0;
 }
 
-template <int NB>
-static int launch_screen8(int grid, int variant, hipStream_t st, const MfmaArgs& a) {
-    constexpr int lds = Mfma16Dims<384>::kLds + kMfma16StageBytes;
-#ifdef TS_DIAG
-    constexpr bool kDiag = NB == 4;     // the timing-only forms (VARIANT 9 .. 13) exist for the headline batch only
-#else
-    constexpr bool kDiag = false;       // ... and in the diagnostic build only (make diag)
-#endif
-    static_assert(lds <= 160 * 1024, "DMA ring + staged candidates must fit the CU's LDS");
-    // a search with a row mask runs the form of the kernel that tests it (VARIANT 14); the unmasked product (8) has no such code
-    const bool masked = a.row_mask != nullptr;
-    static std::atomic<unsigned long long> attr_done{0};
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-        HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<384, NB, 8, false>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<384, NB, 14, false>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        if constexpr (kDiag) {
-            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<384, NB, 9, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<384, NB, 10, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<384, NB, 11, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<384, NB, 12, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<384, NB, 13, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        }
-        attr_done.fetch_or(bit, std::memory_order_release);
-    }
-    if constexpr (kDiag) {
-        if (variant == 9) mfma16_topk_kernel<384, NB, 9, false><<<grid, kMfmaThreads, lds, st>>>(a);
-        else if (variant == 10) mfma16_topk_kernel<384, NB, 10, false><<<grid, kMfmaThreads, lds, st>>>(a);
-        else if (variant == 11) mfma16_topk_kernel<384, NB, 11, false><<<grid, kMfmaThreads, lds, st>>>(a);
-        else if (variant == 12) mfma16_topk_kernel<384, NB, 12, false><<<grid, kMfmaThreads, lds, st>>>(a);
-        else if (variant == 13) mfma16_topk_kernel<384, NB, 13, false><<<grid, kMfmaThreads, lds, st>>>(a);
-        else if (masked) mfma16_topk_kernel<384, NB, 14, false><<<grid, kMfmaThreads, lds, st>>>(a);
-        else mfma16_topk_kernel<384, NB, 8, false><<<grid, kMfmaThreads, lds, st>>>(a);
-    } else {
-        (void)variant;
-        if (masked) mfma16_topk_kernel<384, NB, 14, false><<<grid, kMfmaThreads, lds, st>>>(a);
-        else mfma16_topk_kernel<384, NB, 8, false><<<grid, kMfmaThreads, lds, st>>>(a);
-    }
-    HIP_TRY(hipGetLastError());
-    return TS_OK;
-}
-
-// Before the search's first launch: the image covers every row written so far (allocated with the rows' capacity, made anew
-// when an append has grown it), the launch's queries are quantised and the screen's lists emptied - here (quantize_queries),
-// or by the caller's threshold sample, whose launch has room for it (SampleArgs::scr_qimg).
 int screen_prepare(ts_index* ix, const void* qmat, int nq_launch, bool quantize_queries, hipStream_t st) {
-    const int64_t tiles = ix->n_pad / kTileRows;
-    if (ix->scr_pad != ix->n_pad) {
-        if (ix->scr_rows) HIP_TRY(hipFree(ix->scr_rows));
-        if (ix->scr_tile) HIP_TRY(hipFree(ix->scr_tile));
-        ix->scr_rows = nullptr; ix->scr_tile = nullptr; ix->scr_pad = 0;
-        HIP_TRY(hipMalloc(&ix->scr_rows, (size_t)ix->n_pad * kScreenD));
-        HIP_TRY(hipMalloc((void**)&ix->scr_tile, (size_t)tiles * 16));
-        ix->scr_pad = ix->n_pad;
-        ix->scr_lo = 0;
-        ix->scr_hi = ix->n_pad;
-    }
-    if (ix->scr_lo < ix->scr_hi) {
-        // whole tiles around the written rows: a tile two uploads share is quantised from both
-        const int64_t t0 = ix->scr_lo / kTileRows;
-        const int64_t t1 = std::min(tiles, (ix->scr_hi + kTileRows - 1) / kTileRows);
-        for (int64_t t = t0; t < t1; t += 1 << 20) {
-            const unsigned nblk = (unsigned)std::min<int64_t>(1 << 20, t1 - t);
-            quantize_tiles_kernel<<<nblk, 256, 0, st>>>((const unsigned short*)ix->rows, (signed char*)ix->scr_rows,
-                                                        (float4*)ix->scr_tile, t);
-            HIP_TRY(hipGetLastError());
-        }
-        ix->scr_lo = ix->scr_hi = 0;
-    }
-    if (!ix->scr_q) HIP_TRY(hipMalloc(&ix->scr_q, (size_t)kMfmaQ * kScreenD));
-    if (!ix->scr_qmeta) HIP_TRY(hipMalloc((void**)&ix->scr_qmeta, (size_t)kMfmaQ * 16));
-    if (!ix->scr_cand) HIP_TRY(hipMalloc((void**)&ix->scr_cand, (size_t)kMfmaQ * kScreenCap * 8));
-    if (!ix->scr_count) HIP_TRY(hipMalloc((void**)&ix->scr_count, (size_t)kMfmaQ * 4));
-    if (quantize_queries) {
-        quantize_queries_kernel<<<kMfmaQ, 64, 0, st>>>((const unsigned short*)qmat, std::min(nq_launch, kMfmaQ), (signed char*)ix->scr_q,
-                                                       (float4*)ix->scr_qmeta, ix->scr_count);
-        HIP_TRY(hipGetLastError());
-    }
-    return TS_OK;
+    if (ix->d == 1024) return screen_prepare_wide(ix, qmat, nq_launch, quantize_queries, st);
+    return screen_prepare_w<768>(ix, qmat, nq_launch, quantize_queries, st);
 }
 
-// The full pass, screened: `a` is the bf16 pass's argument block (thresholds, row mask, tile table, the final select's lists).
-// variant 9 .. 13: a timing-only form of the screen (diagnostic build; wrong results), 0: the product.
-int screen_full_pass(ts_index* ix, int nb, int nq, int grid, int variant, hipStream_t st, const MfmaArgs& a) {
-    MfmaArgs s = a;
-    s.corpus = (const unsigned short*)ix->scr_rows;
-    s.q = (const unsigned short*)ix->scr_q;
-    s.cand = ix->scr_cand;
-    s.count = ix->scr_count;
-    s.cap = kScreenCap;
-    s.scr_tile = (const float4*)ix->scr_tile;
-    s.scr_q = (const float4*)ix->scr_qmeta;
-    int rc;
-    switch (nb) {
-        case 1: rc = launch_screen8<1>(grid, variant, st, s); break;
-        case 2: rc = launch_screen8<2>(grid, variant, st, s); break;
-        case 3: rc = launch_screen8<3>(grid, variant, st, s); break;
-        case 4: rc = launch_screen8<4>(grid, variant, st, s); break;
-        default: return fail(TS_ERR_INTERNAL, "no int8 screen with %d query blocks per wave", nb);
-    }
-    TS_TRY(rc);
-    ScreenRescoreArgs r;
-    r.rows = (const unsigned short*)ix->rows;
-    r.q = a.q;
-    r.thr = a.thr;
-    r.scand = ix->scr_cand;
-    r.scount = ix->scr_count;
-    r.cand = a.cand;
-    r.count = a.count;
-    r.cap = a.cap;
-    screen_rescore_kernel<<<dim3((unsigned)nq, kRescoreY), 256, 0, st>>>(r);
-    HIP_TRY(hipGetLastError());
-    return TS_OK;
+int screen_full_pass(ts_index* ix, int nb, int nq, int grid, int variant, bool ksplit, hipStream_t st, const MfmaArgs& a) {
+    if (ix->d == 1024) return screen_full_pass_wide(ix, nb, nq, grid, variant, ksplit, st, a);
+    return screen_full_pass_w<768>(ix, nb, nq, grid, variant, ksplit, st, a);
 }

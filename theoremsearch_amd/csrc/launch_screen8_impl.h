@@ -1,0 +1,134 @@
+// The int8 screen's host side for one width W (768 or 1024; kernels_screen8.h), shared by the translation units that hold the
+// kernel instantiations of a width: launch_screen8.hip (768) and launch_screen8_wide.hip (1024).
+#pragma once
+#include "host.h"
+#include "kernels_screen8.h"
+
+template <int W, int NB>
+static int launch_screen8(int grid, int variant, hipStream_t st, const MfmaArgs& a) {
+    constexpr int D = W / 2;            // the int8 row as a bf16 row of half as many elements
+    constexpr int lds = Mfma16Dims<D>::kLds + kMfma16StageBytes;
+#ifdef TS_DIAG
+    constexpr bool kDiag = NB == 4;     // the timing-only forms (VARIANT 9 .. 13) exist for the headline batch only
+#else
+    constexpr bool kDiag = false;       // ... and in the diagnostic build only (make diag)
+#endif
+    static_assert(lds <= 160 * 1024, "DMA ring + staged candidates must fit the CU's LDS");
+    // a search with a row mask runs the form of the kernel that tests it (VARIANT 14); the unmasked product (8) has no such code
+    const bool masked = a.row_mask != nullptr;
+    static std::atomic<unsigned long long> attr_done{0};
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (!(attr_done.load(std::memory_order_acquire) & bit)) {
+        HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<D, NB, 8, false>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<D, NB, 14, false>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        if constexpr (kDiag) {
+            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<D, NB, 9, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<D, NB, 10, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<D, NB, 11, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<D, NB, 12, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<D, NB, 13, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        }
+        attr_done.fetch_or(bit, std::memory_order_release);
+    }
+    if constexpr (kDiag) {
+        if (variant == 9) mfma16_topk_kernel<D, NB, 9, false><<<grid, kMfmaThreads, lds, st>>>(a);
+        else if (variant == 10) mfma16_topk_kernel<D, NB, 10, false><<<grid, kMfmaThreads, lds, st>>>(a);
+        else if (variant == 11) mfma16_topk_kernel<D, NB, 11, false><<<grid, kMfmaThreads, lds, st>>>(a);
+        else if (variant == 12) mfma16_topk_kernel<D, NB, 12, false><<<grid, kMfmaThreads, lds, st>>>(a);
+        else if (variant == 13) mfma16_topk_kernel<D, NB, 13, false><<<grid, kMfmaThreads, lds, st>>>(a);
+        else if (masked) mfma16_topk_kernel<D, NB, 14, false><<<grid, kMfmaThreads, lds, st>>>(a);
+        else mfma16_topk_kernel<D, NB, 8, false><<<grid, kMfmaThreads, lds, st>>>(a);
+    } else {
+        (void)variant;
+        if (masked) mfma16_topk_kernel<D, NB, 14, false><<<grid, kMfmaThreads, lds, st>>>(a);
+        else mfma16_topk_kernel<D, NB, 8, false><<<grid, kMfmaThreads, lds, st>>>(a);
+    }
+    HIP_TRY(hipGetLastError());
+    return TS_OK;
+}
+
+// Before the search's first launch: the image covers every row written so far (allocated with the rows' capacity, made anew
+// when an append has grown it), the launch's queries are quantised and the screen's lists emptied - here (quantize_queries),
+// or by the caller's threshold sample, whose launch has room for it (SampleArgs::scr_qimg).
+template <int W>
+static int screen_prepare_w(ts_index* ix, const void* qmat, int nq_launch, bool quantize_queries, hipStream_t st) {
+    const int64_t tiles = ix->n_pad / kTileRows;
+    if (ix->scr_pad != ix->n_pad) {
+        if (ix->scr_rows) HIP_TRY(hipFree(ix->scr_rows));
+        if (ix->scr_tile) HIP_TRY(hipFree(ix->scr_tile));
+        ix->scr_rows = nullptr; ix->scr_tile = nullptr; ix->scr_pad = 0;
+        HIP_TRY(hipMalloc(&ix->scr_rows, (size_t)ix->n_pad * W));
+        HIP_TRY(hipMalloc((void**)&ix->scr_tile, (size_t)tiles * 16));
+        ix->scr_pad = ix->n_pad;
+        ix->scr_lo = 0;
+        ix->scr_hi = ix->n_pad;
+    }
+    if (ix->scr_lo < ix->scr_hi) {
+        // whole tiles around the written rows: a tile two uploads share is quantised from both
+        const int64_t t0 = ix->scr_lo / kTileRows;
+        const int64_t t1 = std::min(tiles, (ix->scr_hi + kTileRows - 1) / kTileRows);
+        for (int64_t t = t0; t < t1; t += 1 << 20) {
+            const unsigned nblk = (unsigned)std::min<int64_t>(1 << 20, t1 - t);
+            quantize_tiles_kernel<W><<<nblk, 256, 0, st>>>((const unsigned short*)ix->rows, (signed char*)ix->scr_rows,
+                                                        (float4*)ix->scr_tile, t);
+            HIP_TRY(hipGetLastError());
+        }
+        ix->scr_lo = ix->scr_hi = 0;
+    }
+    if (!ix->scr_q) HIP_TRY(hipMalloc(&ix->scr_q, (size_t)kMfmaQ * W));
+    if (!ix->scr_qmeta) HIP_TRY(hipMalloc((void**)&ix->scr_qmeta, (size_t)kMfmaQ * 16));
+    if (!ix->scr_cand) HIP_TRY(hipMalloc((void**)&ix->scr_cand, (size_t)kMfmaQ * kScreenCap * 8));
+    if (!ix->scr_count) HIP_TRY(hipMalloc((void**)&ix->scr_count, (size_t)kMfmaQ * 4));
+    if (quantize_queries) {
+        quantize_queries_kernel<W><<<kMfmaQ, 64, 0, st>>>((const unsigned short*)qmat, std::min(nq_launch, kMfmaQ), (signed char*)ix->scr_q,
+                                                       (float4*)ix->scr_qmeta, ix->scr_count);
+        HIP_TRY(hipGetLastError());
+    }
+    return TS_OK;
+}
+
+// The full pass, screened: `a` is the bf16 pass's argument block (thresholds, row mask, tile table, the final select's lists).
+// variant 9 .. 13: a timing-only form of the screen (diagnostic build; wrong results), 0: the product.  ksplit (W = 1024): the
+// unscreened pass of this call would have been the paired k-split form - the rescore adds its two half-chains as that form does.
+template <int W>
+static int screen_full_pass_w(ts_index* ix, int nb, int nq, int grid, int variant, bool ksplit, hipStream_t st, const MfmaArgs& a) {
+    MfmaArgs s = a;
+    s.corpus = (const unsigned short*)ix->scr_rows;
+    s.q = (const unsigned short*)ix->scr_q;
+    s.cand = ix->scr_cand;
+    s.count = ix->scr_count;
+    s.cap = kScreenCap;
+    s.scr_tile = (const float4*)ix->scr_tile;
+    s.scr_q = (const float4*)ix->scr_qmeta;
+    int rc;
+    switch (nb) {
+        case 1: rc = launch_screen8<W, 1>(grid, variant, st, s); break;
+        case 2: rc = launch_screen8<W, 2>(grid, variant, st, s); break;
+        case 3: rc = launch_screen8<W, 3>(grid, variant, st, s); break;
+        case 4: rc = launch_screen8<W, 4>(grid, variant, st, s); break;
+        default: return fail(TS_ERR_INTERNAL, "no int8 screen with %d query blocks per wave", nb);
+    }
+    TS_TRY(rc);
+    ScreenRescoreArgs r;
+    r.rows = (const unsigned short*)ix->rows;
+    r.q = a.q;
+    r.thr = a.thr;
+    r.scand = ix->scr_cand;
+    r.scount = ix->scr_count;
+    r.cand = a.cand;
+    r.count = a.count;
+    r.cap = a.cap;
+    if constexpr (W == 1024) {
+        if (ksplit) screen_rescore_kernel<W, true><<<dim3((unsigned)nq, kRescoreY), 256, 0, st>>>(r);
+        else screen_rescore_kernel<W, false><<<dim3((unsigned)nq, kRescoreY), 256, 0, st>>>(r);
+    } else {
+        if (ksplit) return fail(TS_ERR_INTERNAL, "the k-split rescore is a form of the d = 1024 pass, not of d = %d", W);
+        screen_rescore_kernel<W, false><<<dim3((unsigned)nq, kRescoreY), 256, 0, st>>>(r);
+    }
+    HIP_TRY(hipGetLastError());
+    return TS_OK;
+}

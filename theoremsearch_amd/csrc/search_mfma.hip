@@ -127,7 +127,27 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
     const int variant = ix->knobs.get(K_MFMA_VARIANT, 0);
     const bool shape16 = use_shape16(ix);
     const int groups = shape16 ? 0 : mfma_block_queries(ix, nq) / 128;
-    const bool pair = mfma_pairs(ix, nq);
+    // Threshold of the full pass: by default extrapolated from ONE unthresholded sample (Gaussian tail of the
+    // sample's scores, verified afterwards by the candidate count); TS_MFMA_STAT=0 selects the chain of
+    // guaranteed lower bounds (more sample rows to scan, no re-runs ever).
+    const bool statistical = ix->knobs.get(K_MFMA_STAT, 1) != 0;
+    const std::vector<Level> lv = plan_levels(ix->knobs, ix->n, kk, statistical);
+    // TS_MFMA_VARIANT 9 .. 13: the timing-only forms of the int8 screen (diagnostic build only; launch_screen8*.hip)
+#ifdef TS_DIAG
+    const bool screen_diag = variant >= 9 && variant <= 13;
+#else
+    const bool screen_diag = false;
+#endif
+    // bf16 at d = 768 (or, with TS_MFMA_SCREEN_WIDE, d = 1024) behind a threshold: the full pass runs as the int8 screen + exact
+    // rescore (kernels_screen8.h), the same candidates >= thr for the final select
+    const bool screen = shape16 && (variant == 0 || screen_diag) && lv.size() >= 2 && lv.back().stride == 1 && lv.back().run == 1 &&
+                        screen_usable(ix);
+    // d = 1024, 193 .. 256 queries: the unscreened pass is a launch of workgroup pairs, in the k-split form unless TS_MFMA_PAIR=1.
+    // The screen holds all 256 queries in ONE unpaired launch (four blocks per wave: an int8 query fragment is half the
+    // registers); its rescore adds every score in the form the pairs would have (plain chain or two half-chains), bit for bit.
+    const bool pair_form = mfma_pairs(ix, nq);
+    const bool ksplit_form = pair_form && ix->knobs.get(K_MFMA_PAIR, 2) != 1;
+    const bool pair = pair_form && !screen;
     const int nb16 = pair ? 2 : (shape16 ? mfma_block_queries(ix, nq) / 64 : 0);
     if (!ix->attr_done) {
         HIP_TRY(hipFuncSetAttribute((const void*)level_select_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, kLevelLds));
@@ -154,11 +174,6 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
         HIP_TRY(hipMalloc((void**)&ix->pcount, (size_t)kMfmaQ * 4 * grid * 4));
         ix->priv_writers = 4 * grid;
     }
-    // Threshold of the full pass: by default extrapolated from ONE unthresholded sample (Gaussian tail of the
-    // sample's scores, verified afterwards by the candidate count); TS_MFMA_STAT=0 selects the chain of
-    // guaranteed lower bounds (more sample rows to scan, no re-runs ever).
-    const bool statistical = ix->knobs.get(K_MFMA_STAT, 1) != 0;
-    const std::vector<Level> lv = plan_levels(ix->knobs, ix->n, kk, statistical);
     // Expected candidates per query of the full pass under the estimate.  Every candidate costs the pass ~0.3 us of one
     // CU's time (the appending wave holds the other three at the next barrier), whatever N: 160 per query were 10 % of
     // a 1.25M-row shard's pass and 1 % of the 10M pass; an under-filled query (fewer than k back) costs an exact scan
@@ -184,12 +199,6 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
     // equal finishing times for the next search (kernels_select.h, rebalance_tiles).  The table starts as equal shares and
     // is re-made whenever the grid or the number of tiles changes.
     const int64_t full_tiles = lv.back().ntiles;
-    // TS_MFMA_VARIANT 9 .. 13: the timing-only forms of the int8 screen (diagnostic build only; launch_screen8.hip)
-#ifdef TS_DIAG
-    const bool screen_diag = variant >= 9 && variant <= 13;
-#else
-    const bool screen_diag = false;
-#endif
     const bool balance = shape16 && ix->knobs.get(K_MFMA_BALANCE, 1) != 0 && wgs >= 8 && wgs <= 256 && lv.back().stride == 1 &&
                          lv.back().run == 1 && full_tiles >= 32 * (int64_t)wgs && (variant == 0 || variant == 3 || screen_diag);
     if (balance && (ix->part_g != wgs || ix->part_ntiles != full_tiles)) {
@@ -208,10 +217,6 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
         HIP_TRY(hipStreamSynchronize(st));          // `equal` is a local; this happens once per (grid, size)
         ix->part_ntiles = full_tiles;
     }
-    // bf16 at d = 768 behind a threshold: the full pass runs as the int8 screen + exact rescore (kernels_screen8.h), the
-    // same candidates >= thr for the final select
-    const bool screen = shape16 && !pair && (variant == 0 || screen_diag) && lv.size() >= 2 && lv.back().stride == 1 && lv.back().run == 1 &&
-                        screen_usable(ix);
     // the sparsest level as the dense sample (below): its launch also makes the screen's image of the queries
     const bool dense0 = lv.size() >= 2 && dense_sample && lv[0].ntiles * kTileRows <= kLevelSortMax;
     if (screen) TS_TRY(screen_prepare(ix, qmat, mfma_block_queries(ix, nq), !dense0, st));
@@ -310,7 +315,7 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
         a.fb_count = ix->fb_count;
         a.part = (balance && full_pass) ? ix->part : nullptr;
         a.wg_ticks = (balance && full_pass) ? ix->wg_ticks : nullptr;
-        a.pair = (pair && full_pass) ? (ix->knobs.get(K_MFMA_PAIR, 2) == 1 ? 1 : 2) : 0;      // 2: the k-split form (TS_MFMA_PAIR=1: two blocks per wave over the whole row)
+        a.pair = (pair && full_pass) ? (ksplit_form ? 2 : 1) : 0;      // 2: the k-split form (TS_MFMA_PAIR=1: two blocks per wave over the whole row)
         a.pair_pos = nullptr;
         a.pair_lag = 0;
         if (a.pair && ix->knobs.get(K_MFMA_PAIR_LAG, 1) > 0) {
@@ -333,7 +338,7 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
 #endif
         hipEvent_t stop = full_pass ? prof_begin(ix, st, ix->n) : nullptr;  // only the full pass is bracketed
         int rc;
-        if (screen && full_pass) rc = screen_full_pass(ix, nb16, nq, grid, screen_diag ? variant : 0, st, a);
+        if (screen && full_pass) rc = screen_full_pass(ix, nb16, nq, grid, screen_diag ? variant : 0, ksplit_form, st, a);
         else if (ix->dtype == TS_F32 && shape16) rc = launch_pass_mfma16_f32(ix->d, nb16, full_pass, grid, st, a);
         else if (ix->dtype == TS_F32) rc = launch_pass_mfma32_f32(full_pass, variant, grid, st, a);
         else if (shape16) rc = launch_pass_mfma16(ix->d, nb16, full_pass, variant, grid, st, a);
@@ -381,7 +386,7 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
             std::vector<unsigned long long> h((size_t)grid * 16);
             HIP_TRY(hipStreamSynchronize(st));
             HIP_TRY(hipMemcpy(h.data(), a.dbg, h.size() * 8, hipMemcpyDeviceToHost));
-            const double units = (double)(lv.back().ntiles * (variant == 10 ? Mfma16Dims<384>::kUnits : MfmaDims<768>::kUnits)) / grid;
+            const double units = (double)(lv.back().ntiles * (variant == 10 ? (ix->d == 1024 ? Mfma16Dims<512>::kUnits : Mfma16Dims<384>::kUnits) : MfmaDims<768>::kUnits)) / grid;
             for (int wv = 0; wv < 4; ++wv) {
                 double tot = 0, vm = 0, bar = 0, dma = 0;
                 for (int w = wv; w < grid * 4; w += 4) { tot += h[w * 4]; vm += h[w * 4 + 1]; bar += h[w * 4 + 2]; dma += h[w * 4 + 3]; }
@@ -444,6 +449,9 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
     if (!in_place) TS_TRY(scan_search(ix, nq, k, out_scores, out_idx, ix->fb_list, ix->fb_count, st));
     else if (ix->dtype == TS_F32) TS_TRY(scan_search(ix, nq, k, out_scores, out_idx, ix->fb_list, ix->fb_count, st, (const float*)qmat));
     else TS_TRY(scan_search(ix, nq, k, out_scores, out_idx, ix->fb_list, ix->fb_count, st, nullptr, (const unsigned short*)qmat));
-    if (stats) stats->levels = (int)lv.size();
+    if (stats) {
+        stats->levels = (int)lv.size();
+        stats->screened = screen ? 1 : 0;
+    }
     return TS_OK;
 }

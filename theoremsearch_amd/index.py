@@ -216,7 +216,7 @@ class TheoremIndex:
                                                _ffi.as_ptr(scores), _ffi.as_ptr(idx), 0))
             if self.row_offset:
                 idx[idx >= 0] += self.row_offset
-            return (scores, idx, {"algo": 0, "levels": 0, "fallback_queries": 0, "candidates": 0}) if return_stats else (scores, idx)
+            return (scores, idx, {"algo": 0, "levels": 0, "fallback_queries": 0, "candidates": 0, "screened": 0}) if return_stats else (scores, idx)
         if mask is not None:
             m = np.asarray(mask, dtype=bool).reshape(-1)
             if m.shape[0] != self.n:
@@ -231,7 +231,8 @@ class TheoremIndex:
                                                        _ALGOS[algo], C.byref(stats)))
             if return_stats:
                 return scores, idx, {"algo": stats.algo, "levels": stats.levels,
-                                     "fallback_queries": stats.fallback_queries, "candidates": stats.candidates}
+                                     "fallback_queries": stats.fallback_queries, "candidates": stats.candidates,
+                                     "screened": stats.screened}
             return scores, idx
         stats = _ffi.SearchStats()
         _ffi.check(self._lib.ts_search_ex(self._h, _ffi.as_ptr(q), _ffi.np_dtype_code(q), 0, nq, k,
@@ -239,7 +240,8 @@ class TheoremIndex:
                                           C.byref(stats)))
         if return_stats:
             return scores, idx, {"algo": stats.algo, "levels": stats.levels,
-                                 "fallback_queries": stats.fallback_queries, "candidates": stats.candidates}
+                                 "fallback_queries": stats.fallback_queries, "candidates": stats.candidates,
+                                 "screened": stats.screened}
         return scores, idx
 
     def search_device(self, q_ptr: int, q_dtype: str, nq: int, k: int, out_scores_ptr: int, out_idx_ptr: int,
