@@ -10,26 +10,21 @@ every mfma16_topk_kernel instantiation of the device assembly for both."""
 import os
 import shutil
 import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "theoremsearch_amd", "csrc")
+from isa_common import CSRC, audit_ring, hipcc_or_skip
+
 ASM_DIR = os.path.join(CSRC, "build", "asm")
 UNITS = ("launch_mfma16", "launch_mfma16_f32")        # the translation units that instantiate mfma16_topk_kernel
 
 
 @pytest.mark.timeout(900)
 def test_no_register_of_the_fragment_ring_is_read_while_its_load_is_in_flight():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not (os.path.exists(hipcc) or shutil.which("hipcc")):
-        pytest.skip("hipcc not available")
+    hipcc_or_skip()
     r = subprocess.run(["make", "-C", CSRC, "asm"], capture_output=True, text=True, timeout=850)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     try:
-        sys.path.insert(0, os.path.join(ROOT, "tools"))
-        import audit_ring
         for unit in UNITS:
             assert audit_ring.main(os.path.join(ASM_DIR, f"{unit}-hip-amdgcn-amd-amdhsa-gfx950.s")) == 0, unit
         # the register budget the kernel is written for: no scratch, one wave per SIMD
@@ -46,8 +41,6 @@ def test_no_register_of_the_fragment_ring_is_read_while_its_load_is_in_flight():
 
 
 def test_the_audit_sees_an_operand_written_right_in_front_of_its_mfma():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import audit_ring
     good = ["s_waitcnt lgkmcnt(0)", "v_accvgpr_read_b32 v174, a148", "s_nop 1", "s_nop 0",
             "v_mfma_f32_16x16x32_bf16 v[138:141], v[166:169], v[174:177], v[138:141]"]
     bad = ["s_waitcnt lgkmcnt(0)", "v_accvgpr_read_b32 v174, a148",

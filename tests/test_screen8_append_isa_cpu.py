@@ -6,89 +6,19 @@ barrier and can still reach a barrier, the append blocks included wherever hipcc
 load of a kernel argument (the tile-scalar s_load_dwordx4 is the only scalar load) and no vector load from global memory.  The
 row mask is read by the masked form of the kernel only (VARIANT 14): one scalar load of the tile's mask word, no vector load
 either, so the DMA ring's vmcnt queue sees nothing of the path but the overflow case's atomics."""
-import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "theoremsearch_amd", "csrc")
+from isa_common import device_asm, kernel_body, tile_loop
+
 NB = 4
-
-
-def _kernel(text, nb, variant):
-    m = re.search(r"^_ZN2ts18mfma16_topk_kernelILi384ELi%dELi%dELb0ELb0ELb0ELb0EEEvNS_8MfmaArgsE:[^\n]*\n(.*?)\n\.Lfunc_end" % (nb, variant),
-                  text, re.S | re.M)
-    assert m, "no NB = %d screen kernel of variant %d" % (nb, variant)
-    out = []
-    for line in m.group(1).split("\n"):
-        s = line.split(";")[0].strip()
-        if s and not (s.startswith(".") and not s.endswith(":")):
-            out.append(s)
-    return out
-
-
-def _successors(ins):
-    labels = {l[:-1]: i for i, l in enumerate(ins) if l.endswith(":")}
-    succ = []
-    for i, l in enumerate(ins):
-        op = l.split()[0]
-        assert not op.startswith(("s_setpc", "s_swappc", "s_call")), l      # no indirect control flow to follow
-        if op == "s_endpgm":
-            succ.append([])
-        elif op == "s_branch":
-            succ.append([labels[l.split()[1]]])
-        elif op.startswith("s_cbranch"):
-            succ.append([labels[l.split()[1]]] + ([i + 1] if i + 1 < len(ins) else []))
-        else:
-            succ.append([i + 1] if i + 1 < len(ins) else [])
-    return succ
-
-
-def _closure(start, edges):
-    seen, todo = set(start), list(start)
-    while todo:
-        for j in edges[todo.pop()]:
-            if j not in seen:
-                seen.add(j)
-                todo.append(j)
-    return seen
-
-
-def tile_loop(ins):
-    """Indices of the instructions between the first barrier and the last one in execution order: reachable from the first
-    s_barrier of the listing, and with a path to some s_barrier."""
-    succ = _successors(ins)
-    pred = [[] for _ in ins]
-    for i, ss in enumerate(succ):
-        for j in ss:
-            pred[j].append(i)
-    bars = [i for i, l in enumerate(ins) if l.startswith("s_barrier")]
-    assert len(bars) >= 2, bars
-    return sorted(_closure([bars[0]], succ) & _closure(bars, pred))
-
-
-def _compile(tmp):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc):
-        hipcc = shutil.which("hipcc")
-    if not hipcc:
-        pytest.skip("hipcc not available")
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-gpu-rdc", "-fvisibility=hidden",
-                        "-save-temps=obj", "-c", "-o", os.path.join(tmp, "launch_screen8.o"), os.path.join(CSRC, "launch_screen8.hip")],
-                       capture_output=True, text=True, timeout=850, cwd=tmp)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return open(os.path.join(tmp, "launch_screen8-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
 
 
 @pytest.mark.timeout(900)
 def test_screen_append_path():
-    with tempfile.TemporaryDirectory() as tmp:
-        text = _compile(tmp)
-    ins = _kernel(text, NB, 8)
+    text = device_asm("launch_screen8").text
+    ins = kernel_body(text, 384, NB, 8)
     loop = [ins[i] for i in tile_loop(ins)]
     ops = [l.split()[0] for l in loop]
     # the loop was found: the tiles' MFMAs and the append blocks (a ranked ds_write_b64 per accumulator value) are in it
@@ -108,7 +38,7 @@ def test_screen_append_path():
     assert not gl, gl
     # ... and the masked form of the kernel is the one that reads it: a scalar load of one mask word per tile with a passing
     # lane, in front of the same ranked write
-    masked = _kernel(text, NB, 14)
+    masked = kernel_body(text, 384, NB, 14)
     mloop = [masked[i] for i in tile_loop(masked)]
     msl = [l for l in mloop if l.startswith("s_load") and not l.startswith("s_load_dwordx4 ")]
     assert msl and all(l.startswith("s_load_dword ") for l in msl), msl

@@ -1,33 +1,17 @@
 """The int8 screen's tile tail in the compiled gfx950 ISA (launch_screen8.hip, NB = 4): the tile thresholds are computed among
 the tile's MFMAs (screen_thr_piece, TS16_THR8 in kernels_mfma16.h), so between the last i8 MFMA of a steady tile and the load of
 the scalars two tiles ahead there is only the ring's drain, the block test and a little scalar bookkeeping."""
-import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "theoremsearch_amd", "csrc")
+from isa_common import device_asm, kernel_body
+
 NB = 4
 MFMA = "v_mfma_i32_16x16x64_i8"
 # VALU of the tail beyond the 5 NB block-test instructions: the hand-over to the general units (a v_lshl_add_u64 and two
 # v_mov_b32, on the path once per launch) and room for one copy that hipcc may place there
 BOOKKEEPING = 4
-
-
-def _kernel(text, nb):
-    m = re.search(r"^_ZN2ts18mfma16_topk_kernelILi384ELi%dELi8ELb0ELb0ELb0ELb0EEEvNS_8MfmaArgsE:[^\n]*\n(.*?)\n\.Lfunc_end" % nb,
-                  text, re.S | re.M)
-    assert m, "no NB = %d screen kernel" % nb
-    out = []
-    for line in m.group(1).split("\n"):
-        s = line.split(";")[0].strip()
-        if s and not (s.startswith(".") and not s.endswith(":")):
-            out.append(s)
-    return out
 
 
 def _tail_path(ins, start):
@@ -75,18 +59,7 @@ def _steady_tiles(ins):
 
 @pytest.mark.timeout(900)
 def test_screen_tile_tail():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc):
-        hipcc = shutil.which("hipcc")
-    if not hipcc:
-        pytest.skip("hipcc not available")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-gpu-rdc", "-fvisibility=hidden",
-                            "-save-temps=obj", "-c", "-o", os.path.join(tmp, "launch_screen8.o"), os.path.join(CSRC, "launch_screen8.hip")],
-                           capture_output=True, text=True, timeout=850, cwd=tmp)
-        assert r.returncode == 0, r.stderr[-2000:]
-        text = open(os.path.join(tmp, "launch_screen8-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
-    ins = _kernel(text, NB)
+    ins = kernel_body(device_asm("launch_screen8").text, 384, NB, 8)
     tiles = _steady_tiles(ins)
     assert tiles, "no steady tile of %d MFMAs followed by the tile-scalar load" % (24 * NB)
     for b, last, tail, load in tiles:

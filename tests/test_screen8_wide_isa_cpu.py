@@ -5,72 +5,15 @@ and <512, 1 .. 4, 14> (row mask) are there and issue the i8 MFMA; no kernel of t
 loop of the unmasked kernels never drains the DMA ring: the steady units wait for a counted vmcnt behind an immediate, and the
 only s_waitcnt vmcnt(0) between the first barrier and the last are the returning atomics of the full-list path (rare, exact)
 and the last rung of the general units' wait ladder (the end of a workgroup's tile range, nothing left in flight)."""
-import os
 import re
-import shutil
-import subprocess
-import sys
-import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "theoremsearch_amd", "csrc")
+from isa_common import audit_ring, device_asm, kernel_body, tile_loop
+
 MFMA = "v_mfma_i32_16x16x64_i8"
 UNITS = 2                # units (barriers) per tile of 1,024-byte rows
 UNIT_STEPS = 8           # k-steps per unit: 2 NB MFMAs each
-
-
-def _kernel(text, nb, variant):
-    m = re.search(r"^_ZN2ts18mfma16_topk_kernelILi512ELi%dELi%dELb0ELb0ELb0ELb0EEEvNS_8MfmaArgsE:[^\n]*\n(.*?)\n\.Lfunc_end" % (nb, variant),
-                  text, re.S | re.M)
-    assert m, "no NB = %d wide screen kernel of variant %d" % (nb, variant)
-    out = []
-    for line in m.group(1).split("\n"):
-        s = line.split(";")[0].strip()
-        if s and not (s.startswith(".") and not s.endswith(":")):
-            out.append(s)
-    return out
-
-
-def _successors(ins):
-    labels = {l[:-1]: i for i, l in enumerate(ins) if l.endswith(":")}
-    succ = []
-    for i, l in enumerate(ins):
-        op = l.split()[0]
-        assert not op.startswith(("s_setpc", "s_swappc", "s_call")), l      # no indirect control flow to follow
-        if op == "s_endpgm":
-            succ.append([])
-        elif op == "s_branch":
-            succ.append([labels[l.split()[1]]])
-        elif op.startswith("s_cbranch"):
-            succ.append([labels[l.split()[1]]] + ([i + 1] if i + 1 < len(ins) else []))
-        else:
-            succ.append([i + 1] if i + 1 < len(ins) else [])
-    return succ
-
-
-def _closure(start, edges):
-    seen, todo = set(start), list(start)
-    while todo:
-        for j in edges[todo.pop()]:
-            if j not in seen:
-                seen.add(j)
-                todo.append(j)
-    return seen
-
-
-def tile_loop(ins):
-    """Indices of the instructions between the first barrier and the last one in execution order: reachable from the first
-    s_barrier of the listing, and with a path to some s_barrier."""
-    succ = _successors(ins)
-    pred = [[] for _ in ins]
-    for i, ss in enumerate(succ):
-        for j in ss:
-            pred[j].append(i)
-    bars = [i for i, l in enumerate(ins) if l.startswith("s_barrier")]
-    assert len(bars) >= 2, bars
-    return sorted(_closure([bars[0]], succ) & _closure(bars, pred))
 
 
 def check_no_drain(ins, nb):
@@ -111,25 +54,8 @@ def check_no_drain(ins, nb):
 
 @pytest.mark.timeout(900)
 def test_wide_screen_unit_isa():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc):
-        hipcc = shutil.which("hipcc")
-    if not hipcc:
-        pytest.skip("hipcc not available")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-gpu-rdc", "-fvisibility=hidden",
-                            "-save-temps=obj", "-c", "-o", os.path.join(tmp, "launch_screen8_wide.o"),
-                            os.path.join(CSRC, "launch_screen8_wide.hip"), "-Rpass-analysis=kernel-resource-usage"],
-                           capture_output=True, text=True, timeout=850, cwd=tmp)
-        assert r.returncode == 0, r.stderr[-2000:]
-        asm = os.path.join(tmp, "launch_screen8_wide-hip-amdgcn-amd-amdhsa-gfx950.s")
-        sys.path.insert(0, os.path.join(ROOT, "tools"))
-        try:
-            import audit_ring
-            assert audit_ring.main(asm) == 0
-        finally:
-            sys.path.pop(0)
-        text = open(asm).read()
+    asm, text, usage = device_asm("launch_screen8_wide")
+    assert audit_ring.main(asm) == 0
     for variant in (8, 14):
         found = re.findall(r"^_ZN2ts18mfma16_topk_kernelILi512ELi(\d)ELi%dELb0ELb0ELb0ELb0EEEvNS_8MfmaArgsE:" % variant, text, re.M)
         assert sorted(found) == ["1", "2", "3", "4"], (variant, found)
@@ -138,10 +64,10 @@ def test_wide_screen_unit_isa():
     for name in ("quantize_tiles_kernelILi1024E", "quantize_queries_kernelILi1024E", "screen_rescore_kernelILi1024ELb0E",
                  "screen_rescore_kernelILi1024ELb1E"):
         assert re.search(r"^_ZN2ts\d+%s\w*:" % name, text, re.M), name
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
+    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", usage)]
     assert scratch and max(scratch) == 0, scratch
-    spills = [int(x) for x in re.findall(r"[SV]GPRs Spill: (\d+)", r.stderr)]
+    spills = [int(x) for x in re.findall(r"[SV]GPRs Spill: (\d+)", usage)]
     assert spills and max(spills) == 0, spills
     for nb in (1, 2, 3, 4):
-        steady, ladder = check_no_drain(_kernel(text, nb, 8), nb)
+        steady, ladder = check_no_drain(kernel_body(text, 512, nb, 8), nb)
         print("NB = %d: %d steady units without a vmcnt wait behind their barrier, %d ladder ends" % (nb, steady, ladder))

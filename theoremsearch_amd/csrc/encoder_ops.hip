@@ -125,26 +125,17 @@ extern "C" int ts_attention_short(int device, const void* qkv, const int64_t* at
     const unsigned short* in = (const unsigned short*)qkv;
     unsigned short* o = (unsigned short*)out;
     // 65 .. 128 tokens: one query tile at a time (attention_rows_kernel, dynamic LDS: 4 waves x up to 17 KB, two workgroups per CU)
-#define TS_ATTN_ROWS(T_)                                                                                                     \
-    do {                                                                                                                     \
-        constexpr int lds_ = 4 * attn_rows_wave_lds(T_);                                                                     \
-        static std::atomic<unsigned long long> attr_{0};                                                                     \
-        const unsigned long long bit_ = 1ull << (device & 63);                                                               \
-        if (!(attr_.load(std::memory_order_acquire) & bit_)) {                                                               \
-            HIP_TRY(hipFuncSetAttribute((const void*)attention_rows_kernel<T_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_)); \
-            attr_.fetch_or(bit_, std::memory_order_release);                                                                 \
-        }                                                                                                                    \
-        attention_rows_kernel<T_><<<grid, 256, lds_, st>>>(in, attention_mask, batch, seq, heads, o);                        \
-    } while (0)
+#define TS_ATTN_ROWS(T_) \
+    return launch_lds<attention_rows_kernel<T_>>(device, grid, 256, 4 * attn_rows_wave_lds(T_), st, in, attention_mask, batch, seq, heads, o)
     switch ((seq + 15) / 16) {
         case 1: attention_short_kernel<1><<<grid, 256, 0, st>>>(in, attention_mask, batch, seq, heads, o); break;
         case 2: attention_short_kernel<2><<<grid, 256, 0, st>>>(in, attention_mask, batch, seq, heads, o); break;
         case 3: attention_short_kernel<3><<<grid, 256, 0, st>>>(in, attention_mask, batch, seq, heads, o); break;
         case 4: attention_short_kernel<4><<<grid, 256, 0, st>>>(in, attention_mask, batch, seq, heads, o); break;
-        case 5: TS_ATTN_ROWS(5); break;
-        case 6: TS_ATTN_ROWS(6); break;
-        case 7: TS_ATTN_ROWS(7); break;
-        default: TS_ATTN_ROWS(8); break;
+        case 5: TS_ATTN_ROWS(5);
+        case 6: TS_ATTN_ROWS(6);
+        case 7: TS_ATTN_ROWS(7);
+        default: TS_ATTN_ROWS(8);
     }
 #undef TS_ATTN_ROWS
     HIP_TRY(hipGetLastError());
@@ -213,26 +204,15 @@ extern "C" int ts_attention_float(int device, const void* qkv, const void* qkv_b
     const unsigned grid = (unsigned)((int64_t)batch * q_heads);
     const unsigned threads = 64u * (unsigned)std::min(T, 4);
     const float scale_log2e = scale * 1.4426950408889634f;
+    // the limit: what the longest sequence of the head size needs
 #define TS_ATTN_F32(HD_, C_)                                                                                                  \
-    do {                                                                                                                      \
-        const int lds_ = attn_f32_lds(HD_, T);                                                                                \
-        static std::atomic<unsigned long long> attr_{0};                                                                      \
-        const unsigned long long bit_ = 1ull << (device & 63);                                                                \
-        if (!(attr_.load(std::memory_order_acquire) & bit_)) {                                                                \
-            HIP_TRY(hipFuncSetAttribute((const void*)attention_f32_kernel<HD_, C_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                        attn_f32_lds(HD_, attn_f32_max_seq(HD_) / 16)));                                      \
-            attr_.fetch_or(bit_, std::memory_order_release);                                                                  \
-        }                                                                                                                     \
-        attention_f32_kernel<HD_, C_><<<grid, threads, lds_, st>>>((const float*)qkv, attention_mask, batch, seq, q_heads, kv_heads, \
-                                                                     scale_log2e, (float*)out, (unsigned short*)pieces,      \
-                                                                     (const float*)qkv_bias);                                \
-    } while (0)
+    return launch_lds<attention_f32_kernel<HD_, C_>, attn_f32_lds(HD_, attn_f32_max_seq(HD_) / 16)>(                          \
+        device, grid, threads, attn_f32_lds(HD_, T), st, (const float*)qkv, attention_mask, batch, seq, q_heads, kv_heads,    \
+        scale_log2e, (float*)out, (unsigned short*)pieces, (const float*)qkv_bias)
     if (head_dim == 64) { if (causal) TS_ATTN_F32(64, true); else TS_ATTN_F32(64, false); }
     else if (head_dim == 128) { if (causal) TS_ATTN_F32(128, true); else TS_ATTN_F32(128, false); }
     else { if (causal) TS_ATTN_F32(256, true); else TS_ATTN_F32(256, false); }
 #undef TS_ATTN_F32
-    HIP_TRY(hipGetLastError());
-    return TS_OK;
 }
 
 extern "C" int ts_attention_gqa(int device, const void* qkv, const int64_t* attention_mask, int32_t batch, int32_t seq, int32_t q_heads,
@@ -251,17 +231,8 @@ extern "C" int ts_attention_gqa(int device, const void* qkv, const int64_t* atte
     const unsigned grid = (unsigned)(((int64_t)batch * q_heads + 3) / 4);
     const unsigned short* in = (const unsigned short*)qkv;
     unsigned short* o = (unsigned short*)out;
-#define TS_ATTN_GQA(T_, C_)                                                                                                  \
-    do {                                                                                                                     \
-        constexpr int lds_ = 4 * attn_gqa_wave_lds(T_);                                                                      \
-        static std::atomic<unsigned long long> attr_{0};                                                                     \
-        const unsigned long long bit_ = 1ull << (device & 63);                                                               \
-        if (!(attr_.load(std::memory_order_acquire) & bit_)) {                                                               \
-            HIP_TRY(hipFuncSetAttribute((const void*)attention_gqa_kernel<T_, C_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_)); \
-            attr_.fetch_or(bit_, std::memory_order_release);                                                                 \
-        }                                                                                                                    \
-        attention_gqa_kernel<T_, C_><<<grid, 256, lds_, st>>>(in, attention_mask, batch, seq, q_heads, kv_heads, o);         \
-    } while (0)
+#define TS_ATTN_GQA(T_, C_) \
+    return launch_lds<attention_gqa_kernel<T_, C_>>(device, grid, 256, 4 * attn_gqa_wave_lds(T_), st, in, attention_mask, batch, seq, q_heads, kv_heads, o)
     // 65 .. 128 tokens: one query tile at a time against K fragments in registers and a V^T image in LDS that the R query heads
     // of a key / value group (R waves of one workgroup) share
     const int per_kv = q_heads / kv_heads;
@@ -269,15 +240,9 @@ extern "C" int ts_attention_gqa(int device, const void* qkv, const int64_t* atte
     const unsigned rows_grid = (unsigned)((int64_t)batch * kv_heads * (per_kv / R));
 #define TS_ATTN_GQA_ROWS_R(T_, C_, R_)                                                                                       \
     do {                                                                                                                     \
-        constexpr int lds_ = attn_gqa_rows_lds(T_, R_);                                                                      \
-        static_assert(lds_ <= 160 * 1024, "the image and the waves' tiles fit the CU's LDS");                                \
-        static std::atomic<unsigned long long> attr_{0};                                                                     \
-        const unsigned long long bit_ = 1ull << (device & 63);                                                               \
-        if (!(attr_.load(std::memory_order_acquire) & bit_)) {                                                               \
-            HIP_TRY(hipFuncSetAttribute((const void*)attention_gqa_rows_kernel<T_, C_, R_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_)); \
-            attr_.fetch_or(bit_, std::memory_order_release);                                                                 \
-        }                                                                                                                    \
-        attention_gqa_rows_kernel<T_, C_, R_><<<rows_grid, 64 * R_, lds_, st>>>(in, attention_mask, batch, seq, q_heads, kv_heads, o); \
+        static_assert(attn_gqa_rows_lds(T_, R_) <= 160 * 1024, "the image and the waves' tiles fit the CU's LDS");           \
+        return launch_lds<attention_gqa_rows_kernel<T_, C_, R_>>(device, rows_grid, 64 * R_, attn_gqa_rows_lds(T_, R_), st, in, \
+                                                                 attention_mask, batch, seq, q_heads, kv_heads, o);          \
     } while (0)
 #define TS_ATTN_GQA_ROWS(T_, C_)                                                                                             \
     do {                                                                                                                     \
@@ -288,32 +253,30 @@ extern "C" int ts_attention_gqa(int device, const void* qkv, const int64_t* atte
     const int tiles = (seq + 15) / 16;
     if (causal) {
         switch (tiles) {
-            case 1: TS_ATTN_GQA(1, true); break;
-            case 2: TS_ATTN_GQA(2, true); break;
-            case 3: TS_ATTN_GQA(3, true); break;
-            case 4: TS_ATTN_GQA(4, true); break;
-            case 5: TS_ATTN_GQA_ROWS(5, true); break;
-            case 6: TS_ATTN_GQA_ROWS(6, true); break;
-            case 7: TS_ATTN_GQA_ROWS(7, true); break;
-            default: TS_ATTN_GQA_ROWS(8, true); break;
+            case 1: TS_ATTN_GQA(1, true);
+            case 2: TS_ATTN_GQA(2, true);
+            case 3: TS_ATTN_GQA(3, true);
+            case 4: TS_ATTN_GQA(4, true);
+            case 5: TS_ATTN_GQA_ROWS(5, true);
+            case 6: TS_ATTN_GQA_ROWS(6, true);
+            case 7: TS_ATTN_GQA_ROWS(7, true);
+            default: TS_ATTN_GQA_ROWS(8, true);
         }
     } else {
         switch (tiles) {
-            case 1: TS_ATTN_GQA(1, false); break;
-            case 2: TS_ATTN_GQA(2, false); break;
-            case 3: TS_ATTN_GQA(3, false); break;
-            case 4: TS_ATTN_GQA(4, false); break;
-            case 5: TS_ATTN_GQA_ROWS(5, false); break;
-            case 6: TS_ATTN_GQA_ROWS(6, false); break;
-            case 7: TS_ATTN_GQA_ROWS(7, false); break;
-            default: TS_ATTN_GQA_ROWS(8, false); break;
+            case 1: TS_ATTN_GQA(1, false);
+            case 2: TS_ATTN_GQA(2, false);
+            case 3: TS_ATTN_GQA(3, false);
+            case 4: TS_ATTN_GQA(4, false);
+            case 5: TS_ATTN_GQA_ROWS(5, false);
+            case 6: TS_ATTN_GQA_ROWS(6, false);
+            case 7: TS_ATTN_GQA_ROWS(7, false);
+            default: TS_ATTN_GQA_ROWS(8, false);
         }
     }
 #undef TS_ATTN_GQA_ROWS
 #undef TS_ATTN_GQA_ROWS_R
 #undef TS_ATTN_GQA
-    HIP_TRY(hipGetLastError());
-    return TS_OK;
 }
 
 static int qk_norm_rope_launch(int device, void* qkv, const void* q_weight, const void* k_weight, const void* cos_table,

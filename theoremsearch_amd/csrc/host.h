@@ -1,5 +1,6 @@
 // Host side shared by the translation units of libtsearch.so (index.hip, search.hip, search_mfma.hip, the launch_*.hip
-// files, encoder_ops.hip, shards.hip): error reporting, the per-handle knobs, the handles themselves, stream ordering.
+// files, encoder_ops.hip, shards.hip): error reporting, the launch helpers, the per-handle knobs, the handles themselves,
+// stream ordering.
 // Internal: nothing here is part of the C ABI (include/tsearch.h); the library is built with hidden visibility.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -48,6 +49,39 @@ inline int fail(int code, const char* fmt, ...) {
         int rc_ = (expr);       \
         if (rc_ != TS_OK) return rc_; \
     } while (0)
+
+// ---------------------------------------------------------------------------------------------
+// launches
+// ---------------------------------------------------------------------------------------------
+// One launch of a kernel with `lds` bytes of dynamic LDS: the limit is raised per function AND per device, so the first
+// launch of `Kernel` on device `dev` (the CURRENT device: every entry point sets it) raises it, every launch is checked.
+// Limit: what the limit is raised to, once - the largest `lds` this kernel is ever launched with; 0 = to `lds` itself, and
+// again whenever a launch asks for more than any before it on that device (kernels whose `lds` follows the row width).
+template <auto Kernel, int Limit = 0, class... A>
+inline int launch_lds(int dev, dim3 grid, dim3 block, int lds, hipStream_t st, const A&... args) {
+    static std::atomic<int> raised[64];     // per device: the limit set so far
+    static std::mutex raise_mu;
+    const int want = Limit ? Limit : lds;
+    std::atomic<int>& have = raised[dev & 63];
+    if (have.load(std::memory_order_acquire) < want) {
+        std::lock_guard<std::mutex> lock(raise_mu);     // two first launches at once: the limit never goes down
+        if (have.load(std::memory_order_relaxed) < want) {
+            HIP_TRY(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, want));
+            have.store(want, std::memory_order_release);
+        }
+    }
+    Kernel<<<grid, block, lds, st>>>(args...);
+    HIP_TRY(hipGetLastError());
+    return TS_OK;
+}
+
+// The kernel form a TS_MFMA_VARIANT names: go(std::integral_constant<int, V>) for the V of Vs... equal to `variant`, its
+// result in *rc; false when the list does not name it (the caller then launches the product kernel).
+template <int V> using variant_c = std::integral_constant<int, V>;
+template <int... Vs, class Go>
+inline bool launch_variant(int variant, int* rc, Go&& go) {
+    return ((variant == Vs && ((*rc = go(variant_c<Vs>{})), true)) || ...);
+}
 
 // Tuning / diagnostic knobs.  Read from the environment ONCE per handle (ts_index_create / ts_index_view /
 // ts_index_subset), changed afterwards only through ts_index_set_option: no getenv on the search path.
@@ -125,8 +159,6 @@ struct ts_index {
     void* rank_many_buf = nullptr; size_t rank_many_bytes = 0;  // ts_rank_many: slots | keys | counts of one pass of one query block
     const u32* active_mask = nullptr;                        // bitmask of the search in progress (under `mu`)
     int64_t active_allowed = 0;                              // rows that bitmask allows (host masks: counted; else n)
-    bool attr_done = false;
-    bool attr_done_hist = false;
     Knobs knobs;                                             // env at creation, then ts_index_set_option
     hipStream_t last_stream = nullptr;                       // stream the previous call ran on: compared, never used (it may be gone)
     hipEvent_t order_ev = nullptr;                           // recorded at the end of every call on that call's stream: orders the
@@ -306,8 +338,9 @@ int mfma_block_queries(const ts_index* ix, int nq);
 int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx, hipStream_t st, ts_search_stats* stats,
                 const void* qmat, bool in_place);
 // launch_mfma16.hip / launch_mfma16_f32.hip / launch_mfma32.hip: one launch of a matrix kernel (a full pass or a sparse level)
-int launch_pass_mfma16(int d, int nb, bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);
-int launch_pass_mfma16_f32(int d, int nb, bool full_pass, int grid, hipStream_t st, const ts::MfmaArgs& a);
+// on device `dev`, the handle's
+int launch_pass_mfma16(int dev, int d, int nb, bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);
+int launch_pass_mfma16_f32(int dev, int d, int nb, bool full_pass, int grid, hipStream_t st, const ts::MfmaArgs& a);
 // the int8 screen + exact rescore in place of the bf16 full pass (launch_screen8.hip): screen_usable = this index, this launch;
 // ksplit = the rescore takes the k-split form of the d = 1024 pass (the form the call's unscreened pass would have taken)
 bool screen_usable(const ts_index* ix);
@@ -316,5 +349,5 @@ int screen_full_pass(ts_index* ix, int nb, int nq, int grid, int variant, bool k
 // ... their d = 1024 halves (launch_screen8_wide.hip)
 int screen_prepare_wide(ts_index* ix, const void* qmat, int nq_launch, bool quantize_queries, hipStream_t st);
 int screen_full_pass_wide(ts_index* ix, int nb, int nq, int grid, int variant, bool ksplit, hipStream_t st, const ts::MfmaArgs& a);
-int launch_pass_mfma32(int d, int groups, bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);
-int launch_pass_mfma32_f32(bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);
+int launch_pass_mfma32(int dev, int d, int groups, bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);
+int launch_pass_mfma32_f32(int dev, bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);

@@ -5,7 +5,7 @@
 #include "kernels_screen8.h"
 
 template <int W, int NB>
-static int launch_screen8(int grid, int variant, hipStream_t st, const MfmaArgs& a) {
+static int launch_screen8(int dev, int grid, int variant, hipStream_t st, const MfmaArgs& a) {
     constexpr int D = W / 2;            // the int8 row as a bf16 row of half as many elements
     constexpr int lds = Mfma16Dims<D>::kLds + kMfma16StageBytes;
 #ifdef TS_DIAG
@@ -16,39 +16,11 @@ static int launch_screen8(int grid, int variant, hipStream_t st, const MfmaArgs&
     static_assert(lds <= 160 * 1024, "DMA ring + staged candidates must fit the CU's LDS");
     // a search with a row mask runs the form of the kernel that tests it (VARIANT 14); the unmasked product (8) has no such code
     const bool masked = a.row_mask != nullptr;
-    static std::atomic<unsigned long long> attr_done{0};
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-        HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<D, NB, 8, false>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<D, NB, 14, false>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        if constexpr (kDiag) {
-            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<D, NB, 9, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<D, NB, 10, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<D, NB, 11, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<D, NB, 12, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            HIP_TRY(hipFuncSetAttribute((const void*)mfma16_topk_kernel<D, NB, 13, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        }
-        attr_done.fetch_or(bit, std::memory_order_release);
-    }
-    if constexpr (kDiag) {
-        if (variant == 9) mfma16_topk_kernel<D, NB, 9, false><<<grid, kMfmaThreads, lds, st>>>(a);
-        else if (variant == 10) mfma16_topk_kernel<D, NB, 10, false><<<grid, kMfmaThreads, lds, st>>>(a);
-        else if (variant == 11) mfma16_topk_kernel<D, NB, 11, false><<<grid, kMfmaThreads, lds, st>>>(a);
-        else if (variant == 12) mfma16_topk_kernel<D, NB, 12, false><<<grid, kMfmaThreads, lds, st>>>(a);
-        else if (variant == 13) mfma16_topk_kernel<D, NB, 13, false><<<grid, kMfmaThreads, lds, st>>>(a);
-        else if (masked) mfma16_topk_kernel<D, NB, 14, false><<<grid, kMfmaThreads, lds, st>>>(a);
-        else mfma16_topk_kernel<D, NB, 8, false><<<grid, kMfmaThreads, lds, st>>>(a);
-    } else {
-        (void)variant;
-        if (masked) mfma16_topk_kernel<D, NB, 14, false><<<grid, kMfmaThreads, lds, st>>>(a);
-        else mfma16_topk_kernel<D, NB, 8, false><<<grid, kMfmaThreads, lds, st>>>(a);
-    }
-    HIP_TRY(hipGetLastError());
-    return TS_OK;
+    auto go = [&](auto v) { return launch_lds<mfma16_topk_kernel<D, NB, decltype(v)::value, false>>(dev, grid, kMfmaThreads, lds, st, a); };
+    int rc;
+    if constexpr (kDiag)
+        if (launch_variant<9, 10, 11, 12, 13>(variant, &rc, go)) return rc;
+    return masked ? go(variant_c<14>{}) : go(variant_c<8>{});
 }
 
 // Before the search's first launch: the image covers every row written so far (allocated with the rows' capacity, made anew
@@ -106,10 +78,10 @@ static int screen_full_pass_w(ts_index* ix, int nb, int nq, int grid, int varian
     s.scr_q = (const float4*)ix->scr_qmeta;
     int rc;
     switch (nb) {
-        case 1: rc = launch_screen8<W, 1>(grid, variant, st, s); break;
-        case 2: rc = launch_screen8<W, 2>(grid, variant, st, s); break;
-        case 3: rc = launch_screen8<W, 3>(grid, variant, st, s); break;
-        case 4: rc = launch_screen8<W, 4>(grid, variant, st, s); break;
+        case 1: rc = launch_screen8<W, 1>(ix->device, grid, variant, st, s); break;
+        case 2: rc = launch_screen8<W, 2>(ix->device, grid, variant, st, s); break;
+        case 3: rc = launch_screen8<W, 3>(ix->device, grid, variant, st, s); break;
+        case 4: rc = launch_screen8<W, 4>(ix->device, grid, variant, st, s); break;
         default: return fail(TS_ERR_INTERNAL, "no int8 screen with %d query blocks per wave", nb);
     }
     TS_TRY(rc);

@@ -20,21 +20,11 @@ static u64 host_key(float s, int64_t row) {
 }
 
 template <bool F32, int RB, bool GATHER>
-static int launch_rank_many_t(int grid, int lds, hipStream_t st, const RankManyArgs& a) {
-    static std::atomic<unsigned long long> attr_done{0};
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-        // the largest row of its RB (rank_rb): 2,048 bytes at RB = 4, 4,096 (fp32 at d = 1024) at RB = 2
-        constexpr int kMaxLds = rank_lds_bytes(RB, RB == 4 ? 2048 : 4096);
-        static_assert(kMaxLds <= 160 * 1024, "a tile must fit the CU's LDS");
-        HIP_TRY(hipFuncSetAttribute((const void*)rank_many_kernel<F32, RB, GATHER>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
-        attr_done.fetch_or(bit, std::memory_order_release);
-    }
-    rank_many_kernel<F32, RB, GATHER><<<grid, kRankThreads, lds, st>>>(a);
-    HIP_TRY(hipGetLastError());
-    return TS_OK;
+static int launch_rank_many_t(int dev, int grid, int lds, hipStream_t st, const RankManyArgs& a) {
+    // the largest row of its RB (rank_rb): 2,048 bytes at RB = 4, 4,096 (fp32 at d = 1024) at RB = 2
+    constexpr int kMaxLds = rank_lds_bytes(RB, RB == 4 ? 2048 : 4096);
+    static_assert(kMaxLds <= 160 * 1024, "a tile must fit the CU's LDS");
+    return launch_lds<rank_many_kernel<F32, RB, GATHER>, kMaxLds>(dev, grid, kRankThreads, lds, st, a);
 }
 
 static int launch_rank_many(const ts_index* ix, bool gather, int grid, hipStream_t st, const RankManyArgs& a) {
@@ -42,9 +32,9 @@ static int launch_rank_many(const ts_index* ix, bool gather, int grid, hipStream
     const int rb = rank_rb(row_bytes);
     const int lds = rank_lds_bytes(rb, row_bytes);
     const bool f32 = ix->dtype == TS_F32;
-    if (f32 && rb == 4) return gather ? launch_rank_many_t<true, 4, true>(grid, lds, st, a) : launch_rank_many_t<true, 4, false>(grid, lds, st, a);
-    if (f32) return gather ? launch_rank_many_t<true, 2, true>(grid, lds, st, a) : launch_rank_many_t<true, 2, false>(grid, lds, st, a);
-    if (rb == 4) return gather ? launch_rank_many_t<false, 4, true>(grid, lds, st, a) : launch_rank_many_t<false, 4, false>(grid, lds, st, a);
+    if (f32 && rb == 4) return gather ? launch_rank_many_t<true, 4, true>(ix->device, grid, lds, st, a) : launch_rank_many_t<true, 4, false>(ix->device, grid, lds, st, a);
+    if (f32) return gather ? launch_rank_many_t<true, 2, true>(ix->device, grid, lds, st, a) : launch_rank_many_t<true, 2, false>(ix->device, grid, lds, st, a);
+    if (rb == 4) return gather ? launch_rank_many_t<false, 4, true>(ix->device, grid, lds, st, a) : launch_rank_many_t<false, 4, false>(ix->device, grid, lds, st, a);
     return fail(TS_ERR_INTERNAL, "no rank_many kernel for a bf16 row of %d bytes", row_bytes);
 }
 

@@ -60,40 +60,31 @@ static void launch_scan_spec(int qb, int kr, int grid, hipStream_t st, const Sca
 }
 
 template <int DT, bool EMIT>
-static void launch_scan_generic(int qb, int kr, int grid, hipStream_t st, const ScanArgs& a) {
-    const size_t lds = 8192 + (size_t)a.ld * 4 * (qb == 4 ? 4 : 1);
-    auto go = [&](auto kern) {
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        kern<<<grid, 256, lds, st>>>(a);
-    };
-    if (qb == 4) {
-        if (EMIT || kr == 1) go(scan_generic_kernel<DT, 1, EMIT, 4>);
-        else go(scan_generic_kernel<DT, 4, EMIT, 1>);   // k > 64: four lists of 4 keys per lane do not fit; one query per pass
-    } else {
-        if (EMIT || kr == 1) go(scan_generic_kernel<DT, 1, EMIT, 1>);
-        else go(scan_generic_kernel<DT, 4, EMIT, 1>);
-    }
+static int launch_scan_generic(int dev, int qb, int kr, int grid, hipStream_t st, const ScanArgs& a) {
+    const int lds = 8192 + (int)a.ld * 4 * (qb == 4 ? 4 : 1);
+    if (qb == 4 && (EMIT || kr == 1)) return launch_lds<scan_generic_kernel<DT, 1, EMIT, 4>>(dev, grid, 256, lds, st, a);
+    if (EMIT || kr == 1) return launch_lds<scan_generic_kernel<DT, 1, EMIT, 1>>(dev, grid, 256, lds, st, a);
+    return launch_lds<scan_generic_kernel<DT, 4, EMIT, 1>>(dev, grid, 256, lds, st, a);   // k > 64: four lists of 4 keys per lane do not fit; one query per pass
 }
 
-// One scan pass configuration for (dtype, ld); returns the query-batch width used.
+// One scan pass configuration for (dtype, ld).
 template <bool EMIT>
 static int launch_scan(const ts_index* ix, ScanArgs a, int qb_pref, hipStream_t st, int grid) {
     const int kr = (a.k <= 64) ? 1 : 4;
     const bool force_generic = ix->knobs.get(K_SCAN_GENERIC, 0) != 0;
-    if (!force_generic && ix->dtype == TS_F32 && ix->ld == 768) { launch_scan_spec<0, 3, 64, EMIT>(qb_pref, kr, grid, st, a); return qb_pref; }
-    if (!force_generic && ix->dtype == TS_F32 && ix->ld == 1024) { launch_scan_spec<0, 4, 64, EMIT>(qb_pref, kr, grid, st, a); return qb_pref; }
-    if (!force_generic && ix->dtype == TS_BF16 && ix->ld == 768) { launch_scan_spec<1, 3, 32, EMIT>(qb_pref, kr, grid, st, a); return qb_pref; }
-    if (!force_generic && ix->dtype == TS_BF16 && ix->ld == 1024) { launch_scan_spec<1, 2, 64, EMIT>(qb_pref, kr, grid, st, a); return qb_pref; }
+    if (!force_generic && ix->dtype == TS_F32 && ix->ld == 768) { launch_scan_spec<0, 3, 64, EMIT>(qb_pref, kr, grid, st, a); return TS_OK; }
+    if (!force_generic && ix->dtype == TS_F32 && ix->ld == 1024) { launch_scan_spec<0, 4, 64, EMIT>(qb_pref, kr, grid, st, a); return TS_OK; }
+    if (!force_generic && ix->dtype == TS_BF16 && ix->ld == 768) { launch_scan_spec<1, 3, 32, EMIT>(qb_pref, kr, grid, st, a); return TS_OK; }
+    if (!force_generic && ix->dtype == TS_BF16 && ix->ld == 1024) { launch_scan_spec<1, 2, 64, EMIT>(qb_pref, kr, grid, st, a); return TS_OK; }
     // the other common embedding widths (MiniLM-class 384, 512): same kernel, narrower lane groups
-    if (!force_generic && ix->dtype == TS_F32 && ix->ld == 384) { launch_scan_spec<0, 3, 32, EMIT>(qb_pref, kr, grid, st, a); return qb_pref; }
-    if (!force_generic && ix->dtype == TS_BF16 && ix->ld == 384) { launch_scan_spec<1, 3, 16, EMIT>(qb_pref, kr, grid, st, a); return qb_pref; }
-    if (!force_generic && ix->dtype == TS_F32 && ix->ld == 512) { launch_scan_spec<0, 2, 64, EMIT>(qb_pref, kr, grid, st, a); return qb_pref; }
-    if (!force_generic && ix->dtype == TS_BF16 && ix->ld == 512) { launch_scan_spec<1, 2, 32, EMIT>(qb_pref, kr, grid, st, a); return qb_pref; }
+    if (!force_generic && ix->dtype == TS_F32 && ix->ld == 384) { launch_scan_spec<0, 3, 32, EMIT>(qb_pref, kr, grid, st, a); return TS_OK; }
+    if (!force_generic && ix->dtype == TS_BF16 && ix->ld == 384) { launch_scan_spec<1, 3, 16, EMIT>(qb_pref, kr, grid, st, a); return TS_OK; }
+    if (!force_generic && ix->dtype == TS_F32 && ix->ld == 512) { launch_scan_spec<0, 2, 64, EMIT>(qb_pref, kr, grid, st, a); return TS_OK; }
+    if (!force_generic && ix->dtype == TS_BF16 && ix->ld == 512) { launch_scan_spec<1, 2, 32, EMIT>(qb_pref, kr, grid, st, a); return TS_OK; }
     // any other width: queries staged in LDS, 4 per pass while they fit (ld <= 8192) and k <= 64
     const int qb = (qb_pref == 4 && a.ld <= 8192 && (EMIT || kr == 1)) ? 4 : 1;
-    if (ix->dtype == TS_F32) launch_scan_generic<0, EMIT>(qb, kr, grid, st, a);
-    else launch_scan_generic<1, EMIT>(qb, kr, grid, st, a);
-    return qb;
+    if (ix->dtype == TS_F32) return launch_scan_generic<0, EMIT>(ix->device, qb, kr, grid, st, a);
+    return launch_scan_generic<1, EMIT>(ix->device, qb, kr, grid, st, a);
 }
 
 // Reduce [slots][m] partial keys to the final k per query: select rounds of 4096-key segments.
@@ -107,11 +98,6 @@ static int run_select_rounds(ts_index* ix, int slots, int m, int k, float* out_s
         if (m > 1024 && m <= kHistSelectMax) {
             // the usual case (k <= 12 over 1024 workgroups, or k up to 256 over the fewer workgroups scan_search uses on a
             // small corpus): one launch, histogram cut instead of rounds of bitonic sorts
-            if (!ix->attr_done_hist) {
-                HIP_TRY(hipFuncSetAttribute((const void*)select_hist_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, kHistSelectLds));
-                HIP_TRY(hipFuncSetAttribute((const void*)select_hist_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, kHistSelectLds));
-                ix->attr_done_hist = true;
-            }
             SelectArgs a;
             memset(&a, 0, sizeof(a));
             a.in = in;
@@ -125,10 +111,8 @@ static int run_select_rounds(ts_index* ix, int slots, int m, int k, float* out_s
             a.qcount = qcount;
             a.out_scores = out_scores;
             a.out_idx = out_idx;
-            if (k <= 64) select_hist_kernel<1><<<slots, kLevelThreads, kHistSelectLds, st>>>(a);
-            else select_hist_kernel<4><<<slots, kLevelThreads, kHistSelectLds, st>>>(a);
-            HIP_TRY(hipGetLastError());
-            return TS_OK;
+            if (k <= 64) return launch_lds<select_hist_kernel<1>>(ix->device, slots, kLevelThreads, kHistSelectLds, st, a);
+            return launch_lds<select_hist_kernel<4>>(ix->device, slots, kLevelThreads, kHistSelectLds, st, a);
         }
         SelectArgs a;
         memset(&a, 0, sizeof(a));
@@ -218,8 +202,9 @@ int scan_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
     const bool wide_k_one_wave = k > 64 && ix->dtype == TS_BF16 && (ix->ld == 768 || ix->ld == 384);
     const int qb = ((nq >= 2 || qcount) && !wide_k_one_wave) ? 4 : 1;
     hipEvent_t stop = qcount ? nullptr : prof_begin(ix, st, ix->n);  // the MFMA path's fall-back pass is not bracketed
-    launch_scan<false>(ix, a, qb, st, grid);
+    const int rc = launch_scan<false>(ix, a, qb, st, grid);
     prof_end(stop, st);
+    TS_TRY(rc);
     HIP_TRY(hipGetLastError());
     if (one_launch) return TS_OK;
     return run_select_rounds(ix, nq, grid * k, k, out_scores, out_idx, qlist, qcount, st);
@@ -452,12 +437,13 @@ extern "C" int ts_search_biased(ts_index* ix, const void* queries, int q_dtype, 
 }
 
 template <int DT, int CH, int G>
-static void launch_rank_spec(int qb, int grid, hipStream_t st, const RankArgs& a) {
+static int launch_rank_spec(int qb, int grid, hipStream_t st, const RankArgs& a) {
     if (qb == 4) rank_kernel<DT, CH, G, 4><<<grid, 256, 0, st>>>(a);
     else rank_kernel<DT, CH, G, 1><<<grid, 256, 0, st>>>(a);
+    return TS_OK;       // the caller checks the launch
 }
 
-static void launch_rank(const ts_index* ix, const RankArgs& a, hipStream_t st, int grid) {
+static int launch_rank(const ts_index* ix, const RankArgs& a, hipStream_t st, int grid) {
     const int qb = a.nq >= 2 ? 4 : 1;
     const bool force_generic = ix->knobs.get(K_SCAN_GENERIC, 0) != 0;
     if (!force_generic && ix->dtype == TS_F32 && ix->ld == 768) return launch_rank_spec<0, 3, 64>(qb, grid, st, a);
@@ -468,14 +454,9 @@ static void launch_rank(const ts_index* ix, const RankArgs& a, hipStream_t st, i
     if (!force_generic && ix->dtype == TS_BF16 && ix->ld == 384) return launch_rank_spec<1, 3, 16>(qb, grid, st, a);
     if (!force_generic && ix->dtype == TS_F32 && ix->ld == 512) return launch_rank_spec<0, 2, 64>(qb, grid, st, a);
     if (!force_generic && ix->dtype == TS_BF16 && ix->ld == 512) return launch_rank_spec<1, 2, 32>(qb, grid, st, a);
-    const size_t lds = (size_t)a.ld * 4;
-    if (ix->dtype == TS_F32) {
-        hipFuncSetAttribute((const void*)rank_generic_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        rank_generic_kernel<0><<<grid, 256, lds, st>>>(a);
-    } else {
-        hipFuncSetAttribute((const void*)rank_generic_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        rank_generic_kernel<1><<<grid, 256, lds, st>>>(a);
-    }
+    const int lds = (int)a.ld * 4;
+    if (ix->dtype == TS_F32) return launch_lds<rank_generic_kernel<0>>(ix->device, grid, 256, lds, st, a);
+    return launch_lds<rank_generic_kernel<1>>(ix->device, grid, 256, lds, st, a);
 }
 
 // host twin of ord_f32 (common.h): the score half of a key
@@ -547,8 +528,9 @@ static int rank_impl(ts_index* ix, const void* queries, int q_dtype, int q_on_de
         a.counts = d_counts;
         a.tscore = d_tscore;
         hipEvent_t stop = prof_begin(ix, st, ix->n);
-        launch_rank(ix, a, st, ix->cu_count * kScanGridPerCU);
+        const int rc = launch_rank(ix, a, st, ix->cu_count * kScanGridPerCU);
         prof_end(stop, st);
+        TS_TRY(rc);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(counts.data(), d_counts, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
         if (target_rows) HIP_TRY(hipMemcpyAsync(tscore.data(), d_tscore, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
@@ -628,8 +610,8 @@ extern "C" int ts_scores(ts_index* ix, const void* queries, int q_dtype, int q_o
         a.nq = nb;
         a.k = 1;
         a.scores = dout + (size_t)q0 * ix->n;
-        launch_scan<true>(ix, a, nb >= 2 ? 4 : 1, st, ix->cu_count * kScanGridPerCU);
-        if (hipGetLastError() != hipSuccess) rc = fail(TS_ERR_HIP, "score kernel launch failed");
+        rc = launch_scan<true>(ix, a, nb >= 2 ? 4 : 1, st, ix->cu_count * kScanGridPerCU);
+        if (rc == TS_OK && hipGetLastError() != hipSuccess) rc = fail(TS_ERR_HIP, "score kernel launch failed");
     }
     if (!out_on_device) {
         if (rc == TS_OK && hipMemcpyAsync(out, dout, (size_t)nq * ix->n * 4, hipMemcpyDeviceToHost, st) != hipSuccess)

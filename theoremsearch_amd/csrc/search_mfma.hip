@@ -1,5 +1,7 @@
 // The matrix path of a search: planning of the threshold levels, the dense threshold sample and its
 // select, the full pass (launch_mfma*.hip hold the kernel instantiations), the final select, the exact re-run.
+// mfma_search runs the stages in order: mfma_plan (what this search is), mfma_scratch (the handle's buffers), then per level
+// mfma_sample (level 0 as the dense sample) or mfma_level (a matrix kernel + its select).
 #include "host.h"
 #include "kernels_mfma.h"
 #include "kernels_mfma16.h"
@@ -117,91 +119,111 @@ int mfma_block_queries(const ts_index* ix, int nq) {
     return nq <= 128 && ix->knobs.get(K_MFMA_GROUPS, 0) != 2 ? 128 : 256;
 }
 
-// `qmat`: the queries as the kernels multiply them (storage dtype, row stride d = ld, a whole launch's worth of rows):
-// the prepared copy, or the caller's own device matrix when it already has that form (`in_place`).
-int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx, hipStream_t st, ts_search_stats* stats,
-                       const void* qmat, bool in_place) {
+// What one search of `nq` queries for `k` results on this handle is: every decision, made once (mfma_plan) and read by the
+// stages below.
+struct MfmaPlan {
+    std::vector<Level> lv;      // threshold levels, sparsest first; the last one is the full pass
+    int kk, variant;
+    bool shape16, statistical, dense_sample, dense0;
+    bool screen_diag, screen, ksplit_form, pair;
+    int nq_launch, groups, nb16;
+    int grid, wgs, nwriters, priv_cap, pair_lag;
+    int stat_cands;
+    int64_t pop;
+    float z_tail, tail_p;
+    double sample_rows;
+    bool balance;
+};
+
+static MfmaPlan mfma_plan(const ts_index* ix, int nq, int k) {
+    MfmaPlan p;
     // threshold rank: the k-th best of a sample is already a valid lower bound of the final k-th best; private
     // lists + spill absorb the run-to-run spread of the candidate count, so no safety margin in the rank
-    const int kk = std::max(k, ix->knobs.get(K_MFMA_MIN_RANK, 1));
-    const int variant = ix->knobs.get(K_MFMA_VARIANT, 0);
-    const bool shape16 = use_shape16(ix);
-    const int groups = shape16 ? 0 : mfma_block_queries(ix, nq) / 128;
+    p.kk = std::max(k, ix->knobs.get(K_MFMA_MIN_RANK, 1));
+    p.variant = ix->knobs.get(K_MFMA_VARIANT, 0);
+    p.shape16 = use_shape16(ix);
+    p.nq_launch = mfma_block_queries(ix, nq);
+    p.groups = p.shape16 ? 0 : p.nq_launch / 128;
     // Threshold of the full pass: by default extrapolated from ONE unthresholded sample (Gaussian tail of the
     // sample's scores, verified afterwards by the candidate count); TS_MFMA_STAT=0 selects the chain of
     // guaranteed lower bounds (more sample rows to scan, no re-runs ever).
-    const bool statistical = ix->knobs.get(K_MFMA_STAT, 1) != 0;
-    const std::vector<Level> lv = plan_levels(ix->knobs, ix->n, kk, statistical);
+    p.statistical = ix->knobs.get(K_MFMA_STAT, 1) != 0;
+    p.lv = plan_levels(ix->knobs, ix->n, p.kk, p.statistical);
+    const std::vector<Level>& lv = p.lv;
     // TS_MFMA_VARIANT 9 .. 13: the timing-only forms of the int8 screen (diagnostic build only; launch_screen8*.hip)
 #ifdef TS_DIAG
-    const bool screen_diag = variant >= 9 && variant <= 13;
+    p.screen_diag = p.variant >= 9 && p.variant <= 13;
 #else
-    const bool screen_diag = false;
+    p.screen_diag = false;
 #endif
     // bf16 at d = 768 (or, with TS_MFMA_SCREEN_WIDE, d = 1024) behind a threshold: the full pass runs as the int8 screen + exact
     // rescore (kernels_screen8.h), the same candidates >= thr for the final select
-    const bool screen = shape16 && (variant == 0 || screen_diag) && lv.size() >= 2 && lv.back().stride == 1 && lv.back().run == 1 &&
-                        screen_usable(ix);
+    p.screen = p.shape16 && (p.variant == 0 || p.screen_diag) && lv.size() >= 2 && lv.back().stride == 1 && lv.back().run == 1 &&
+               screen_usable(ix);
     // d = 1024, 193 .. 256 queries: the unscreened pass is a launch of workgroup pairs, in the k-split form unless TS_MFMA_PAIR=1.
     // The screen holds all 256 queries in ONE unpaired launch (four blocks per wave: an int8 query fragment is half the
     // registers); its rescore adds every score in the form the pairs would have (plain chain or two half-chains), bit for bit.
     const bool pair_form = mfma_pairs(ix, nq);
-    const bool ksplit_form = pair_form && ix->knobs.get(K_MFMA_PAIR, 2) != 1;
-    const bool pair = pair_form && !screen;
-    const int nb16 = pair ? 2 : (shape16 ? mfma_block_queries(ix, nq) / 64 : 0);
-    if (!ix->attr_done) {
-        HIP_TRY(hipFuncSetAttribute((const void*)level_select_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, kLevelLds));
-        HIP_TRY(hipFuncSetAttribute((const void*)level_select_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, kLevelLds));
-        ix->attr_done = true;
-    }
+    p.ksplit_form = pair_form && ix->knobs.get(K_MFMA_PAIR, 2) != 1;
+    p.pair = pair_form && !p.screen;
+    p.pair_lag = p.pair ? std::max(0, ix->knobs.get(K_MFMA_PAIR_LAG, 1)) : 0;
+    p.nb16 = p.pair ? 2 : (p.shape16 ? p.nq_launch / 64 : 0);
     // The sparsest level (every score a candidate, at most kLevelSortMax rows) runs as a dense score matrix + one select per
     // query (kernels_sample.h) instead of the full-pass kernel over the sample + a gather from lane-private lists; the
     // latter stays selectable (TS_MFMA_SAMPLE=0) as the A/B partner and serves the thresholded sparse levels of the
     // guaranteed chain (TS_MFMA_STAT=0).
-    const bool dense_sample = ix->knobs.get(K_MFMA_SAMPLE, 1) != 0;
-    if (dense_sample && !ix->sample) HIP_TRY(hipMalloc((void**)&ix->sample, (size_t)kMfmaQ * kLevelSortMax * 4));
-    const int grid = mfma_grid(ix);
-    const int wgs = pair ? grid / 2 : grid;                 // tile ranges of the full pass: one per workgroup, or one per pair
+    p.dense_sample = ix->knobs.get(K_MFMA_SAMPLE, 1) != 0;
+    // the sparsest level as the dense sample (below): its launch also makes the screen's image of the queries
+    p.dense0 = lv.size() >= 2 && p.dense_sample && lv[0].ntiles * kTileRows <= kLevelSortMax;
+    p.grid = mfma_grid(ix);
+    p.wgs = p.pair ? p.grid / 2 : p.grid;                 // tile ranges of the full pass: one per workgroup, or one per pair
     // lane-private candidate lists: 2 writers x 32 entries per workgroup and query (32x32 shape) or 4 x 16 (16x16 shape)
-    const int nwriters = (shape16 ? 4 : 2) * grid;
-    const int priv_cap = shape16 ? kMfma16PrivCap : kMfmaPrivCap;
-    if (ix->priv_writers < 4 * grid) {
-        if (ix->priv) HIP_TRY(hipFree(ix->priv));
-        if (ix->pcount) HIP_TRY(hipFree(ix->pcount));
-        ix->priv = nullptr; ix->pcount = nullptr; ix->priv_writers = 0;
-        static_assert(4 * kMfma16PrivCap == 2 * kMfmaPrivCap, "both shapes use the same list bytes per workgroup");
-        HIP_TRY(hipMalloc((void**)&ix->priv, (size_t)kMfmaQ * 4 * grid * kMfma16PrivCap * 8));
-        HIP_TRY(hipMalloc((void**)&ix->pcount, (size_t)kMfmaQ * 4 * grid * 4));
-        ix->priv_writers = 4 * grid;
-    }
+    p.nwriters = (p.shape16 ? 4 : 2) * p.grid;
+    p.priv_cap = p.shape16 ? kMfma16PrivCap : kMfmaPrivCap;
     // Expected candidates per query of the full pass under the estimate.  Every candidate costs the pass ~0.3 us of one
     // CU's time (the appending wave holds the other three at the next barrier), whatever N: 160 per query were 10 % of
     // a 1.25M-row shard's pass and 1 % of the 10M pass; an under-filled query (fewer than k back) costs an exact scan
     // pass.  6 k (at least 64) keeps the under-fill probability negligible for Gaussian-like scores (Poisson mean 64
     // against k = 10, estimate error e^+-0.15) - measured on 10M / 1.25M x 768: 160 / 96 / 64 / 40 expected candidates
     // -> 0 re-runs, 24 -> 5-7 re-runs per 256 queries; full pass 0.459 / 0.447 / 0.438 / 0.424 ms on the shard.
-    const int stat_cands = std::min(2048, std::max(2 * kk, ix->knobs.get(K_MFMA_STAT_CANDS, std::max(64, 6 * kk))));
+    p.stat_cands = std::min(2048, std::max(2 * p.kk, ix->knobs.get(K_MFMA_STAT_CANDS, std::max(64, 6 * p.kk))));
     // rows the candidates are drawn from: all of them, or the rows a filter allows (the sample sees only those too)
-    const int64_t pop = ix->active_mask ? ix->active_allowed : ix->n;
-    const float z_tail = (statistical && lv.size() == 2)
-                             ? (float)normal_tail_z(std::min(0.25, (double)stat_cands / (double)std::max<int64_t>(pop, 1)))
-                             : 0.0f;
+    p.pop = ix->active_mask ? ix->active_allowed : ix->n;
+    p.z_tail = (p.statistical && lv.size() == 2)
+                   ? (float)normal_tail_z(std::min(0.25, (double)p.stat_cands / (double)std::max<int64_t>(p.pop, 1)))
+                   : 0.0f;
     // Second estimate (exponential tail fit of the sample's order statistics, kernels_select.h), for score distributions
     // with heavier tails than a Gaussian.  Only where it is needed: when the guaranteed bound alone (the kk-th best of
     // the sample admits ~kk * N / sample rows) would swamp the candidate buffer - large corpora; it aims at
     // max(2048, 8 kk) expected candidates, a quarter of the buffer.
-    const double sample_rows = (double)std::max<int64_t>(1, lv[0].ntiles * kTileRows);
-    const bool bound_swamps = (double)kk * (double)ix->n / sample_rows > 0.5 * kCandCap;
-    const float tail_p = (z_tail > 0.0f && bound_swamps && ix->knobs.get(K_MFMA_TAIL_FIT, 1))
-                             ? (float)std::min(0.25, (double)std::max(2048, 8 * kk) / (double)std::max<int64_t>(pop, 1))
-                             : 0.0f;
+    p.sample_rows = (double)std::max<int64_t>(1, lv[0].ntiles * kTileRows);
+    const bool bound_swamps = (double)p.kk * (double)ix->n / p.sample_rows > 0.5 * kCandCap;
+    p.tail_p = (p.z_tail > 0.0f && bound_swamps && ix->knobs.get(K_MFMA_TAIL_FIT, 1))
+                   ? (float)std::min(0.25, (double)std::max(2048, 8 * p.kk) / (double)std::max<int64_t>(p.pop, 1))
+                   : 0.0f;
     // Feedback partition of the full pass (16x16 kernel): the final select moves the workgroups' tile boundaries towards
     // equal finishing times for the next search (kernels_select.h, rebalance_tiles).  The table starts as equal shares and
     // is re-made whenever the grid or the number of tiles changes.
-    const int64_t full_tiles = lv.back().ntiles;
-    const bool balance = shape16 && ix->knobs.get(K_MFMA_BALANCE, 1) != 0 && wgs >= 8 && wgs <= 256 && lv.back().stride == 1 &&
-                         lv.back().run == 1 && full_tiles >= 32 * (int64_t)wgs && (variant == 0 || variant == 3 || screen_diag);
-    if (balance && (ix->part_g != wgs || ix->part_ntiles != full_tiles)) {
+    p.balance = p.shape16 && ix->knobs.get(K_MFMA_BALANCE, 1) != 0 && p.wgs >= 8 && p.wgs <= 256 && lv.back().stride == 1 &&
+                lv.back().run == 1 && lv.back().ntiles >= 32 * (int64_t)p.wgs && (p.variant == 0 || p.variant == 3 || p.screen_diag);
+    return p;
+}
+
+// The per-handle scratch this plan needs: made on first use, re-made when the grid outgrows it.
+static int mfma_scratch(ts_index* ix, const MfmaPlan& p, hipStream_t st) {
+    if (p.dense_sample && !ix->sample) HIP_TRY(hipMalloc((void**)&ix->sample, (size_t)kMfmaQ * kLevelSortMax * 4));
+    if (ix->priv_writers < 4 * p.grid) {
+        if (ix->priv) HIP_TRY(hipFree(ix->priv));
+        if (ix->pcount) HIP_TRY(hipFree(ix->pcount));
+        ix->priv = nullptr; ix->pcount = nullptr; ix->priv_writers = 0;
+        static_assert(4 * kMfma16PrivCap == 2 * kMfmaPrivCap, "both shapes use the same list bytes per workgroup");
+        HIP_TRY(hipMalloc((void**)&ix->priv, (size_t)kMfmaQ * 4 * p.grid * kMfma16PrivCap * 8));
+        HIP_TRY(hipMalloc((void**)&ix->pcount, (size_t)kMfmaQ * 4 * p.grid * 4));
+        ix->priv_writers = 4 * p.grid;
+    }
+    const int wgs = p.wgs;
+    const int64_t full_tiles = p.lv.back().ntiles;
+    if (p.balance && (ix->part_g != wgs || ix->part_ntiles != full_tiles)) {
         if (ix->part_g != wgs) {
             if (ix->part) HIP_TRY(hipFree(ix->part));
             if (ix->wg_ticks) HIP_TRY(hipFree(ix->wg_ticks));
@@ -217,241 +239,253 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
         HIP_TRY(hipStreamSynchronize(st));          // `equal` is a local; this happens once per (grid, size)
         ix->part_ntiles = full_tiles;
     }
-    // the sparsest level as the dense sample (below): its launch also makes the screen's image of the queries
-    const bool dense0 = lv.size() >= 2 && dense_sample && lv[0].ntiles * kTileRows <= kLevelSortMax;
-    if (screen) TS_TRY(screen_prepare(ix, qmat, mfma_block_queries(ix, nq), !dense0, st));
-    for (size_t i = 0; i < lv.size(); ++i) {
-        const bool full_pass = (i + 1 == lv.size());
-        if (i == 0 && !full_pass && dense_sample && lv[0].ntiles * kTileRows <= kLevelSortMax) {
-            SampleArgs sa;
-            memset(&sa, 0, sizeof(sa));
-            sa.corpus = ix->rows;
-            sa.n = ix->n;
-            sa.ld = (int)ix->ld;
-            sa.ntiles = lv[0].ntiles;
-            sa.tile_stride = lv[0].stride;
-            sa.run = lv[0].run;
-            sa.q = qmat;
-            sa.nq = nq;
-            sa.row_mask = ix->active_mask;
-            sa.scores = ix->sample;
-            sa.row_stride = (int)((lv[0].ntiles * kTileRows + 63) / 64 * 64);
-            sa.fb_count = ix->fb_count;
-            // 32 rows per workgroup and one 64-query chunk: 512 workgroups of 50 KB LDS at 4,096 rows x 256 queries, two to
-            // a CU (64-row workgroups serving two chunks each measured the same: 15.2 / 25.0 us against 14.9 / 24.3 us at
-            // 4,096 / 8,192 rows - the launch is latency, not work)
-            const bool f32 = ix->dtype == TS_F32;
-            const int nchunks = (nq + 63) / 64;
-            const int wg_rows = 32;
-            // the previous search's full pass left its workgroups' times: one extra workgroup of this launch moves the
-            // tile boundaries before this search's pass reads them
-            if (ix->rebalance_pending && balance && ix->rebalance_grid == wgs && ix->rebalance_grid <= 256) {
-                sa.part = ix->part;
-                sa.wg_ticks = ix->wg_ticks;
-                sa.part_g = ix->rebalance_grid;
-                const int b = ix->knobs.get(K_MFMA_BALANCE, 1);      // TS_MFMA_BALANCE = n > 1: gain n / 10 (default 0.7)
-                sa.part_gain = (b >= 2 && b <= 10) ? 0.1f * (float)b : 0.7f;
-            }
-            ix->rebalance_pending = false;
-            if (screen) {
-                sa.scr_qimg = (signed char*)ix->scr_q;
-                sa.scr_qmeta = (float4*)ix->scr_qmeta;
-                sa.scr_count = ix->scr_count;
-                sa.scr_nrows = std::min(mfma_block_queries(ix, nq), kMfmaQ);
-            }
-            const dim3 sgrid((unsigned)(sa.row_stride / wg_rows), (unsigned)(nchunks + ((sa.part || sa.scr_qimg) ? 1 : 0)));
-            const int slds = sample_lds_bytes(wg_rows, (int)(ix->ld * ix->elem()));
-            constexpr int kSampleLdsMax = 144 * 1024;   // dynamic part; the kernel also has a few hundred static bytes (rebalance_tiles)
-            if (slds > kSampleLdsMax) return fail(TS_ERR_INTERNAL, "threshold sample: rows of %lld bytes do not fit the LDS", (long long)(ix->ld * ix->elem()));
-            {
-                static std::atomic<unsigned long long> sample_attr{0};
-                int dev = 0;
-                HIP_TRY(hipGetDevice(&dev));
-                const unsigned long long bit = 1ull << (dev & 63);
-                if (!(sample_attr.load(std::memory_order_acquire) & bit)) {
-                    HIP_TRY(hipFuncSetAttribute((const void*)sample_scores_kernel<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, kSampleLdsMax));
-                    HIP_TRY(hipFuncSetAttribute((const void*)sample_scores_kernel<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, kSampleLdsMax));
-                    sample_attr.fetch_or(bit, std::memory_order_release);
-                }
-            }
-            if (f32) sample_scores_kernel<true, 2><<<sgrid, 256, slds, st>>>(sa);
-            else sample_scores_kernel<false, 2><<<sgrid, 256, slds, st>>>(sa);
-            HIP_TRY(hipGetLastError());
-            LevelArgs l;
-            memset(&l, 0, sizeof(l));
-            l.count = ix->count;
-            l.kk = kk;
-            l.thr = ix->thr;
-            l.z_tail = z_tail;
-            l.tail_p = tail_p;
-            l.tail_z = (float)normal_tail_z(std::min(0.25, 32.0 / sample_rows));
-            l.nq = nq;
-            // where the select cuts first: ~2 kl of the sample's live rows above it on Gaussian-like scores
-            const int kl = tail_p > 0.0f ? std::max(kk, 32) : kk;
-            const double live = sample_rows * (double)pop / (double)std::max<int64_t>(ix->n, 1);
-            const float z_sel = (float)normal_tail_z(std::min(0.25, 2.0 * kl / std::max(live, 1.0)));
-            sample_select_fast_kernel<kSelThreads><<<nq, kSelThreads, 0, st>>>(l, ix->sample, sa.row_stride, z_sel);
-            HIP_TRY(hipGetLastError());
-            continue;
-        }
-        MfmaArgs a;
-        a.corpus = (const unsigned short*)ix->rows;
-        a.n = ix->n;
-        a.ntiles = lv[i].ntiles;
-        a.tile_stride = lv[i].stride;
-        a.run = lv[i].run;
-        a.q = (const unsigned short*)qmat;
-        a.thr = ix->thr;
-        a.nq = ix->knobs.get(K_MFMA_NO_IDLE, 0) ? 256 : nq;
-        a.row_mask = ix->active_mask;
-        a.ahead = ix->knobs.get(K_MFMA_AHEAD, 0);
-        a.priv = ix->priv;
-        a.pcount = ix->pcount;
-        a.cand = ix->cand;
-        a.count = ix->count;
-        a.cap = kCandCap;
-        a.first_level = (i == 0) ? 1 : 0;      // thresholds and per-search counters are initialised inside the first launch of a search
-        a.nq_real = nq;
-        a.fb_count = ix->fb_count;
-        a.part = (balance && full_pass) ? ix->part : nullptr;
-        a.wg_ticks = (balance && full_pass) ? ix->wg_ticks : nullptr;
-        a.pair = (pair && full_pass) ? (ksplit_form ? 2 : 1) : 0;      // 2: the k-split form (TS_MFMA_PAIR=1: two blocks per wave over the whole row)
-        a.pair_pos = nullptr;
-        a.pair_lag = 0;
-        if (a.pair && ix->knobs.get(K_MFMA_PAIR_LAG, 1) > 0) {
-            if (!ix->pair_pos) {
-                // one word per workgroup of the pass (index 2 * pair + half < grid): sized for the largest grid the option allows
-                HIP_TRY(hipMalloc((void**)&ix->pair_pos, kMfmaMaxGrid * sizeof(unsigned)));
-                HIP_TRY(hipMemsetAsync(ix->pair_pos, 0, kMfmaMaxGrid * sizeof(unsigned), st));
-            }
-            a.pair_pos = ix->pair_pos;
-            a.pair_lag = ix->knobs.get(K_MFMA_PAIR_LAG, 1);
-        }
-        a.dbg = nullptr;
-        a.scr_tile = nullptr;
-        a.scr_q = nullptr;
+    if (p.pair_lag > 0 && !ix->pair_pos) {
+        // one word per workgroup of the pass (index 2 * pair + half < grid): sized for the largest grid the option allows
+        HIP_TRY(hipMalloc((void**)&ix->pair_pos, kMfmaMaxGrid * sizeof(unsigned)));
+        HIP_TRY(hipMemsetAsync(ix->pair_pos, 0, kMfmaMaxGrid * sizeof(unsigned), st));
+    }
 #ifdef TS_DIAG
-        if (variant >= 3) {
-            if (!ix->dbg) HIP_TRY(hipMalloc((void**)&ix->dbg, 2048 * 4 * 4 * 8));
-            a.dbg = ix->dbg;
-        }
+    if (p.variant >= 3 && !ix->dbg) HIP_TRY(hipMalloc((void**)&ix->dbg, 2048 * 4 * 4 * 8));
 #endif
-        hipEvent_t stop = full_pass ? prof_begin(ix, st, ix->n) : nullptr;  // only the full pass is bracketed
-        int rc;
-        if (screen && full_pass) rc = screen_full_pass(ix, nb16, nq, grid, screen_diag ? variant : 0, ksplit_form, st, a);
-        else if (ix->dtype == TS_F32 && shape16) rc = launch_pass_mfma16_f32(ix->d, nb16, full_pass, grid, st, a);
-        else if (ix->dtype == TS_F32) rc = launch_pass_mfma32_f32(full_pass, variant, grid, st, a);
-        else if (shape16) rc = launch_pass_mfma16(ix->d, nb16, full_pass, variant, grid, st, a);
-        else rc = launch_pass_mfma32(ix->d, groups, full_pass, variant, grid, st, a);
-        prof_end(stop, st);
-        TS_TRY(rc);
+    return TS_OK;
+}
+
+// Level 0 as the dense threshold sample: the score matrix (with the riders its launch has room for: last search's rebalance,
+// the screen's image of the queries) and one select per query.
+static int mfma_sample(ts_index* ix, const MfmaPlan& p, int nq, const void* qmat, hipStream_t st) {
+    const Level& lv0 = p.lv[0];
+    SampleArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.corpus = ix->rows;
+    sa.n = ix->n;
+    sa.ld = (int)ix->ld;
+    sa.ntiles = lv0.ntiles;
+    sa.tile_stride = lv0.stride;
+    sa.run = lv0.run;
+    sa.q = qmat;
+    sa.nq = nq;
+    sa.row_mask = ix->active_mask;
+    sa.scores = ix->sample;
+    sa.row_stride = (int)((lv0.ntiles * kTileRows + 63) / 64 * 64);
+    sa.fb_count = ix->fb_count;
+    // 32 rows per workgroup and one 64-query chunk: 512 workgroups of 50 KB LDS at 4,096 rows x 256 queries, two to
+    // a CU (64-row workgroups serving two chunks each measured the same: 15.2 / 25.0 us against 14.9 / 24.3 us at
+    // 4,096 / 8,192 rows - the launch is latency, not work)
+    const bool f32 = ix->dtype == TS_F32;
+    const int nchunks = (nq + 63) / 64;
+    const int wg_rows = 32;
+    // the previous search's full pass left its workgroups' times: one extra workgroup of this launch moves the
+    // tile boundaries before this search's pass reads them
+    if (ix->rebalance_pending && p.balance && ix->rebalance_grid == p.wgs && ix->rebalance_grid <= 256) {
+        sa.part = ix->part;
+        sa.wg_ticks = ix->wg_ticks;
+        sa.part_g = ix->rebalance_grid;
+        const int b = ix->knobs.get(K_MFMA_BALANCE, 1);      // TS_MFMA_BALANCE = n > 1: gain n / 10 (default 0.7)
+        sa.part_gain = (b >= 2 && b <= 10) ? 0.1f * (float)b : 0.7f;
+    }
+    ix->rebalance_pending = false;
+    if (p.screen) {
+        sa.scr_qimg = (signed char*)ix->scr_q;
+        sa.scr_qmeta = (float4*)ix->scr_qmeta;
+        sa.scr_count = ix->scr_count;
+        sa.scr_nrows = std::min(p.nq_launch, kMfmaQ);
+    }
+    const dim3 sgrid((unsigned)(sa.row_stride / wg_rows), (unsigned)(nchunks + ((sa.part || sa.scr_qimg) ? 1 : 0)));
+    const int slds = sample_lds_bytes(wg_rows, (int)(ix->ld * ix->elem()));
+    constexpr int kSampleLdsMax = 144 * 1024;   // dynamic part; the kernel also has a few hundred static bytes (rebalance_tiles)
+    if (slds > kSampleLdsMax) return fail(TS_ERR_INTERNAL, "threshold sample: rows of %lld bytes do not fit the LDS", (long long)(ix->ld * ix->elem()));
+    if (f32) TS_TRY((launch_lds<sample_scores_kernel<true, 2>, kSampleLdsMax>(ix->device, sgrid, 256, slds, st, sa)));
+    else TS_TRY((launch_lds<sample_scores_kernel<false, 2>, kSampleLdsMax>(ix->device, sgrid, 256, slds, st, sa)));
+    LevelArgs l;
+    memset(&l, 0, sizeof(l));
+    l.count = ix->count;
+    l.kk = p.kk;
+    l.thr = ix->thr;
+    l.z_tail = p.z_tail;
+    l.tail_p = p.tail_p;
+    l.tail_z = (float)normal_tail_z(std::min(0.25, 32.0 / p.sample_rows));
+    l.nq = nq;
+    // where the select cuts first: ~2 kl of the sample's live rows above it on Gaussian-like scores
+    const int kl = p.tail_p > 0.0f ? std::max(p.kk, 32) : p.kk;
+    const double live = p.sample_rows * (double)p.pop / (double)std::max<int64_t>(ix->n, 1);
+    const float z_sel = (float)normal_tail_z(std::min(0.25, 2.0 * kl / std::max(live, 1.0)));
+    sample_select_fast_kernel<kSelThreads><<<nq, kSelThreads, 0, st>>>(l, ix->sample, sa.row_stride, z_sel);
+    HIP_TRY(hipGetLastError());
+    return TS_OK;
+}
+
 #ifdef TS_DIAG
-        if (a.dbg && full_pass && shape16 && (variant == 3 || (screen && variant == 11))) {
-            // clock probe (MI355X_MICROARCH.md "DVFS give-back" item 6): shader cycles / 100 MHz ticks around the tile loop,
-            // median over workgroups
-            std::vector<unsigned long long> h((size_t)grid * 4);
-            HIP_TRY(hipStreamSynchronize(st));
-            HIP_TRY(hipMemcpy(h.data(), a.dbg, h.size() * 8, hipMemcpyDeviceToHost));
-            std::vector<double> ghz, cpu_;
-            for (int w = 0; w < grid; ++w)
-                if (h[w * 4 + 1] > 0 && h[w * 4 + 2] > 0) {
-                    ghz.push_back((double)h[w * 4] / (double)h[w * 4 + 1] * 0.1);
-                    cpu_.push_back((double)h[w * 4] / (double)h[w * 4 + 2]);
-                }
-            if (!ghz.empty()) {
-                std::sort(ghz.begin(), ghz.end());
-                std::sort(cpu_.begin(), cpu_.end());
-                ix->probe_ghz = ghz[ghz.size() / 2];
-                ix->probe_cycles_per_unit = cpu_[cpu_.size() / 2];
-                ix->probe_units = (double)h[2];
-                if (ix->knobs.get(K_PROBE_SPREAD, 0)) {
-                    // the launch ends with its slowest workgroup: time inside the tile loop per workgroup (100 MHz ticks),
-                    // and its mean by workgroup id % 8 (the XCD under round-robin dispatch)
-                    std::vector<double> us;
-                    double xm[8] = {0}, xn[8] = {0};
-                    for (int w = 0; w < grid; ++w)
-                        if (h[w * 4 + 1] > 0) {
-                            us.push_back((double)h[w * 4 + 1] * 0.01);
-                            xm[w & 7] += us.back();
-                            xn[w & 7] += 1;
-                        }
-                    std::sort(us.begin(), us.end());
-                    fprintf(stderr, "[tsearch probe] tile loop per workgroup: min %.1f us, median %.1f, max %.1f; mean by id %% 8:", us.front(),
-                            us[us.size() / 2], us.back());
-                    for (int x = 0; x < 8; ++x) fprintf(stderr, " %.1f", xm[x] / std::max(1.0, xn[x]));
-                    fprintf(stderr, "\n");
-                }
+// What a timing variant's full pass left in MfmaArgs::dbg, read back and printed (or kept in the handle: the clock probe).
+static int mfma_diag_readout(ts_index* ix, const MfmaPlan& p, const unsigned long long* dbg, hipStream_t st) {
+    const int grid = p.grid, variant = p.variant;
+    if (p.shape16 && (variant == 3 || (p.screen && variant == 11))) {
+        // clock probe (MI355X_MICROARCH.md "DVFS give-back" item 6): shader cycles / 100 MHz ticks around the tile loop,
+        // median over workgroups
+        std::vector<unsigned long long> h((size_t)grid * 4);
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost));
+        std::vector<double> ghz, cpu_;
+        for (int w = 0; w < grid; ++w)
+            if (h[w * 4 + 1] > 0 && h[w * 4 + 2] > 0) {
+                ghz.push_back((double)h[w * 4] / (double)h[w * 4 + 1] * 0.1);
+                cpu_.push_back((double)h[w * 4] / (double)h[w * 4 + 2]);
             }
-        } else if (a.dbg && full_pass && shape16 && (variant == 5 || (screen && variant == 10))) {
-            std::vector<unsigned long long> h((size_t)grid * 16);
-            HIP_TRY(hipStreamSynchronize(st));
-            HIP_TRY(hipMemcpy(h.data(), a.dbg, h.size() * 8, hipMemcpyDeviceToHost));
-            const double units = (double)(lv.back().ntiles * (variant == 10 ? (ix->d == 1024 ? Mfma16Dims<512>::kUnits : Mfma16Dims<384>::kUnits) : MfmaDims<768>::kUnits)) / grid;
-            for (int wv = 0; wv < 4; ++wv) {
-                double tot = 0, vm = 0, bar = 0, dma = 0;
-                for (int w = wv; w < grid * 4; w += 4) { tot += h[w * 4]; vm += h[w * 4 + 1]; bar += h[w * 4 + 2]; dma += h[w * 4 + 3]; }
-                if (variant == 10)
-                    fprintf(stderr, "[tsearch stamps8] wave %d per tile: total %.0f cycles, vmcnt wait %.0f, barrier wait %.0f, tile tail %.0f (drain to end of epilogue; stamp cost ~40 each included)\n",
-                            wv, tot / grid / units, vm / grid / units, bar / grid / units, dma / grid / units);
-                else
-                    fprintf(stderr, "[tsearch stamps16] wave %d per unit: total %.0f cycles, vmcnt wait %.0f, barrier wait %.0f, DMA issue %.0f (6 pieces; stamp cost ~40 each included)\n",
-                            wv, tot / grid / units, vm / grid / units, bar / grid / units, dma / grid / units);
-            }
-        } else if (a.dbg && full_pass && !shape16) {
-            std::vector<unsigned long long> h((size_t)grid * 16);
-            HIP_TRY(hipStreamSynchronize(st));
-            HIP_TRY(hipMemcpy(h.data(), a.dbg, h.size() * 8, hipMemcpyDeviceToHost));
-            for (int wv = 0; wv < 4; ++wv) {  // by wave of the workgroup: with small batches the waves differ
-                double tot = 0, vm = 0, bar = 0, units = 0;
-                for (int w = wv; w < grid * 4; w += 4) { tot += h[w * 4]; vm += h[w * 4 + 1]; bar += h[w * 4 + 2]; units += h[w * 4 + 3]; }
-                fprintf(stderr, "[tsearch stamps] wave %d per unit: total %.0f cycles, vmcnt wait %.0f, barrier wait %.0f (units/wave %.0f)\n",
-                        wv, tot / units, vm / units, bar / units, units / grid);
+        if (!ghz.empty()) {
+            std::sort(ghz.begin(), ghz.end());
+            std::sort(cpu_.begin(), cpu_.end());
+            ix->probe_ghz = ghz[ghz.size() / 2];
+            ix->probe_cycles_per_unit = cpu_[cpu_.size() / 2];
+            ix->probe_units = (double)h[2];
+            if (ix->knobs.get(K_PROBE_SPREAD, 0)) {
+                // the launch ends with its slowest workgroup: time inside the tile loop per workgroup (100 MHz ticks),
+                // and its mean by workgroup id % 8 (the XCD under round-robin dispatch)
+                std::vector<double> us;
+                double xm[8] = {0}, xn[8] = {0};
+                for (int w = 0; w < grid; ++w)
+                    if (h[w * 4 + 1] > 0) {
+                        us.push_back((double)h[w * 4 + 1] * 0.01);
+                        xm[w & 7] += us.back();
+                        xn[w & 7] += 1;
+                    }
+                std::sort(us.begin(), us.end());
+                fprintf(stderr, "[tsearch probe] tile loop per workgroup: min %.1f us, median %.1f, max %.1f; mean by id %% 8:", us.front(),
+                        us[us.size() / 2], us.back());
+                for (int x = 0; x < 8; ++x) fprintf(stderr, " %.1f", xm[x] / std::max(1.0, xn[x]));
+                fprintf(stderr, "\n");
             }
         }
+    } else if (p.shape16 && (variant == 5 || (p.screen && variant == 10))) {
+        std::vector<unsigned long long> h((size_t)grid * 16);
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost));
+        const double units = (double)(p.lv.back().ntiles * (variant == 10 ? (ix->d == 1024 ? Mfma16Dims<512>::kUnits : Mfma16Dims<384>::kUnits) : MfmaDims<768>::kUnits)) / grid;
+        for (int wv = 0; wv < 4; ++wv) {
+            double tot = 0, vm = 0, bar = 0, dma = 0;
+            for (int w = wv; w < grid * 4; w += 4) { tot += h[w * 4]; vm += h[w * 4 + 1]; bar += h[w * 4 + 2]; dma += h[w * 4 + 3]; }
+            if (variant == 10)
+                fprintf(stderr, "[tsearch stamps8] wave %d per tile: total %.0f cycles, vmcnt wait %.0f, barrier wait %.0f, tile tail %.0f (drain to end of epilogue; stamp cost ~40 each included)\n",
+                        wv, tot / grid / units, vm / grid / units, bar / grid / units, dma / grid / units);
+            else
+                fprintf(stderr, "[tsearch stamps16] wave %d per unit: total %.0f cycles, vmcnt wait %.0f, barrier wait %.0f, DMA issue %.0f (6 pieces; stamp cost ~40 each included)\n",
+                        wv, tot / grid / units, vm / grid / units, bar / grid / units, dma / grid / units);
+        }
+    } else if (!p.shape16) {
+        std::vector<unsigned long long> h((size_t)grid * 16);
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost));
+        for (int wv = 0; wv < 4; ++wv) {  // by wave of the workgroup: with small batches the waves differ
+            double tot = 0, vm = 0, bar = 0, units = 0;
+            for (int w = wv; w < grid * 4; w += 4) { tot += h[w * 4]; vm += h[w * 4 + 1]; bar += h[w * 4 + 2]; units += h[w * 4 + 3]; }
+            fprintf(stderr, "[tsearch stamps] wave %d per unit: total %.0f cycles, vmcnt wait %.0f, barrier wait %.0f (units/wave %.0f)\n",
+                    wv, tot / units, vm / units, bar / units, units / grid);
+        }
+    }
+    return TS_OK;
+}
 #endif
-        LevelArgs l;
-        memset(&l, 0, sizeof(l));
-        l.priv = ix->priv;
-        l.pcount = ix->pcount;
-        l.nwriters = (shape16 && full_pass) ? 0 : nwriters;   // the 16x16 full pass stages its candidates in LDS: shared lists only
-        l.priv_cap = priv_cap;
-        l.cand = ix->cand;
-        l.count = ix->count;
-        l.cap = kCandCap;
-        l.kk = kk;
-        l.thr = ix->thr;
-        l.final_level = full_pass;
-        l.z_tail = full_pass ? 0.0f : z_tail;
-        l.tail_p = full_pass ? 0.0f : tail_p;
-        l.tail_z = (float)normal_tail_z(std::min(0.25, 32.0 / sample_rows));
-        // fewer candidates back than there are answers = the threshold was too high (an estimate that overshot, or a sample
-        // score that differs from the pass's in the last bit): exact re-run
-        l.min_fill = (int)std::min<int64_t>(k, pop);
-        l.out_scores = out_scores;
-        l.out_idx = out_idx;
-        l.k_user = k;
-        l.row_offset = ix->row_offset;
-        l.id_map = ix->id_map;
-        l.fb_list = ix->fb_list;
-        l.fb_count = ix->fb_count;
-        l.stat_q = ix->stat;
-        l.nq = nq;
-        if (kk <= 64) level_select_kernel<1><<<nq, kLevelThreads, kLevelLds, st>>>(l);
-        else level_select_kernel<4><<<nq, kLevelThreads, kLevelLds, st>>>(l);
-        HIP_TRY(hipGetLastError());
+
+// Level `i` on a matrix kernel (the full pass, or a sparse level of the guaranteed chain / of TS_MFMA_SAMPLE=0) and its select.
+static int mfma_level(ts_index* ix, const MfmaPlan& p, size_t i, int nq, int k, float* out_scores, int64_t* out_idx, const void* qmat,
+                      hipStream_t st) {
+    const Level& lv = p.lv[i];
+    const bool full_pass = (i + 1 == p.lv.size());
+    MfmaArgs a;
+    a.corpus = (const unsigned short*)ix->rows;
+    a.n = ix->n;
+    a.ntiles = lv.ntiles;
+    a.tile_stride = lv.stride;
+    a.run = lv.run;
+    a.q = (const unsigned short*)qmat;
+    a.thr = ix->thr;
+    a.nq = ix->knobs.get(K_MFMA_NO_IDLE, 0) ? 256 : nq;
+    a.row_mask = ix->active_mask;
+    a.ahead = ix->knobs.get(K_MFMA_AHEAD, 0);
+    a.priv = ix->priv;
+    a.pcount = ix->pcount;
+    a.cand = ix->cand;
+    a.count = ix->count;
+    a.cap = kCandCap;
+    a.first_level = (i == 0) ? 1 : 0;      // thresholds and per-search counters are initialised inside the first launch of a search
+    a.nq_real = nq;
+    a.fb_count = ix->fb_count;
+    a.part = (p.balance && full_pass) ? ix->part : nullptr;
+    a.wg_ticks = (p.balance && full_pass) ? ix->wg_ticks : nullptr;
+    a.pair = (p.pair && full_pass) ? (p.ksplit_form ? 2 : 1) : 0;      // 2: the k-split form (TS_MFMA_PAIR=1: two blocks per wave over the whole row)
+    const bool paced = a.pair && p.pair_lag > 0;
+    a.pair_pos = paced ? ix->pair_pos : nullptr;
+    a.pair_lag = paced ? p.pair_lag : 0;
+    a.dbg = nullptr;
+    a.scr_tile = nullptr;
+    a.scr_q = nullptr;
+#ifdef TS_DIAG
+    if (p.variant >= 3) a.dbg = ix->dbg;
+#endif
+    hipEvent_t stop = full_pass ? prof_begin(ix, st, ix->n) : nullptr;  // only the full pass is bracketed
+    int rc;
+    if (p.screen && full_pass) rc = screen_full_pass(ix, p.nb16, nq, p.grid, p.screen_diag ? p.variant : 0, p.ksplit_form, st, a);
+    else if (ix->dtype == TS_F32 && p.shape16) rc = launch_pass_mfma16_f32(ix->device, ix->d, p.nb16, full_pass, p.grid, st, a);
+    else if (ix->dtype == TS_F32) rc = launch_pass_mfma32_f32(ix->device, full_pass, p.variant, p.grid, st, a);
+    else if (p.shape16) rc = launch_pass_mfma16(ix->device, ix->d, p.nb16, full_pass, p.variant, p.grid, st, a);
+    else rc = launch_pass_mfma32(ix->device, ix->d, p.groups, full_pass, p.variant, p.grid, st, a);
+    prof_end(stop, st);
+    TS_TRY(rc);
+#ifdef TS_DIAG
+    if (a.dbg && full_pass) TS_TRY(mfma_diag_readout(ix, p, a.dbg, st));
+#endif
+    LevelArgs l;
+    memset(&l, 0, sizeof(l));
+    l.priv = ix->priv;
+    l.pcount = ix->pcount;
+    l.nwriters = (p.shape16 && full_pass) ? 0 : p.nwriters;   // the 16x16 full pass stages its candidates in LDS: shared lists only
+    l.priv_cap = p.priv_cap;
+    l.cand = ix->cand;
+    l.count = ix->count;
+    l.cap = kCandCap;
+    l.kk = p.kk;
+    l.thr = ix->thr;
+    l.final_level = full_pass;
+    l.z_tail = full_pass ? 0.0f : p.z_tail;
+    l.tail_p = full_pass ? 0.0f : p.tail_p;
+    l.tail_z = (float)normal_tail_z(std::min(0.25, 32.0 / p.sample_rows));
+    // fewer candidates back than there are answers = the threshold was too high (an estimate that overshot, or a sample
+    // score that differs from the pass's in the last bit): exact re-run
+    l.min_fill = (int)std::min<int64_t>(k, p.pop);
+    l.out_scores = out_scores;
+    l.out_idx = out_idx;
+    l.k_user = k;
+    l.row_offset = ix->row_offset;
+    l.id_map = ix->id_map;
+    l.fb_list = ix->fb_list;
+    l.fb_count = ix->fb_count;
+    l.stat_q = ix->stat;
+    l.nq = nq;
+    if (p.kk <= 64) return launch_lds<level_select_kernel<1>>(ix->device, nq, kLevelThreads, kLevelLds, st, l);
+    return launch_lds<level_select_kernel<4>>(ix->device, nq, kLevelThreads, kLevelLds, st, l);
+}
+
+// `qmat`: the queries as the kernels multiply them (storage dtype, row stride d = ld, a whole launch's worth of rows):
+// the prepared copy, or the caller's own device matrix when it already has that form (`in_place`).
+int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx, hipStream_t st, ts_search_stats* stats,
+                       const void* qmat, bool in_place) {
+    const MfmaPlan p = mfma_plan(ix, nq, k);
+    TS_TRY(mfma_scratch(ix, p, st));
+    if (p.screen) TS_TRY(screen_prepare(ix, qmat, p.nq_launch, !p.dense0, st));
+    for (size_t i = 0; i < p.lv.size(); ++i) {
+        if (i == 0 && p.dense0) TS_TRY(mfma_sample(ix, p, nq, qmat, st));
+        else TS_TRY(mfma_level(ix, p, i, nq, k, out_scores, out_idx, qmat, st));
     }
     // the pass just finished left its workgroups' times: the next search's sample launch moves the tile boundaries (without
     // a dense sample: block 0 of the re-run launch below)
-    ix->rebalance_pending = balance;
-    ix->rebalance_grid = wgs;
-    ix->rebalance_in_rerun = !(dense_sample && lv.size() == 2);
+    ix->rebalance_pending = p.balance;
+    ix->rebalance_grid = p.wgs;
+    ix->rebalance_in_rerun = !(p.dense_sample && p.lv.size() == 2);
     // exact fall-back for queries that lost candidates (device-side count; one empty launch when 0)
     if (!in_place) TS_TRY(scan_search(ix, nq, k, out_scores, out_idx, ix->fb_list, ix->fb_count, st));
     else if (ix->dtype == TS_F32) TS_TRY(scan_search(ix, nq, k, out_scores, out_idx, ix->fb_list, ix->fb_count, st, (const float*)qmat));
     else TS_TRY(scan_search(ix, nq, k, out_scores, out_idx, ix->fb_list, ix->fb_count, st, nullptr, (const unsigned short*)qmat));
     if (stats) {
-        stats->levels = (int)lv.size();
-        stats->screened = screen ? 1 : 0;
+        stats->levels = (int)p.lv.size();
+        stats->screened = p.screen ? 1 : 0;
     }
     return TS_OK;
 }
