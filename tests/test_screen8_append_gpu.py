@@ -1,4 +1,4 @@
-"""The int8 screen's admitted-pair path (mfma8_append_block in kernels_mfma16.h: a wave-private LDS list filled at a
+"""The int8 screen's admitted-pair path (mfma8_append_block in kernels_screen8_tile.h: a wave-private LDS list filled at a
 wave-uniform count + the lane's rank among the passing lanes, an exact slow path when the list is full, a checked form for the
 corpus's last tile and for masked searches) under load it never sees on Gaussian rows: tiles in which hundreds of (row, query)
 pairs pass at once.  Every case compares TS_MFMA_SCREEN=1 with TS_MFMA_SCREEN=0 on one index: identical ids, identical score bits.

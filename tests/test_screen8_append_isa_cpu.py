@@ -1,7 +1,7 @@
 """The int8 screen's admitted-pair path in the compiled gfx950 ISA (launch_screen8.hip, NB = 4, the unmasked product kernel):
 a wave that stages (row, query) pairs waits for nothing.  Its list is wave-private, the fill count is a scalar register that
 lives through the tile loop, an entry's place is that count plus the lane's rank in the mask of passing lanes
-(mfma8_append_block in kernels_mfma16.h).  So inside the tile loop - every instruction that can be reached from the first
+(mfma8_append_block in kernels_screen8_tile.h).  So inside the tile loop - every instruction that can be reached from the first
 barrier and can still reach a barrier, the append blocks included wherever hipcc has placed them - there is no LDS atomic, no
 load of a kernel argument (the tile-scalar s_load_dwordx4 is the only scalar load) and no vector load from global memory.  The
 row mask is read by the masked form of the kernel only (VARIANT 14): one scalar load of the tile's mask word, no vector load

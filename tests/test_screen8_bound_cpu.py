@@ -1,4 +1,4 @@
-"""A numpy mirror of the int8 screen's quantiser and integer threshold (kernels_screen8.h, screen_int_thr in kernels_mfma16.h):
+"""A numpy mirror of the int8 screen's quantiser and integer threshold (kernels_screen8.h; screen_fold_query / screen_thr_piece in kernels_screen8_tile.h):
 no pair whose exact score reaches the threshold is screened out, on Gaussian and adversarial rows, with the fp32 steps of the
 threshold computed in fp32 as the kernel computes them."""
 import numpy as np
@@ -46,7 +46,7 @@ def quantize_queries(q):
 
 
 def int_thr(tx, ty, tz, thr, athr, rq, eq, qn):
-    """screen_int_thr in fp32: [tiles] x [queries]."""
+    """screen_fold_query + screen_thr_piece in fp32: [tiles] x [queries]."""
     with np.errstate(invalid="ignore", over="ignore"):
         sub = (ty[:, None] * qn[None, :] + tz[:, None] * eq[None, :]).astype(np.float32)
         mag = (athr[None, :] + sub).astype(np.float32)

@@ -1,4 +1,4 @@
-"""A numpy mirror of the int8 screen's folded threshold order (screen_fold_query / screen_thr_piece, kernels_mfma16.h): the
+"""A numpy mirror of the int8 screen's folded threshold order (screen_fold_query / screen_thr_piece, kernels_screen8_tile.h): the
 query's side q1, q2, q3 in fp64 rounded to fp32 on the admitting side, then per (tile, query) three fp32 FMAs, the clamp and
 floor.  Against the formula it replaced (the fp32 chain of tests/test_screen8_bound_cpu.py): no pair whose exact score reaches
 the threshold is screened out, no finite threshold drops by more than one unit, and the admitted pairs rise by at most 1 %."""

@@ -1,5 +1,5 @@
 """The int8 screen's tile tail in the compiled gfx950 ISA (launch_screen8.hip, NB = 4): the tile thresholds are computed among
-the tile's MFMAs (screen_thr_piece, TS16_THR8 in kernels_mfma16.h), so between the last i8 MFMA of a steady tile and the load of
+the tile's MFMAs (screen_thr_piece in kernels_screen8_tile.h, TS16_THR8 in kernels_mfma16.h), so between the last i8 MFMA of a steady tile and the load of
 the scalars two tiles ahead there is only the ring's drain, the block test and a little scalar bookkeeping."""
 import re
 

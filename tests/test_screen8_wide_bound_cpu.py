@@ -1,5 +1,5 @@
 """A numpy mirror of the int8 screen at d = 1024 (kernels_screen8.h with W = 1024; screen_fold_query / screen_thr_piece in
-kernels_mfma16.h): the quantisers with gamma = 1024 * 2^-22, the query's side folded in fp64 and rounded to fp32 on the
+kernels_screen8_tile.h): the quantisers with gamma = 1024 * 2^-22, the query's side folded in fp64 and rounded to fp32 on the
 admitting side, three fp32 FMAs per (tile, query), the clamp and floor.  The fp32 score of the unscreened pass is emulated in
 both of its summation orders - one chain of 32 k-steps, and the k-split's two chains of 16 k-steps added once - each in two
 models of a k-step (its 32 exact products added in fp64 and rounded once into the accumulator; every product added in fp32,

@@ -321,8 +321,6 @@ static inline bool use_shape16(const ts_index* ix) {
     return ix->dtype == TS_BF16 && mfma_dim(ix->d) && ix->knobs.get(K_MFMA_SHAPE, 16) != 32;
 }
 
-// fp32 index: mfma16_topk_kernel<D, NB, ., ., F32 = true>.  d = 1024: one block of 16 queries per wave, 64 per launch;
-
 // ---------------------------------------------------------------------------------------------
 // functions one translation unit defines for the others
 // ---------------------------------------------------------------------------------------------

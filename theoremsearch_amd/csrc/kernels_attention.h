@@ -18,7 +18,7 @@
 //   * O^T leaves the accumulators as [d = 4 (l >> 4) + r][q = l & 15]: four consecutive d per lane, staged through the same LDS and
 //     written as whole 128-byte rows.
 #pragma once
-#include "kernels_mfma16.h"
+#include "kernels_mfma16_ops.h"
 
 namespace ts {
 

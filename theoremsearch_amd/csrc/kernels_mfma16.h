@@ -33,13 +33,11 @@
 #pragma once
 #include <type_traits>
 
-#include "kernels_mfma.h"
+#include "kernels_mfma16_ops.h"
+#include "kernels_screen8_tile.h"
+#include "mfma16_variants.h"
 
 namespace ts {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-// a corpus fragment in flight (one ds_read_b128): four dwords, so that copies of it are four plain register moves
-typedef __attribute__((ext_vector_type(4))) unsigned frag16;
 
 constexpr int kMfma16PrivCap = 16;   // entries of a lane-private candidate list (4 * gridDim.x writers per query)
 // Full pass: candidates are staged in LDS (16 bytes each: key, query) and written to the queries' shared lists when the
@@ -53,111 +51,6 @@ constexpr int kMfma16StageBytes = 4 * kMfma16StageCap * 16 + 16;     // + one co
 // paired full pass: 64 dwords behind the staged candidates, where the partner workgroup's position lands (one LDS-DMA dword
 // per lane of wave 0, all from the same address)
 constexpr int kMfma16PaceBytes = 256;
-// int8 screen (I8, kernels_screen8.h): the same LDS bytes hold 8-byte entries (row, query), twice as many per wave - a screened
-// wave expects ~125 of them against ~40 exact candidates of the bf16 pass
-constexpr int kScreenStageCap = 2 * kMfma16StageCap;
-constexpr int kScreenListCap = 65536;   // entries of a query's global list of screened rows (kScreenCap, kernels_screen8.h)
-
-// MFMA statements with pinned register classes: accumulator and corpus fragment in VGPRs, query fragment in a VGPR
-// ("v" forms) or an AGPR ("a" forms) quadruple.  No pads inside: the A fragment comes from a ds_read behind the k-step's
-// explicit lgkmcnt wait (lds_read16 below), the query fragments are written once before the loop, accumulators chain
-// MFMA -> MFMA; the only non-MFMA reader of an accumulator is the epilogue, behind mfma16_settle().
-__device__ __forceinline__ void mfma16_v_first(f32x4& acc, const frag16& a, const bf16x8& b) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void mfma16_v(f32x4& acc, const frag16& a, const bf16x8& b) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void mfma16_a_first(f32x4& acc, const frag16& a, const bf16x8& b) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "a"(b));
-}
-__device__ __forceinline__ void mfma16_a(f32x4& acc, const frag16& a, const bf16x8& b) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "a"(b));
-}
-// int8 screen (I8): v_mfma_i32_16x16x64_i8, 64 bytes of K per 16-byte operand; the accumulator registers hold i32 bits
-__device__ __forceinline__ void mfma8_v_first(f32x4& acc, const frag16& a, const bf16x8& b) {
-    asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void mfma8_v(f32x4& acc, const frag16& a, const bf16x8& b) {
-    asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void mfma8_a_first(f32x4& acc, const frag16& a, const bf16x8& b) {
-    asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "a"(b));
-}
-__device__ __forceinline__ void mfma8_a(f32x4& acc, const frag16& a, const bf16x8& b) {
-    asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "a"(b));
-}
-// fp32 rows (F32): v_mfma_f32_16x16x4_f32, one float of the corpus chunk x one float of the query chunk per instruction
-__device__ __forceinline__ void mfma16f_v_first(f32x4& acc, float a, float b) {
-    asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void mfma16f_v(f32x4& acc, float a, float b) {
-    asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void mfma16f_a(f32x4& acc, float a, float b) {
-    asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "a"(b));
-}
-__device__ __forceinline__ void mfma16f_a_first(f32x4& acc, float a, float b) {
-    asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "a"(b));
-}
-// A-fragment read with a fixed place in the instruction stream (asm volatile statements keep their order among themselves):
-// the compiler does not know the result is asynchronous - every consumer sits behind an explicit s_waitcnt lgkmcnt below.
-template <int OFF>
-__device__ __forceinline__ void lds_read16(frag16& dst, unsigned addr) {
-    static_assert(OFF >= 0 && OFF < 65536, "ds_read offset field");
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
-// LDS-DMA piece with a wave-uniform base in SGPRs, a 32-bit per-lane offset and an immediate: no vector arithmetic per
-// piece.  The immediate is added to the global AND to the LDS address (LDS address = M0 + immediate + 16 * lane), so the
-// caller passes lds_dst - IMM.
-#ifndef TS16_DMA_IMM_LDS
-#define TS16_DMA_IMM_LDS 1
-#endif
-template <int IMM, bool NT = true>
-__device__ __forceinline__ void lds_dma16s(unsigned voff, const void* sbase, unsigned lds_dst) {
-    static_assert(IMM >= 0 && IMM < 4096, "13-bit signed immediate");
-    if constexpr (NT)
-        asm volatile(
-            "s_mov_b32 m0, %2\n\t"
-            "s_nop 0\n\t"
-            "global_load_lds_dwordx4 %0, %1 offset:%3" TS_DMA_POLICY
-            :
-            : "v"(voff), "s"(sbase), "s"(lds_dst), "n"(IMM)
-            : "memory");
-    else
-        asm volatile(
-            "s_mov_b32 m0, %2\n\t"
-            "s_nop 0\n\t"
-            "global_load_lds_dwordx4 %0, %1 offset:%3"
-            :
-            : "v"(voff), "s"(sbase), "s"(lds_dst), "n"(IMM)
-            : "memory");
-}
-// Every outstanding fragment read has landed; names the whole ring, so that no copy of a ring register the compiler may
-// need where control flow merges (end of a tile, steady / general branch) is placed above it.
-template <int N>
-__device__ __forceinline__ void lds_ring_landed(frag16 (&af)[N]) {
-    static_assert(N == 6 || N == 8, "ring of 3 or 4 k-steps, two row blocks");
-    if constexpr (N == 6)
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(af[0]), "+v"(af[1]), "+v"(af[2]), "+v"(af[3]), "+v"(af[4]), "+v"(af[5]));
-    else
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(af[0]), "+v"(af[1]), "+v"(af[2]), "+v"(af[3]), "+v"(af[4]), "+v"(af[5]),
-                     "+v"(af[6]), "+v"(af[7]));
-}
-// wait states between the last MFMA writing an accumulator and its first VALU reader (hipcc pads nothing for asm)
-template <int NB>
-__device__ __forceinline__ void mfma16_settle(f32x4 (&acc)[2][NB]) {
-    if constexpr (NB == 4)
-        asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[0][2]), "+v"(acc[0][3]), "+v"(acc[1][0]),
-                     "+v"(acc[1][1]), "+v"(acc[1][2]), "+v"(acc[1][3]));
-    else if constexpr (NB == 3)
-        asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[0][2]), "+v"(acc[1][0]), "+v"(acc[1][1]),
-                     "+v"(acc[1][2]));
-    else if constexpr (NB == 2)
-        asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[1][0]), "+v"(acc[1][1]));
-    else
-        asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc[0][0]), "+v"(acc[1][0]));
-}
 
 // Threshold test of one query block: the lane's 8 scores (4 rows of each row block) against the block's threshold,
 // in 5 instructions with a fixed order (asm volatile statements keep their order among themselves and the MFMAs).
@@ -191,101 +84,6 @@ __device__ __forceinline__ void ksplit_test_b(float& m, const f32x4& a1) {
 }
 __device__ __forceinline__ void ksplit_test_c(u64& mask, float m, float thr) {
     asm volatile("v_cmp_ge_f32 %0, %1, %2" : "=s"(mask) : "v"(m), "v"(thr));
-}
-
-// The same test on the i32 dot products of the int8 screen against the block's integer threshold of the tile.
-__device__ __forceinline__ u64 mfma8_block_test(const f32x4& a0, const f32x4& a1, int thr, int& m) {
-    u64 mask;
-    asm volatile(
-        "v_max3_i32 %0, %2, %3, %4\n\t"
-        "v_max3_i32 %0, %0, %5, %6\n\t"
-        "v_max3_i32 %0, %0, %7, %8\n\t"
-        "v_max_i32 %0, %0, %9\n\t"
-        "v_cmp_ge_i32 %1, %0, %10"
-        : "=&v"(m), "=s"(mask)
-        : "v"(a0[0]), "v"(a0[1]), "v"(a0[2]), "v"(a0[3]), "v"(a1[0]), "v"(a1[1]), "v"(a1[2]), "v"(a1[3]), "v"(thr));
-    return mask;
-}
-
-// Integer thresholds of the int8 screen (kernels_screen8.h has the derivation and the rounding argument): every row of a tile
-// whose exact fp32 score can reach the query's `thr` has an int8 dot product >= the (tile, query) threshold.  The query's side
-// is folded once per launch: with rq = 1 / s_q, eq = |e_q|, qn = |q| (rq = NaN: the query holds a non-finite value) and
-// athr = |thr| (0 where thr is infinite),
-//   q1 = rq (thr - athr 2^-18),  q2 = rq qn (1 + 2^-18),  q3 = rq eq (1 + 2^-18)
-// in fp64, rounded to fp32 on the admitting side (q1 down, q2 and q3 up).
-__device__ __forceinline__ void screen_fold_query(float thr, float rq, float eq, float qn, float& q1, float& q2, float& q3) {
-    const double athr = __builtin_isinf(thr) ? 0.0 : fabs((double)thr);
-    const double v1 = (double)rq * ((double)thr - athr * 0x1p-18);
-    const double v2 = (double)rq * (double)qn * (1.0 + 0x1p-18);
-    const double v3 = (double)rq * (double)eq * (1.0 + 0x1p-18);
-    q1 = (float)v1;
-    q2 = (float)v2;
-    q3 = (float)v3;
-    if ((double)q1 > v1) q1 = nextafterf(q1, -__builtin_inff());      // (NaN compares false and stays NaN)
-    if ((double)q2 < v2) q2 = nextafterf(q2, __builtin_inff());
-    if ((double)q3 < v3) q3 = nextafterf(q3, __builtin_inff());
-}
-// fp64 -> fp32, never below the value (non-negative bounds that must not shrink)
-__device__ __forceinline__ float f32_up(double v) {
-    const float f = (float)v;
-    return (double)f >= v ? f : __uint_as_float(__float_as_uint(f) + 1u);
-}
-// The screen's image of one query, by one wave (kernels_screen8.h has the quantisation; kD = the screen's width, 768 or 1024):
-// row r of q [nrows x kD] bf16 -> row r of img [256 x kD] int8 and meta[r] = {1 / s_q (NaN: non-finite value), |e_q|, |q|, 0}; a zero row past nrows.  Also empties
-// the query's list of screened rows.  Needs nothing but the prepared queries, so it rides in whatever launch comes before the
-// screen: the extra workgroup row of the threshold sample (kernels_sample.h), or quantize_queries_kernel.
-template <int kD>
-__device__ __forceinline__ void screen_quantize_query(const unsigned short* __restrict__ q, int nrows, int r, int lane,
-                                                      signed char* __restrict__ img, float4* __restrict__ meta, u32* __restrict__ scount) {
-    static_assert(kD == 768 || kD == 1024, "widths the int8 screen serves");
-    float v[kD / 64];
-    float amax = 0.0f;
-    int bad = 0;
-#pragma unroll
-    for (int j = 0; j < kD / 64; ++j) {
-        v[j] = r < nrows ? bf16_to_f32(q[(int64_t)r * kD + lane + 64 * j]) : 0.0f;
-        if (!(fabsf(v[j]) <= 3.4028235e38f)) bad = 1;
-        else amax = fmaxf(amax, fabsf(v[j]));
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        amax = fmaxf(amax, __shfl_xor(amax, o));
-        bad |= __shfl_xor(bad, o);
-    }
-    const float s = amax > 0.0f ? amax / 127.0f : 1.0f;
-    double ee = 0.0, qq = 0.0;
-#pragma unroll
-    for (int j = 0; j < kD / 64; ++j) {
-        float qx = 0.0f;
-        if (fabsf(v[j]) <= 3.4028235e38f) qx = fminf(127.0f, fmaxf(-127.0f, rintf(v[j] / s)));
-        img[(int64_t)r * kD + lane + 64 * j] = (signed char)(int)qx;
-        const double e = (double)v[j] - (double)s * (double)qx;
-        ee += e * e;
-        qq += (double)v[j] * (double)v[j];
-    }
-    ee = wave_sum_f64(ee);
-    qq = wave_sum_f64(qq);
-    if (lane == 0) {
-        meta[r] = make_float4(bad ? __builtin_nanf("") : 1.0f / s, f32_up(sqrt(ee) * (1.0 + 0x1p-40)), f32_up(sqrt(qq) * (1.0 + 0x1p-40)), 0.0f);
-        scount[r] = 0;
-    }
-}
-
-// The threshold of (tile, query) from the tile's scalars tm = (tx = 1 / s_t, ty = coefficient of |q|, tz = coefficient of
-// |e_q|; tx = NaN: the tile holds a non-finite value): floor(clamp(fma(tx, fma(-tz, q3, fma(-ty, q2, q1)), -1))), in four
-// pieces of at most two VALU instructions with fixed places between the MFMAs of the tile (TS16_THR8): none of it reads an
-// accumulator.  The clamp is v_max / v_min (maxNum: a NaN yields the other operand, so NaN -> INT_MIN: every row of the tile is
-// a candidate, the exact rescore decides); the literals are -2^31 and 2^30.
-template <int P>
-__device__ __forceinline__ void screen_thr_piece(int& t, const f32x4& tm, float q1, float q2, float q3) {
-    static_assert(P >= 0 && P < 4, "four pieces");
-    if constexpr (P == 0)
-        asm volatile("v_fma_f32 %0, -%1, %2, %3\n\tv_fma_f32 %0, -%4, %5, %0" : "=&v"(t) : "s"(tm[1]), "v"(q2), "v"(q1), "s"(tm[2]), "v"(q3));
-    else if constexpr (P == 1)
-        asm volatile("v_fma_f32 %0, %1, %0, -1.0\n\tv_max_f32 %0, 0xcf000000, %0" : "+v"(t) : "s"(tm[0]));
-    else if constexpr (P == 2)
-        asm volatile("v_min_f32 %0, 0x4e800000, %0\n\tv_floor_f32 %0, %0" : "+v"(t));
-    else
-        asm volatile("v_cvt_i32_f32 %0, %0" : "+v"(t));
 }
 
 // Append the passing scores of one query block (rare path: entered for a block only when some lane passed).  Written
@@ -327,60 +125,6 @@ __device__ __forceinline__ void mfma16_append_block(const f32x4& a0, const f32x4
     }
 }
 
-// The int8 screen's form of the rare path: (row, query) pairs whose dot product reaches the tile's integer threshold, staged as
-// 8-byte entries (row, query) in the wave's own LDS list; the exact score is the rescore's business.  The screen admits eight
-// times the pairs of the bf16 pass, and a wave on this path holds up the other three at the next barrier, so it waits for
-// nothing: the list belongs to one wave, hence an entry's place is a wave-uniform fill count (`scnt`, an SGPR that lives through
-// the whole tile loop; no LDS counter, no atomic) plus the lane's rank among the passing lanes.  Per accumulator value: one
-// compare into a lane mask, a scalar branch over the (usual) empty mask, v_mbcnt, one ds_write_b64, scnt += popcount.  The
-// ds_write stays in flight - nobody reads the list before the flush behind the tile loop - and an LDS operation in flight only
-// makes the fragment ring's counted lgkmcnt waits stricter, never looser (LDS returns in order: "at most N outstanding" then
-// certifies the ring's reads and this write), the argument the tile-scalar load already relies on.
-// CHECKED: the tile may hold rows >= n (the corpus's last tile) or the search has a row mask (tested before an entry is
-// staged: masked-off rows would fill the list up to ten times faster); everything else takes the unchecked form.  A tile is one
-// word of the row mask, so the caller reads it once per tile with a SCALAR load (no vector-memory operation: the DMA ring's
-// vmcnt queue is left alone), clears the bits of rows >= n and hands every lane its eight bits: `live` bit (g & 3) + 16 (g >> 2)
-// = row g of this lane.  A value is looked up there only once some lane's score has passed.
-// Padding queries (qid >= nq_real) have threshold 2^30 except in a tile with a non-finite value (INT_MIN): no dot product of
-// 768 or 1,024 int8 pairs reaches INT_MAX, which is what they are compared with here.
-// A full list sends the wave's further pairs straight to the queries' global lists (vector memory: the DMA ring's counted
-// waits see two operations more and wait longer - slow, rare, exact).
-// (The pointers are spelled as global-memory pointers: they come out of pinned SGPRs, where hipcc no longer sees that they were
-// kernel arguments and would fall back to flat instructions, which count in both wait queues.)
-typedef __attribute__((address_space(1))) u32* screen_u32_gptr;
-typedef __attribute__((address_space(1))) u64* screen_u64_gptr;
-typedef const __attribute__((address_space(4))) u32* screen_mask_cptr;   // (constant address space: a scalar load)
-template <bool CHECKED>
-__device__ __forceinline__ void mfma8_append_block(const f32x4& a0, const f32x4& a1, int thr, int qid, u32 row_base, u32& scnt,
-                                                   uint2* stage, u32 live, u32 nq_real, screen_u32_gptr count, screen_u64_gptr cand) {
-    const int thr_q = (u32)qid < nq_real ? thr : 0x7fffffff;
-#pragma unroll
-    for (int g = 0; g < 8; ++g) {
-        const int s = __builtin_bit_cast(int, (g < 4) ? a0[g & 3] : a1[g & 3]);
-        const u32 row = row_base + (g & 3) + 16 * (g >> 2);
-        bool pass = s >= thr_q;
-        if constexpr (CHECKED) {
-            if (__builtin_amdgcn_ballot_w64(pass) == 0) continue;
-            pass = pass && ((live >> ((g & 3) + 16 * (g >> 2))) & 1u) != 0;
-        }
-        const u64 m = __builtin_amdgcn_ballot_w64(pass);
-        if (m == 0) continue;
-        const u32 at = scnt + __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u));
-        const u32 np = (u32)__builtin_popcountll(m);
-        if (__builtin_expect(scnt + np <= (u32)kScreenStageCap, 1)) {
-            if (pass) stage[at] = make_uint2(row, (u32)qid);
-        } else if (pass) {
-            if (at < (u32)kScreenStageCap) {
-                stage[at] = make_uint2(row, (u32)qid);
-            } else {                                                           // list full: straight to the query's list
-                const u32 pos = __hip_atomic_fetch_add(&count[qid], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (pos < (u32)kScreenListCap) cand[(int64_t)qid * kScreenListCap + pos] = (u64)row;
-            }
-        }
-        scnt += np;
-    }
-}
-
 // Pacing of a workgroup pair (PAIR).  Both halves of a pair stream the same tiles; the second reader of a tile is served by
 // the XCD's L2 only while the two stay within what that L2 holds of the stream - 4 MB turn over in ~7 us at 535 GB/s per XCD,
 // about 15 units of 16 KB per pair.  Left alone they drift (an append, a slow barrier) and a pair that is further apart reads
@@ -409,19 +153,82 @@ __device__ __forceinline__ void pair_read_word(unsigned& dst, unsigned lds_word)
     asm volatile("ds_read_b32 %0, %1" : "=v"(dst) : "v"(lds_word));
 }
 
+// k-split, end of a tile: this wave's sums of blocks 2, 3 into its part of the exchange buffer ([4][lane] x 16 bytes), where
+// wave ^ 2 fetches them behind the third unit barrier of the next tile.
+template <int NB>
+__device__ __forceinline__ void ksplit_hand_over(f32x4 (&acc)[2][NB], uint4* mine) {
+    asm volatile("" : "+v"(acc[0][2]), "+v"(acc[0][3]), "+v"(acc[1][2]), "+v"(acc[1][3]));
+    mine[0] = *reinterpret_cast<const uint4*>(&acc[0][2]); mine[64] = *reinterpret_cast<const uint4*>(&acc[0][3]);
+    mine[128] = *reinterpret_cast<const uint4*>(&acc[1][2]); mine[192] = *reinterpret_cast<const uint4*>(&acc[1][3]);
+}
+
+// The tail of a tile of the bf16 / fp32 pass (behind the ring's drain and the accumulators' wait states): the block tests against
+// the queries' thresholds and the append path of the blocks that passed.
+// (the scalars come by reference, so that they are read where the rare path uses them, as the code did inside the tile loop)
+template <int NB, int VARIANT, bool STAGED>
+__device__ __forceinline__ void mfma16_tile_tail(const f32x4 (&acc)[2][NB], const float (&thr)[NB], const int (&qid)[NB], u32 (&cnt)[NB], const int64_t& t0,
+                                                 const int& t, const int& kq, const int& writer, const int& nwriters, const MfmaArgs& a, uint4* const& stage,
+                                                 u32* const& stage_cnt) {
+    // lane holds rows 4 kq + {0..3} of both row blocks for query qid[b]
+    float best[NB];
+    u64 hit[NB], any_hit = 0;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        hit[b] = mfma16_block_test(acc[0][b], acc[1][b], thr[b], best[b]);
+        any_hit |= hit[b];
+    }
+    if (variant_test_only(VARIANT)) {         // diagnostic: the test without the append path
+        asm volatile("" ::"s"(any_hit));
+        return;
+    }
+    if (__builtin_expect(any_hit != 0, 0)) {
+        const int64_t lt = t0 + t;
+        // (64-bit divisions are hundreds of instructions: runs of one tile - the default - take the short way)
+        const int64_t tile_row = (a.run == 1 ? lt * a.tile_stride : (lt / a.run) * a.run * a.tile_stride + lt % a.run) * kTileRows;
+        const int64_t row_base = tile_row + 4 * kq;
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+            if (hit[b] != 0)
+                mfma16_append_block<STAGED>(acc[0][b], acc[1][b], thr[b], best[b], qid[b], writer, nwriters, cnt[b], row_base, a,
+                                             stage, stage_cnt);
+    }
+}
+
+// What the kernel does behind its tile loop.
+// The staged candidates of a wave -> the queries' shared lists: the tile loop is over (no DMA in flight that a counted wait
+// still watches).
+__device__ __forceinline__ void mfma16_flush_stage(const MfmaArgs& a, const uint4* stage, const u32* stage_cnt, int lane) {
+    const u32 n = min(*stage_cnt, (u32)kMfma16StageCap);
+    for (u32 e = lane; e < n; e += 64) {
+        const uint4 v = stage[e];
+        const u32 pos = atomicAdd(&a.count[v.z], 1u);
+        if (pos < (u32)a.cap) a.cand[(int64_t)v.z * a.cap + pos] = ((u64)v.y << 32) | v.x;
+    }
+}
+// The stamped forms' read-out: one wave's cycle sums (d = this wave's four words of MfmaArgs::dbg; `last` = the DMA issue, or
+// the tile tails of the screen).
+__device__ __forceinline__ void mfma16_write_stamps(unsigned long long* d, unsigned long long t_all0, unsigned long long t_vm,
+                                                    unsigned long long t_bar, unsigned long long last) {
+    d[0] = cycle_stamp() - t_all0;
+    d[1] = t_vm;
+    d[2] = t_bar;
+    d[3] = last;
+}
+// The clock probe's read-out: shader cycles, 100 MHz ticks and units of the workgroup's tile loop (four words of MfmaArgs::dbg per
+// workgroup; their address is computed behind the two clock reads).
+__device__ __forceinline__ void mfma16_write_probe(unsigned long long* dbg, unsigned long long c_begin, unsigned long long r_begin, int nu) {
+    const unsigned long long c_end = __builtin_amdgcn_s_memtime();
+    const unsigned long long r_end = __builtin_amdgcn_s_memrealtime();
+    unsigned long long* d = dbg + (size_t)blockIdx.x * 4;
+    d[0] = c_end - c_begin;
+    d[1] = r_end - r_begin;
+    d[2] = (unsigned long long)nu;
+    d[3] = 0;
+}
+
 // NB = query blocks (of 16) per wave: the launch serves 64 * NB queries.
-// VARIANT 0 = the product kernel.  Timing-only diagnostics (wrong results): 1 = no epilogue, 2 = DMA stream only,
-// 7 = no DMA (MFMA + LDS reads), 4 = threshold test without the append path, 5 = product + per-unit cycle stamps around
-// the vmcnt wait, the barrier and each DMA issue (sums per wave into a.dbg; the stamps drain the LDS queue: read the
-// SHARES, not the length).  3 = product + clock probe: s_memtime / s_memrealtime around the tile loop into a.dbg
-// (4 words per workgroup: shader cycles, 100 MHz ticks, units, 0) - MI355X_MICROARCH.md "DVFS give-back" item 6.
-// 6 = product + s_sleep of ~256 cycles per unit (how much of an added idle cycle shows up as time under the power cap).
-// 8 = the int8 screen (below, I8).  Its timing-only forms (the diagnostic build, I8 as well): 9 = no epilogue, 10 = cycle
-// stamps around the vmcnt wait, the barrier and the tile tail (the drain to the end of the epilogue; a.dbg as 5, the tail in
-// place of the DMA issue), 11 = clock probe (as 3), 12 = DMA stream only, 13 = the block test without the append path and the
-// flush (the screen's form of 4: product - 13 = what the admitted pairs cost inside the launch, 13 - 9 = the fall-through tail).
-// 14 = the screen of a search with a row mask (a product kernel): 8 holds no code that reads MfmaArgs::row_mask; 14 and the
-// product-with-instruments forms 10, 11 test the mask (when there is one) before a pair is staged.
+// VARIANT: the product kernel, one of its timing-only diagnostics, or a form of the int8 screen - mfma16_variants.h names and
+// describes each value.
 // SPARSE only changes the symbol (sample levels show up under their own name in kernel traces).
 //
 // F32: the same kernel over an fp32 index (exact fp32: v_mfma_f32_16x16x4_f32, bit for bit an fmaf chain).  A row of D
@@ -448,7 +255,7 @@ __device__ __forceinline__ void pair_read_word(unsigned& dst, unsigned lds_word)
 // two masks.  So a tile's candidates are appended one tile late, the last tile's after the loop (one more barrier).
 // Registers: 24 query fragments in VGPRs, 40 in AGPRs.  (With 32 in VGPRs hipcc parked two in AGPRs and copied them back one
 // instruction ahead of their MFMA - asm text, no hazard padding: wrong k-steps.  tools/audit_ring.py reports that pattern.)
-// VARIANT 8 (I8): the int8 screen of the d = 768 / 1024 bf16 full pass (kernels_screen8.h).  A row of 768 int8 values has the bytes of a
+// kVariantScreen .. kVariantScreenMasked (I8): the int8 screen of the d = 768 / 1024 bf16 full pass (kernels_screen8.h).  A row of 768 int8 values has the bytes of a
 // d = 384 bf16 row, one of 1,024 those of a d = 512 row, so it runs as D = 384 or D = 512 - the same ring, swizzle, fragment reads and query fragments (bytes 64 ks + 16 kq of the row
 // at both operands: whatever k order the i8 instruction gives the bytes of a lane, both operands share it and the integer dot
 // product is exact) - with the i8 MFMA, an integer threshold per (tile, query) from the tile's scalars and (row, query) pairs
@@ -456,17 +263,17 @@ __device__ __forceinline__ void pair_read_word(unsigned& dst, unsigned lds_word)
 template <int D, int NB, int VARIANT, bool SPARSE, bool F32 = false, bool PAIR = false, bool KSPLIT = false>
 __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a) {
     static_assert(!PAIR || (!SPARSE && !F32), "pairs exist for the bf16 full pass");
-    constexpr bool I8 = VARIANT >= 8 && VARIANT <= 14;
-    constexpr bool kMasked8 = I8 && VARIANT != 8;           // the row mask is looked at (8: the unmasked product)
+    constexpr bool I8 = variant_is_screen(VARIANT);
+    constexpr bool kMasked8 = variant_masked(VARIANT);       // the row mask is looked at (kVariantScreen: the unmasked product)
     static_assert(!I8 || ((D == 384 || D == 512) && !SPARSE && !F32 && !PAIR), "the screen is the full pass over 768- or 1,024-byte int8 rows");
-    static_assert(!KSPLIT || (PAIR && NB == 4 && (VARIANT == 0 || VARIANT == 1 || VARIANT == 2 || VARIANT == 7) && D == 1024), "the k-split is the paired pass of d = 1024 with four query blocks per wave");
+    static_assert(!KSPLIT || (PAIR && NB == 4 && variant_ksplit_form(VARIANT) && D == 1024), "the k-split is the paired pass of d = 1024 with four query blocks per wave");
     constexpr int Deq = F32 ? 2 * D : D;                 // row length in 2-byte elements
     using dims = typename std::conditional<KSPLIT, MfmaDims<Deq, MfmaGeomKsplit<Deq>>, Mfma16Dims<Deq>>::type;
-    constexpr bool kNoEpi = VARIANT == 1 || VARIANT == 7 || VARIANT == 9;
-    constexpr bool kNoDma = VARIANT == 7;
-    constexpr bool kNoMma = VARIANT == 2 || VARIANT == 12;
-    constexpr bool kStamps = VARIANT == 5 || VARIANT == 10;   // cycle stamps (general units only)
-    constexpr bool kProbe = VARIANT == 3 || VARIANT == 11;    // clock probe
+    constexpr bool kNoEpi = variant_no_epilogue(VARIANT);
+    constexpr bool kNoDma = variant_no_dma(VARIANT);
+    constexpr bool kNoMma = variant_no_mma(VARIANT);
+    constexpr bool kStamps = variant_stamped(VARIANT);        // cycle stamps (general units only)
+    constexpr bool kProbe = variant_probe(VARIANT);           // clock probe
     constexpr int kStepsAll = Deq / 32;                  // k-steps (16-byte chunks per lane) per tile
     constexpr int kUnitStepsAll = dims::kUnitK / 32;     // k-steps per unit
     constexpr int kSteps = KSPLIT ? kStepsAll / 2 : kStepsAll;               // ... of them, this wave's
@@ -657,8 +464,8 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
 #pragma unroll
     for (int b = 0; b < NB; ++b) cnt[b] = 0;
     int slot = 0, u = 0;
-    unsigned long long t_vm = 0, t_bar = 0, t_dma = 0, t_all0 = 0;   // VARIANT 5: cycle sums of the waits / DMA issue
-    unsigned long long t_tail = 0;                                   // VARIANT 10: cycles of the tile tails
+    unsigned long long t_vm = 0, t_bar = 0, t_dma = 0, t_all0 = 0;   // kVariantStamps: cycle sums of the waits / DMA issue
+    unsigned long long t_tail = 0;                                   // kVariantScreenStamps: cycles of the tile tails
     if (kStamps) t_all0 = cycle_stamp();
     unsigned long long c_begin = 0, r_begin = 0;
     if (kProbe) {
@@ -713,10 +520,10 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
             if (do_issue) {                                                                                \
                 constexpr int j_ = (S_) / kPieceEvery;                                                     \
                 unsigned long long d0_ = 0;                                                                \
-                if (VARIANT == 5) d0_ = cycle_stamp();                                                     \
+                if (VARIANT == kVariantStamps) d0_ = cycle_stamp();                                        \
                 if constexpr (steady_) lds_dma16s<j_ * 128, kStreamNT>(dma_voff, ssrc, idst + j_ * (4096 - 128 * TS16_DMA_IMM_LDS)); \
                 else lds_dma16<kStreamNT>(isrc + j_ * 128, idst + j_ * 4096);                                         \
-                if (VARIANT == 5) t_dma += cycle_stamp() - d0_;                                            \
+                if (VARIANT == kVariantStamps) t_dma += cycle_stamp() - d0_;                               \
             }                                                                                              \
     } while (0)
     // k-split: the blocks that go to the partner (2, 3) first - at the end of a tile their sums are four MFMAs old when they are
@@ -864,7 +671,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
             if (pace) pair_publish_and_fetch(pace_mine, pace_partner, (unsigned)t, pace_word);            \
         }                                                                                                  \
         if constexpr (PAIR && (UI) == (1 % kUnits)) pair_read_word(pace_v, pace_word);                     \
-        if (VARIANT == 6) __builtin_amdgcn_s_sleep(4);                                                     \
+        if (VARIANT == kVariantSleep) __builtin_amdgcn_s_sleep(4);                                         \
         constexpr bool do_issue = !kNoDma;                                                                 \
         constexpr bool steady_ = true;                                                                     \
         const unsigned char* isrc = nullptr;                                                               \
@@ -893,7 +700,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
         asm volatile("" ::: "memory");                                                                     \
         if constexpr (KSPLIT && (UI) == 2) TS16_KSPLIT_FETCH();                                            \
         if (kStamps) { t_vm += s1_ - s0_; t_bar += cycle_stamp() - s1_; }                                  \
-        if (VARIANT == 6) __builtin_amdgcn_s_sleep(4);   /* ~256 idle cycles per unit: elasticity of time to cycles */ \
+        if (VARIANT == kVariantSleep) __builtin_amdgcn_s_sleep(4);   /* ~256 idle cycles per unit: elasticity of time to cycles */ \
         const bool do_issue = issue_u < nu && !kNoDma;                                                     \
         constexpr bool steady_ = false;                                                                    \
         const unsigned char* isrc = tile_src + issue_ui * (kUnitK * 2);                                    \
@@ -909,6 +716,8 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     } while (0)
 
     // k-split: the candidates of tile TP (one tile late), from the sums and masks the fillers of the next tile's last unit left
+    // (a macro, and the after-loop block that uses it inline: as functions they change the code of the k-split instantiation -
+    // profiles/HISTORY.md, round 11)
 #define TS16_KSPLIT_APPEND(TP)                                                                             \
     do {                                                                                                   \
         if (__builtin_expect((hit_[0] | hit_[1]) != 0, 0)) {                                               \
@@ -941,14 +750,9 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     // ahead: the load of tile t + 2 goes out at the end of tile t and is pinned behind the ring's drain at the end of tile t + 1,
     // where hipcc's own lgkmcnt(0) for it finds nothing left to wait for.  (Scalar loads join no vector-memory count of the ring;
     // in flight they make the ring's counted lgkmcnt waits stricter, never looser.)
-    // (through the constant address space: the kernel's own stores could alias a global pointer, and hipcc would make it a
-    // vector load - whose wait, vmcnt(0), drains the DMA ring at every tile)
-    // (one 16-byte load into one SGPR quadruple: loads of separate words get merged into pairs that the loop-carried registers
-    // do not line up with, and hipcc copies them - behind a wait for the load it has just issued)
-    typedef const __attribute__((address_space(4))) f32x4* tile_scalars_ptr;
+    // (tile_scalars_ptr / screen_tile_scalars, kernels_screen8_tile.h: why a constant-address-space pointer and one 16-byte load)
     const tile_scalars_ptr scr_tile = (tile_scalars_ptr)a.scr_tile;
     f32x4 tmc = {0.0f, 0.0f, 0.0f, 0.0f}, tmn = {0.0f, 0.0f, 0.0f, 0.0f};
-    auto tile_scalars = [&](f32x4& tm, int64_t lt) __attribute__((always_inline)) { tm = scr_tile[lt]; };
     // I8: this tile's integer thresholds, computed among its MFMAs (piece 0 writes them; no initialisation: a loop of one
     // trip here changes the code hipcc makes for the other instantiations)
     int ithr[I8 ? NB : 1];
@@ -961,8 +765,8 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     screen_u64_gptr s_cand = nullptr;
     screen_mask_cptr s_mask = nullptr;
     if constexpr (I8) {
-        tile_scalars(tmc, t0);
-        tile_scalars(tmn, t0 + (nt > 1 ? 1 : 0));
+        screen_tile_scalars(tmc, scr_tile, t0);
+        screen_tile_scalars(tmn, scr_tile, t0 + (nt > 1 ? 1 : 0));
         asm volatile("" : "+s"(tmc), "+s"(tmn));
         const int64_t whole = a.n / kTileRows - t0;      // this workgroup's tiles in front of the first one with padding rows
         t_chk = whole < (int64_t)nt ? (whole > 0 ? (int)whole : 0) : nt;
@@ -1017,7 +821,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
                 TS16_UNIT(6 % kUnits);
                 TS16_UNIT(7 % kUnits);
             }
-            if (VARIANT == 10) tail0 = cycle_stamp();
+            if (VARIANT == kVariantScreenStamps) tail0 = cycle_stamp();
             if constexpr (!kNoMma) lds_ring_landed(af);
         }
         if constexpr (kNoMma) return;
@@ -1029,10 +833,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
             }
             if (t > 0) TS16_KSPLIT_APPEND(t - 1);        // the previous tile, summed and tested by this tile's fillers
             // blocks 2, 3 go to the partner (their last MFMAs are four MFMAs back: TS16_BF16_ORDER); blocks 0, 1 are kept
-            asm volatile("" : "+v"(acc[0][2]), "+v"(acc[0][3]), "+v"(acc[1][2]), "+v"(acc[1][3]));
-            uint4* mine = xbuf + wave * 256 + lane;
-            mine[0] = *reinterpret_cast<const uint4*>(&acc[0][2]); mine[64] = *reinterpret_cast<const uint4*>(&acc[0][3]);
-            mine[128] = *reinterpret_cast<const uint4*>(&acc[1][2]); mine[192] = *reinterpret_cast<const uint4*>(&acc[1][3]);
+            ksplit_hand_over(acc, xbuf + wave * 256 + lane);
             return;
         }
         // The last k-step issued its MFMAs in block order, so with NB = 4 the results of block b are at least 6 MFMAs
@@ -1050,25 +851,17 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
         if constexpr (I8) {
             // tile t + 1's scalars: landed behind the drain above
             asm volatile("" : "+s"(tmn));
-            int ibest[NB];
-            u64 ihit[NB], iany = 0;
-#pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                ihit[b] = mfma8_block_test(acc[0][b], acc[1][b], ithr[b], ibest[b]);
-                iany |= ihit[b];
-            }
-            if constexpr (VARIANT == 13) {           // diagnostic: the test without the append path
+            u64 ihit[NB];
+            const u64 iany = screen_tile_test<NB>(acc, ithr, ihit);
+            if constexpr (variant_test_only(VARIANT)) {   // diagnostic: the test without the append path
                 asm volatile("" ::"s"(iany));
             } else if (__builtin_expect(iany != 0, 0)) {
+                // (the two loops over mfma8_append_block stay here: inside a function of their own - or of the whole tail - hipcc
+                // orders the general units of mfma16_topk_kernel<512, 2, kVariantScreen> differently: profiles/HISTORY.md, round 11)
                 const u32 row_base = ((u32)t0 + (u32)t) * kTileRows + 4 * kq;   // the screen runs over every tile (run 1, stride 1)
                 if (kMasked8 || t >= t_chk) {
                     // the tile's rows that may be returned: its word of the row mask (all of them without a mask), less rows >= n
-                    const u32 tile_row = ((u32)t0 + (u32)t) * kTileRows;
-                    u32 word = 0xffffffffu;
-                    if (tile_row >= s_n) word = 0u;
-                    else if (kMasked8 && s_mask != nullptr) word = s_mask[tile_row >> 5];
-                    if (tile_row < s_n && s_n - tile_row < (u32)kTileRows) word &= (1u << (s_n - tile_row)) - 1u;
-                    const u32 live = word >> (4 * kq);
+                    const u32 live = screen_tile_live<kMasked8>(((u32)t0 + (u32)t) * kTileRows, s_n, s_mask) >> (4 * kq);
 #pragma unroll
                     for (int b = 0; b < NB; ++b)
                         if (ihit[b] != 0)
@@ -1080,34 +873,12 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
                             mfma8_append_block<false>(acc[0][b], acc[1][b], ithr[b], qid[b], row_base, scnt, stage8, 0u, s_nq, s_count, s_cand);
                 }
             }
-            if (VARIANT == 10) t_tail += cycle_stamp() - tail0;
+            if (VARIANT == kVariantScreenStamps) t_tail += cycle_stamp() - tail0;
             tmc = tmn;
-            tile_scalars(tmn, t0 + (t + 2 < nt ? t + 2 : nt - 1));
+            screen_tile_scalars(tmn, scr_tile, t0 + (t + 2 < nt ? t + 2 : nt - 1));
             return;
         }
-        // lane holds rows 4 kq + {0..3} of both row blocks for query qid[b]
-        float best[NB];
-        u64 hit[NB], any_hit = 0;
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            hit[b] = mfma16_block_test(acc[0][b], acc[1][b], thr[b], best[b]);
-            any_hit |= hit[b];
-        }
-        if (VARIANT == 4) {                      // diagnostic: the test without the append path
-            asm volatile("" ::"s"(any_hit));
-            return;
-        }
-        if (__builtin_expect(any_hit != 0, 0)) {
-            const int64_t lt = t0 + t;
-            // (64-bit divisions are hundreds of instructions: runs of one tile - the default - take the short way)
-            const int64_t tile_row = (a.run == 1 ? lt * a.tile_stride : (lt / a.run) * a.run * a.tile_stride + lt % a.run) * kTileRows;
-            const int64_t row_base = tile_row + 4 * kq;
-#pragma unroll
-            for (int b = 0; b < NB; ++b)
-                if (hit[b] != 0)
-                    mfma16_append_block<kStaged>(acc[0][b], acc[1][b], thr[b], best[b], qid[b], writer, nwriters, cnt[b], row_base, a,
-                                                 stage, stage_cnt);
-        }
+        mfma16_tile_tail<NB, VARIANT, kStaged>(acc, thr, qid, cnt, t0, t, kq, writer, nwriters, a, stage, stage_cnt);
     };
     if constexpr (KSPLIT) {
         for (int t = 0; t < nt; t += 2) {
@@ -1154,44 +925,19 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
 #undef TS16_THR8
 #undef TS16_PIECE
 #undef TS16_ISSUED
-    if (I8 && VARIANT != 13) {
-        // (this wave's own writes, read back by the wave that made them: LDS works them off in order)
-        const u32 n = min(scnt, (u32)kScreenStageCap);
-        for (u32 e = lane; e < n; e += 64) {
-            const uint2 v = stage8[e];
-            const u32 pos = __hip_atomic_fetch_add(&s_count[v.y], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (pos < (u32)kScreenListCap) s_cand[(int64_t)v.y * kScreenListCap + pos] = (u64)v.x;
-        }
+    if (I8 && !variant_test_only(VARIANT)) {
+        screen_flush_stage(stage8, scnt, lane, s_count, s_cand);
     } else if (kStaged && !I8) {
-        // the tile loop is over (no DMA in flight that a counted wait still watches): staged candidates -> shared lists
-        const u32 n = min(*stage_cnt, (u32)kMfma16StageCap);
-        for (u32 e = lane; e < n; e += 64) {
-            const uint4 v = stage[e];
-            const u32 pos = atomicAdd(&a.count[v.z], 1u);
-            if (pos < (u32)a.cap) a.cand[(int64_t)v.z * a.cap + pos] = ((u64)v.y << 32) | v.x;
-        }
+        mfma16_flush_stage(a, stage, stage_cnt, lane);
     } else {
 #pragma unroll
         for (int b = 0; b < NB; ++b) a.pcount[(int64_t)qid[b] * nwriters + writer] = cnt[b];
     }
     if (!SPARSE && a.wg_ticks && threadIdx.x == 0 && qhalf == 0)
         a.wg_ticks[wg] = (unsigned)(__builtin_amdgcn_s_memrealtime() - wg_start);
-    if (kStamps && a.dbg && lane == 0) {
-        unsigned long long* d = a.dbg + ((size_t)blockIdx.x * 4 + wave) * 4;
-        d[0] = cycle_stamp() - t_all0;
-        d[1] = t_vm;
-        d[2] = t_bar;
-        d[3] = VARIANT == 10 ? t_tail : t_dma;
-    }
-    if (kProbe && a.dbg && threadIdx.x == 0) {
-        const unsigned long long c_end = __builtin_amdgcn_s_memtime();
-        const unsigned long long r_end = __builtin_amdgcn_s_memrealtime();
-        unsigned long long* d = a.dbg + (size_t)blockIdx.x * 4;
-        d[0] = c_end - c_begin;
-        d[1] = r_end - r_begin;
-        d[2] = (unsigned long long)nu;
-        d[3] = 0;
-    }
+    if (kStamps && a.dbg && lane == 0)
+        mfma16_write_stamps(a.dbg + ((size_t)blockIdx.x * 4 + wave) * 4, t_all0, t_vm, t_bar, VARIANT == kVariantScreenStamps ? t_tail : t_dma);
+    if (kProbe && a.dbg && threadIdx.x == 0) mfma16_write_probe(a.dbg, c_begin, r_begin, nu);
 }
 
 }  // namespace ts

@@ -25,7 +25,7 @@
 //     costs kRankT compares per score), are summed over the four lanes of a query by shuffles and flushed with one global
 //     atomic per (workgroup, query, target) at the end.  NaN scores and padding rows never count.
 #pragma once
-#include "kernels_mfma16.h"
+#include "kernels_mfma16_ops.h"
 
 namespace ts {
 

@@ -21,7 +21,7 @@
 // the additions only; the thresholds they produce are estimates that the full pass verifies (a query with fewer than k
 // candidates back is re-run exactly), so nothing downstream depends on bit-equal sample scores.
 #pragma once
-#include "kernels_mfma16.h"
+#include "kernels_screen8_tile.h"
 
 namespace ts {
 
@@ -43,7 +43,7 @@ struct SampleArgs {
     const unsigned* wg_ticks;
     int part_g;
     float part_gain;
-    // optional: the int8 screen's image of this launch's queries (screen_quantize_query, kernels_mfma16.h; bf16 at d = 768 or 1024),
+    // optional: the int8 screen's image of this launch's queries (screen_quantize_query, kernels_screen8_tile.h; bf16 at d = 768 or 1024),
     // made by the workgroups of the extra row (grid.y = chunks + 1 then) - it needs only `q`, and the screen runs behind the
     // select that follows this launch
     signed char* scr_qimg;

@@ -14,7 +14,7 @@
 //   S >= thr  =>  x~.q~ >= (thr - E_t |q| - X_t |e_q|) / (s_t s_q),   E_t = max|e_x| + 768 2^-22 (X_t + max|e_x|), X_t = max|s_t x~|
 // over the rows of the tile.  The tile scalars are computed in fp64 and rounded up (tx = 1 / s_t, ty = E_t, tz = X_t).
 //
-// The integer threshold (kernels_mfma16.h) takes a relative slack of 2^-18 of M = athr + ty qn + tz eq (athr = |thr|, 0 where
+// The integer threshold (kernels_screen8_tile.h) takes a relative slack of 2^-18 of M = athr + ty qn + tz eq (athr = |thr|, 0 where
 // thr is infinite; qn = |q|, eq = |e_q|, rq = 1 / s_q) and one more unit:
 //   floor(tx (thr - athr 2^-18 - (ty qn + tz eq)(1 + 2^-18)) rq - 1) = floor(tx (Q1 - ty Q2 - tz Q3) - 1)
 // with the query's side folded once per launch (screen_fold_query): Q1 = rq (thr - athr 2^-18), Q2 = rq qn (1 + 2^-18),
@@ -112,7 +112,7 @@ __global__ void __launch_bounds__(256) quantize_tiles_kernel(const unsigned shor
     }
 }
 
-// One wave per query of the launch (256 workgroups): screen_quantize_query (kernels_mfma16.h) as a launch of its own - for
+// One wave per query of the launch (256 workgroups): screen_quantize_query (kernels_screen8_tile.h) as a launch of its own - for
 // searches whose threshold does not come from the dense sample, whose launch carries this work otherwise (kernels_sample.h).
 template <int W>
 __global__ void __launch_bounds__(64) quantize_queries_kernel(const unsigned short* __restrict__ q, int nrows,

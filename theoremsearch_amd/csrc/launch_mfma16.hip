@@ -15,14 +15,14 @@ static int launch_mfma16(int dev, bool full_pass, int variant, int grid, hipStre
     constexpr bool kDiag = false;                     // ... and in the diagnostic build only (make diag)
 #endif
     if (!full_pass) {
-        if constexpr (kSparseToo) return launch_lds<mfma16_topk_kernel<D, NB, 0, true>>(dev, grid, kMfmaThreads, lds, st, a);
+        if constexpr (kSparseToo) return launch_lds<mfma16_topk_kernel<D, NB, kVariantProduct, true>>(dev, grid, kMfmaThreads, lds, st, a);
         else return fail(TS_ERR_INTERNAL, "no sparse level of the 16x16 kernel at d = %d", D);
     }
     auto go = [&](auto v) { return launch_lds<mfma16_topk_kernel<D, NB, decltype(v)::value, false>>(dev, grid, kMfmaThreads, lds, st, a); };
     int rc;
     if constexpr (kDiag)
-        if (launch_variant<1, 2, 3, 4, 7, 5, 6>(variant, &rc, go)) return rc;
-    return go(variant_c<0>{});
+        if (launch_variant<kVariantNoEpilogue, kVariantDmaOnly, kVariantClockProbe, kVariantTestOnly, kVariantNoDma, kVariantStamps, kVariantSleep>(variant, &rc, go)) return rc;
+    return go(variant_c<kVariantProduct>{});
 }
 
 
@@ -41,9 +41,9 @@ static int launch_mfma16_pair(int dev, int variant, int grid, hipStream_t st, co
     };
 #ifdef TS_DIAG
     int rc;
-    if (launch_variant<1, 2, 7>(variant, &rc, go)) return rc;
+    if (launch_variant<kVariantNoEpilogue, kVariantDmaOnly, kVariantNoDma>(variant, &rc, go)) return rc;
 #endif
-    return go(variant_c<0>{});
+    return go(variant_c<kVariantProduct>{});
 }
 
 // d = 384 / 512 / 768 / 1024, nb = query blocks of 16 per wave (64 * nb queries per launch; d = 1024: at most 3)

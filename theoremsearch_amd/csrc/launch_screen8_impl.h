@@ -9,18 +9,18 @@ static int launch_screen8(int dev, int grid, int variant, hipStream_t st, const 
     constexpr int D = W / 2;            // the int8 row as a bf16 row of half as many elements
     constexpr int lds = Mfma16Dims<D>::kLds + kMfma16StageBytes;
 #ifdef TS_DIAG
-    constexpr bool kDiag = NB == 4;     // the timing-only forms (VARIANT 9 .. 13) exist for the headline batch only
+    constexpr bool kDiag = NB == 4;     // the timing-only forms (variant_screen_diag) exist for the headline batch only
 #else
     constexpr bool kDiag = false;       // ... and in the diagnostic build only (make diag)
 #endif
     static_assert(lds <= 160 * 1024, "DMA ring + staged candidates must fit the CU's LDS");
-    // a search with a row mask runs the form of the kernel that tests it (VARIANT 14); the unmasked product (8) has no such code
+    // a search with a row mask runs the form of the kernel that tests it (kVariantScreenMasked); the unmasked product (kVariantScreen) has no such code
     const bool masked = a.row_mask != nullptr;
     auto go = [&](auto v) { return launch_lds<mfma16_topk_kernel<D, NB, decltype(v)::value, false>>(dev, grid, kMfmaThreads, lds, st, a); };
     int rc;
     if constexpr (kDiag)
-        if (launch_variant<9, 10, 11, 12, 13>(variant, &rc, go)) return rc;
-    return masked ? go(variant_c<14>{}) : go(variant_c<8>{});
+        if (launch_variant<kVariantScreenNoEpilogue, kVariantScreenStamps, kVariantScreenClockProbe, kVariantScreenDmaOnly, kVariantScreenTestOnly>(variant, &rc, go)) return rc;
+    return masked ? go(variant_c<kVariantScreenMasked>{}) : go(variant_c<kVariantScreen>{});
 }
 
 // Before the search's first launch: the image covers every row written so far (allocated with the rows' capacity, made anew
@@ -64,7 +64,7 @@ static int screen_prepare_w(ts_index* ix, const void* qmat, int nq_launch, bool 
 }
 
 // The full pass, screened: `a` is the bf16 pass's argument block (thresholds, row mask, tile table, the final select's lists).
-// variant 9 .. 13: a timing-only form of the screen (diagnostic build; wrong results), 0: the product.  ksplit (W = 1024): the
+// variant: a timing-only form of the screen (variant_screen_diag; diagnostic build; wrong results), or kVariantProduct.  ksplit (W = 1024): the
 // unscreened pass of this call would have been the paired k-split form - the rescore adds its two half-chains as that form does.
 template <int W>
 static int screen_full_pass_w(ts_index* ix, int nb, int nq, int grid, int variant, bool ksplit, hipStream_t st, const MfmaArgs& a) {

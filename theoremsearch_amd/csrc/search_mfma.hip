@@ -5,6 +5,7 @@
 #include "host.h"
 #include "kernels_mfma.h"
 #include "kernels_mfma16.h"
+#include "mfma16_variants.h"
 #include "kernels_mfma_f32.h"
 #include "kernels_sample.h"
 #include "kernels_select.h"
@@ -150,15 +151,15 @@ static MfmaPlan mfma_plan(const ts_index* ix, int nq, int k) {
     p.statistical = ix->knobs.get(K_MFMA_STAT, 1) != 0;
     p.lv = plan_levels(ix->knobs, ix->n, p.kk, p.statistical);
     const std::vector<Level>& lv = p.lv;
-    // TS_MFMA_VARIANT 9 .. 13: the timing-only forms of the int8 screen (diagnostic build only; launch_screen8*.hip)
+    // TS_MFMA_VARIANT kVariantScreenNoEpilogue .. kVariantScreenTestOnly: the timing-only forms of the int8 screen (diagnostic build only; launch_screen8*.hip)
 #ifdef TS_DIAG
-    p.screen_diag = p.variant >= 9 && p.variant <= 13;
+    p.screen_diag = variant_screen_diag(p.variant);
 #else
     p.screen_diag = false;
 #endif
     // bf16 at d = 768 (or, with TS_MFMA_SCREEN_WIDE, d = 1024) behind a threshold: the full pass runs as the int8 screen + exact
     // rescore (kernels_screen8.h), the same candidates >= thr for the final select
-    p.screen = p.shape16 && (p.variant == 0 || p.screen_diag) && lv.size() >= 2 && lv.back().stride == 1 && lv.back().run == 1 &&
+    p.screen = p.shape16 && (p.variant == kVariantProduct || p.screen_diag) && lv.size() >= 2 && lv.back().stride == 1 && lv.back().run == 1 &&
                screen_usable(ix);
     // d = 1024, 193 .. 256 queries: the unscreened pass is a launch of workgroup pairs, in the k-split form unless TS_MFMA_PAIR=1.
     // The screen holds all 256 queries in ONE unpaired launch (four blocks per wave: an int8 query fragment is half the
@@ -205,7 +206,7 @@ static MfmaPlan mfma_plan(const ts_index* ix, int nq, int k) {
     // equal finishing times for the next search (kernels_select.h, rebalance_tiles).  The table starts as equal shares and
     // is re-made whenever the grid or the number of tiles changes.
     p.balance = p.shape16 && ix->knobs.get(K_MFMA_BALANCE, 1) != 0 && p.wgs >= 8 && p.wgs <= 256 && lv.back().stride == 1 &&
-                lv.back().run == 1 && lv.back().ntiles >= 32 * (int64_t)p.wgs && (p.variant == 0 || p.variant == 3 || p.screen_diag);
+                lv.back().run == 1 && lv.back().ntiles >= 32 * (int64_t)p.wgs && (p.variant == kVariantProduct || p.variant == kVariantClockProbe || p.screen_diag);
     return p;
 }
 
@@ -245,7 +246,7 @@ static int mfma_scratch(ts_index* ix, const MfmaPlan& p, hipStream_t st) {
         HIP_TRY(hipMemsetAsync(ix->pair_pos, 0, kMfmaMaxGrid * sizeof(unsigned), st));
     }
 #ifdef TS_DIAG
-    if (p.variant >= 3 && !ix->dbg) HIP_TRY(hipMalloc((void**)&ix->dbg, 2048 * 4 * 4 * 8));
+    if (variant_gets_dbg(p.variant) && !ix->dbg) HIP_TRY(hipMalloc((void**)&ix->dbg, 2048 * 4 * 4 * 8));
 #endif
     return TS_OK;
 }
@@ -318,7 +319,7 @@ static int mfma_sample(ts_index* ix, const MfmaPlan& p, int nq, const void* qmat
 // What a timing variant's full pass left in MfmaArgs::dbg, read back and printed (or kept in the handle: the clock probe).
 static int mfma_diag_readout(ts_index* ix, const MfmaPlan& p, const unsigned long long* dbg, hipStream_t st) {
     const int grid = p.grid, variant = p.variant;
-    if (p.shape16 && (variant == 3 || (p.screen && variant == 11))) {
+    if (p.shape16 && (variant == kVariantClockProbe || (p.screen && variant == kVariantScreenClockProbe))) {
         // clock probe (MI355X_MICROARCH.md "DVFS give-back" item 6): shader cycles / 100 MHz ticks around the tile loop,
         // median over workgroups
         std::vector<unsigned long long> h((size_t)grid * 4);
@@ -354,15 +355,15 @@ static int mfma_diag_readout(ts_index* ix, const MfmaPlan& p, const unsigned lon
                 fprintf(stderr, "\n");
             }
         }
-    } else if (p.shape16 && (variant == 5 || (p.screen && variant == 10))) {
+    } else if (p.shape16 && (variant == kVariantStamps || (p.screen && variant == kVariantScreenStamps))) {
         std::vector<unsigned long long> h((size_t)grid * 16);
         HIP_TRY(hipStreamSynchronize(st));
         HIP_TRY(hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost));
-        const double units = (double)(p.lv.back().ntiles * (variant == 10 ? (ix->d == 1024 ? Mfma16Dims<512>::kUnits : Mfma16Dims<384>::kUnits) : MfmaDims<768>::kUnits)) / grid;
+        const double units = (double)(p.lv.back().ntiles * (variant == kVariantScreenStamps ? (ix->d == 1024 ? Mfma16Dims<512>::kUnits : Mfma16Dims<384>::kUnits) : MfmaDims<768>::kUnits)) / grid;
         for (int wv = 0; wv < 4; ++wv) {
             double tot = 0, vm = 0, bar = 0, dma = 0;
             for (int w = wv; w < grid * 4; w += 4) { tot += h[w * 4]; vm += h[w * 4 + 1]; bar += h[w * 4 + 2]; dma += h[w * 4 + 3]; }
-            if (variant == 10)
+            if (variant == kVariantScreenStamps)
                 fprintf(stderr, "[tsearch stamps8] wave %d per tile: total %.0f cycles, vmcnt wait %.0f, barrier wait %.0f, tile tail %.0f (drain to end of epilogue; stamp cost ~40 each included)\n",
                         wv, tot / grid / units, vm / grid / units, bar / grid / units, dma / grid / units);
             else
@@ -418,11 +419,11 @@ static int mfma_level(ts_index* ix, const MfmaPlan& p, size_t i, int nq, int k, 
     a.scr_tile = nullptr;
     a.scr_q = nullptr;
 #ifdef TS_DIAG
-    if (p.variant >= 3) a.dbg = ix->dbg;
+    if (variant_gets_dbg(p.variant)) a.dbg = ix->dbg;
 #endif
     hipEvent_t stop = full_pass ? prof_begin(ix, st, ix->n) : nullptr;  // only the full pass is bracketed
     int rc;
-    if (p.screen && full_pass) rc = screen_full_pass(ix, p.nb16, nq, p.grid, p.screen_diag ? p.variant : 0, p.ksplit_form, st, a);
+    if (p.screen && full_pass) rc = screen_full_pass(ix, p.nb16, nq, p.grid, p.screen_diag ? p.variant : kVariantProduct, p.ksplit_form, st, a);
     else if (ix->dtype == TS_F32 && p.shape16) rc = launch_pass_mfma16_f32(ix->device, ix->d, p.nb16, full_pass, p.grid, st, a);
     else if (ix->dtype == TS_F32) rc = launch_pass_mfma32_f32(ix->device, full_pass, p.variant, p.grid, st, a);
     else if (p.shape16) rc = launch_pass_mfma16(ix->device, ix->d, p.nb16, full_pass, p.variant, p.grid, st, a);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Audit of the hand-placed LDS reads of kernels_mfma16.h in the compiled ISA.
+"""Audit of the hand-placed LDS reads of kernels_mfma16.h (lds_read16, kernels_mfma16_ops.h) in the compiled ISA.
 
 The corpus fragments are fetched by `asm volatile` ds_read_b128 statements hipcc does not count: between such a read and
 the explicit `s_waitcnt lgkmcnt(N)` that covers it, nothing may read the destination registers (an MFMA would multiply

@@ -2,7 +2,7 @@
 //
 //   leg 0  stream + matrix   the product kernel's tile loop without its epilogue and candidate path: the same 256 workgroups
 //                            x 4 waves, the same LDS-DMA ring, the same ds_read_b128 and v_mfma_f32_16x16x32_bf16 count per
-//                            unit (mfma16_topk_kernel<768, 4, VARIANT 1>)
+//                            unit (mfma16_topk_kernel<768, 4, kVariantNoEpilogue>)
 //   leg 1  stream only       the DMA ring alone (VARIANT 2): what HBM -> LDS delivers with nothing else on the chip
 //   leg 2  matrix + LDS      the MFMAs and the fragment reads without the DMA stream (VARIANT 7)
 //   leg 3  bare matrix       the same number of v_mfma_f32_16x16x32_bf16 per wave with every operand in registers: the bf16
@@ -121,14 +121,14 @@ int run_leg(int leg, const unsigned short* corpus, int64_t rows, const unsigned 
     a.nq_real = 256;
     a.fb_count = s.fb;
     if (!s.attr) {
-        if (hipFuncSetAttribute((const void*)mfma16_topk_kernel<kD, kNB, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds) != hipSuccess) return -1;
-        if (hipFuncSetAttribute((const void*)mfma16_topk_kernel<kD, kNB, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds) != hipSuccess) return -1;
-        if (hipFuncSetAttribute((const void*)mfma16_topk_kernel<kD, kNB, 7, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)mfma16_topk_kernel<kD, kNB, kVariantNoEpilogue, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)mfma16_topk_kernel<kD, kNB, kVariantDmaOnly, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)mfma16_topk_kernel<kD, kNB, kVariantNoDma, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds) != hipSuccess) return -1;
         s.attr = true;
     }
-    if (leg == 0) mfma16_topk_kernel<kD, kNB, 1, false><<<grid, kMfmaThreads, kLds, st>>>(a);
-    else if (leg == 1) mfma16_topk_kernel<kD, kNB, 2, false><<<grid, kMfmaThreads, kLds, st>>>(a);
-    else if (leg == 2) mfma16_topk_kernel<kD, kNB, 7, false><<<grid, kMfmaThreads, kLds, st>>>(a);
+    if (leg == 0) mfma16_topk_kernel<kD, kNB, kVariantNoEpilogue, false><<<grid, kMfmaThreads, kLds, st>>>(a);
+    else if (leg == 1) mfma16_topk_kernel<kD, kNB, kVariantDmaOnly, false><<<grid, kMfmaThreads, kLds, st>>>(a);
+    else if (leg == 2) mfma16_topk_kernel<kD, kNB, kVariantNoDma, false><<<grid, kMfmaThreads, kLds, st>>>(a);
     else bare_mfma_kernel<<<grid, kMfmaThreads, 0, st>>>(q, corpus, a.ntiles, s.sink);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
