@@ -134,9 +134,14 @@ int ts_index_info(const ts_index *ix, int64_t *n, int32_t *d, int32_t *dtype, in
  * (an int8 image of the rows, 768 bytes per row more) followed by an exact rescore of the screened rows from the bf16 rows.
  * "TS_MFMA_SCREEN_WIDE" (default 0): the same for bf16 d = 1024 indexes - opt-in because the image costs 1,024 bytes per row
  * (10.24 GB at 10M rows; allocated and filled on the first screened search, kept up to date lazily after uploads / appends).
- * Contract of both: ids and score bits of every search are identical with the option on and off, for every batch size and
- * whichever form the unscreened d = 1024 pass would take (TS_MFMA_PAIR, TS_MFMA_GRID); views and attached rows are never
- * screened.  ts_search_stats.screened tells which pass a call ran. */
+ * "TS_MFMA_SCREEN_F32" (default 0): the same for fp32 indexes at d = 768 and d = 1024 on the 16x16 kernel (never the 32x32x2
+ * kernel, TS_MFMA_F32=32, and only the usual two-level search: not with TS_MFMA_STAT=0 or TS_MFMA_SAMPLE=0) - int8 screen, then an exact fp32 rescore that repeats the fp32 pass's fmaf chain; a screened search
+ * holds up to 256 queries per launch instead of 64 or 128.  Opt-in because the image costs d bytes per row on top of the rows
+ * (+25 %: 7.68 GB at 10M x 768).  TS_MFMA_SCREEN=0 switches every screen off.
+ * Contract of all three: ids and score bits of every search are identical with the option on and off, for every batch size and
+ * whichever form the unscreened pass would take (TS_MFMA_PAIR, TS_MFMA_GRID at bf16 d = 1024) - for every query that neither
+ * call sent to the exact re-run, which has the scan's arithmetic either way; views and attached rows are never screened.
+ * ts_search_stats.screened tells which pass a call ran. */
 int ts_index_set_option(ts_index *ix, const char *name, int32_t value);
 int ts_index_reset_option(ts_index *ix, const char *name);
 

@@ -89,14 +89,14 @@ enum Knob {
     K_MFMA_MIN_RANK, K_MFMA_VARIANT, K_MFMA_GROUPS, K_MFMA_GRID, K_MFMA_STAT, K_MFMA_STAT_CANDS, K_MFMA_TAIL_FIT,
     K_MFMA_NO_IDLE, K_MFMA_AHEAD, K_MFMA_TARGET_CANDS, K_MFMA_FIRST_ROWS, K_MFMA_TARGET_SPARSE, K_MFMA_RUN,
     K_MFMA_MIN_ROWS, K_MFMA_SHAPE, K_MFMA_F32, K_SCAN_GENERIC, K_SCAN_MAX_QUERIES, K_MFMA_BALANCE, K_PROBE_SPREAD, K_MFMA_SAMPLE,
-    K_MFMA_PAIR, K_MFMA_PAIR_LAG, K_MFMA_SCREEN, K_MFMA_SCREEN_WIDE, K_COUNT
+    K_MFMA_PAIR, K_MFMA_PAIR_LAG, K_MFMA_SCREEN, K_MFMA_SCREEN_WIDE, K_MFMA_SCREEN_F32, K_COUNT
 };
 inline const char* const kKnobNames[K_COUNT] = {
     "TS_MFMA_MIN_RANK", "TS_MFMA_VARIANT", "TS_MFMA_GROUPS", "TS_MFMA_GRID", "TS_MFMA_STAT", "TS_MFMA_STAT_CANDS",
     "TS_MFMA_TAIL_FIT", "TS_MFMA_NO_IDLE", "TS_MFMA_AHEAD", "TS_MFMA_TARGET_CANDS", "TS_MFMA_FIRST_ROWS",
     "TS_MFMA_TARGET_SPARSE", "TS_MFMA_RUN", "TS_MFMA_MIN_ROWS", "TS_MFMA_SHAPE", "TS_MFMA_F32", "TS_SCAN_GENERIC",
     "TS_SCAN_MAX_QUERIES", "TS_MFMA_BALANCE", "TS_PROBE_SPREAD", "TS_MFMA_SAMPLE", "TS_MFMA_PAIR", "TS_MFMA_PAIR_LAG",
-    "TS_MFMA_SCREEN", "TS_MFMA_SCREEN_WIDE"};
+    "TS_MFMA_SCREEN", "TS_MFMA_SCREEN_WIDE", "TS_MFMA_SCREEN_F32"};
 struct Knobs {
     int v[K_COUNT];
     bool set[K_COUNT];
@@ -165,7 +165,7 @@ struct ts_index {
     bool ordered = false;                                    //   next call behind it (`ordered`: recorded at least once)
     int64_t* part = nullptr;    unsigned* wg_ticks = nullptr;    // full pass of the 16x16 kernel: tile boundaries per workgroup, their times
     int part_g = 0;             int64_t part_ntiles = -1;        // ... the grid and tile count the table was made for
-    // int8 screen of the d = 768 (or, opt-in, 1024) bf16 full pass (kernels_screen8.h): the image [scr_pad x d] int8 + [scr_pad / 32] tile scalars,
+    // int8 screen of the d = 768 (or, opt-in, 1024) bf16 full pass and, opt-in, of the d = 768 / 1024 fp32 one (kernels_screen8.h): the image [scr_pad x d] int8 + [scr_pad / 32] tile scalars,
     // brought up to date before a screened pass for the rows written since (scr_lo .. scr_hi, marked by every upload / append)
     void* scr_rows = nullptr;   float* scr_tile = nullptr;   int64_t scr_pad = 0;
     int64_t scr_lo = 0, scr_hi = 0;
@@ -339,13 +339,19 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
 // on device `dev`, the handle's
 int launch_pass_mfma16(int dev, int d, int nb, bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);
 int launch_pass_mfma16_f32(int dev, int d, int nb, bool full_pass, int grid, hipStream_t st, const ts::MfmaArgs& a);
-// the int8 screen + exact rescore in place of the bf16 full pass (launch_screen8.hip): screen_usable = this index, this launch;
-// ksplit = the rescore takes the k-split form of the d = 1024 pass (the form the call's unscreened pass would have taken)
+// the int8 screen + exact rescore in place of the full pass (launch_screen8.hip): screen_usable = this index, this launch;
+// ksplit = the rescore takes the k-split form of the d = 1024 bf16 pass (the form the call's unscreened pass would have taken)
 bool screen_usable(const ts_index* ix);
 int screen_prepare(ts_index* ix, const void* qmat, int nq_launch, bool quantize_queries, hipStream_t st);
 int screen_full_pass(ts_index* ix, int nb, int nq, int grid, int variant, bool ksplit, hipStream_t st, const ts::MfmaArgs& a);
+// ... the screen's launch alone, the tile kernel over the image (either width)
+int screen_tile_pass(ts_index* ix, int nb, int grid, int variant, hipStream_t st, const ts::MfmaArgs& a);
 // ... their d = 1024 halves (launch_screen8_wide.hip)
 int screen_prepare_wide(ts_index* ix, const void* qmat, int nq_launch, bool quantize_queries, hipStream_t st);
 int screen_full_pass_wide(ts_index* ix, int nb, int nq, int grid, int variant, bool ksplit, hipStream_t st, const ts::MfmaArgs& a);
+int screen_tile_pass_wide(ts_index* ix, int nb, int grid, int variant, hipStream_t st, const ts::MfmaArgs& a);
+// ... and those of fp32 indexes (launch_screen8_f32.hip): fp32 quantisers, screen_tile_pass, the fp32 rescore
+int screen_prepare_f32(ts_index* ix, const void* qmat, int nq_launch, hipStream_t st);
+int screen_full_pass_f32(ts_index* ix, int nb, int nq, int grid, int variant, hipStream_t st, const ts::MfmaArgs& a);
 int launch_pass_mfma32(int dev, int d, int groups, bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);
 int launch_pass_mfma32_f32(int dev, bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);

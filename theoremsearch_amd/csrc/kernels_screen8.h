@@ -43,6 +43,44 @@
 // A tile with a NaN / Inf value, or a query with one, has threshold INT_MIN (tx or rq is NaN; the clamp's maxNum turns the NaN
 // into -2^31): all of its pairs are candidates and the exact rescore treats them as the bf16 pass does (a NaN score is never a
 // candidate).  An infinite thr gives 2^30 (+inf: nothing passes) or INT_MIN (-inf: everything does).
+//
+// fp32 rows (TS_MFMA_SCREEN_F32; d = 768 and 1024; the quantisers and the rescore are in kernels_screen8_f32.h).  The image, the
+// scalars' layout, the fold, the integer threshold and the tile kernel are the ones above; three things differ.
+//   * Stored values.  x and q are the stored fp32 values: e_x = x - s_t x~ and e_q = q - s_q q~ are measured against them (in
+//     fp64, whatever the fp32 division and rint made of x~), so the decomposition of x.q above holds as it stands.
+//   * Score arithmetic.  The fp32 pass does not add exact products: its score S is a chain of W fused multiply-adds from a zero
+//     accumulator, S = fma(x_k q_k, S) over k in the kernel's fixed permutation k = 16 s + 4 (lane >> 4) + i (k-step s
+//     ascending, then MFMA i = 0 .. 3 of v_mfma_f32_16x16x4_f32, then the four lane groups inside one instruction), with ONE
+//     rounding per term.  Term j of the chain passes through at most W - j + 1 roundings, so, u = 2^-24,
+//       |S - x.q| <= gamma_W sum |x_k q_k| <= gamma_W |x| |q|,  gamma_W = W u / (1 - W u) <= W 2^-24 (1 + 2^-13)  (W <= 1024)
+//     in any order of the terms - one rounding more per term than the bf16 pass, whose products are exact.  g = W 2^-22 is
+//     4 (1 - W u) gamma_W: still four times the bound (less 2^-14 of it), the factor that covers a matrix pipe that does not
+//     round every addition to nearest.  kScreenGamma<W> stays as it is.
+//   * Range.  fp32 values are not pre-shrunk by a bf16 rounding and span 2^-149 .. 2^128.  With a_t = the largest magnitude of a
+//     tile and a_q = that of a query:
+//       - Overflow.  Every partial sum of the chain is at most W a_t a_q (1 + gamma_W).  Past 2^128 the chain gives +-Inf or NaN
+//         where x.q is finite, and the inequality above says nothing.
+//       - Underflow.  A product, a partial sum or an operand below 2^-126 is rounded to a multiple of 2^-149 or, in a flushing
+//         mode, to zero: per term an absolute error of at most 2^-126 (the result), 2^-126 a_q (an x_k taken as zero) or
+//         2^-126 a_t (a q_k), which gamma_W's relative model does not contain: U = W 2^-126 (1 + a_q + a_t) in all.
+//       - The scalars.  s_t = a_t / 127 and s_q = a_q / 127 must be normal fp32 numbers with finite reciprocals, and the three
+//         FMAs of the threshold must stay clear of underflow themselves: their rounding argument above (2^-24 R per operation)
+//         holds while 2^-24 R is far above 2^-126.
+//     The rule, decided in the quantisers (the tile loop only ever sees a NaN scalar): a tile is IN RANGE when a_t = 0 or
+//     2^-100 <= a_t <= 2^64, a query when a_q = 0 or 2^-40 <= a_q <= 2^40.  Every other tile and every other query gets
+//     1 / s = NaN, like a tile or query with a NaN / Inf value: threshold INT_MIN, all of its pairs are candidates and the exact
+//     rescore decides.  For a pair of an in-range tile and an in-range query:
+//       - W a_t a_q (1 + gamma_W) <= 2^10 2^64 2^40 (1 + 2^-13) < 2^115: nothing in the chain overflows;
+//       - |q| >= a_q >= 2^-40 (a zero query has S = 0 = x.q exactly), so U <= |q| W 2^-126 (2^40 + 1 + 2^40 a_t)
+//         <= |q| W 2^-85 (1 + a_t): the tile adds that to its coefficient of |q|,
+//           E_t = max|e_x| + g (X_t + max|e_x|) + W 2^-85 (1 + a_t)
+//         (relative to a_t it is 2^-63 of g: it only shows where the tile is tiny), and S >= thr  =>  x~.q~ >= ... as above;
+//       - 127 2^-64 <= 1 / s_t <= 127 2^100 and 127 2^-40 <= 1 / s_q <= 127 2^40: normal, finite (a zero tile or query has s = 1);
+//         X_t <= 33 a_t and |q| <= 32 a_q are finite, the fp64 sums of squares are far inside fp64;
+//       - R >= Q2 ty >= 127 W 2^-85 > 2^-69 (Q2 = rq |q| (1 + 2^-18) >= 127, ty = E_t >= W 2^-85), so 2^-24 R > 2^-93: an
+//         underflow inside the three FMAs (at most 2^-126 each, e.g. tz Q3 with a tiny |e_q|) is 2^-33 of one rounding.  Q1 may
+//         overflow fp32 for a huge thr: rounded down it is FLT_MAX or -Inf, both on the admitting side; tx (...) may overflow
+//         too: -Inf admits everything, +Inf only arises where the certified bound is itself beyond any integer dot product.
 #pragma once
 #include "kernels_mfma16.h"
 

@@ -1,5 +1,6 @@
 // The int8 screen's host side for one width W (768 or 1024; kernels_screen8.h), shared by the translation units that hold the
-// kernel instantiations of a width: launch_screen8.hip (768) and launch_screen8_wide.hip (1024).
+// kernel instantiations of a width: launch_screen8.hip (768) and launch_screen8_wide.hip (1024) - and by launch_screen8_f32.hip
+// (fp32 indexes, either width), which brings quantisers and a rescore of its own and launches the tile kernel through those two.
 #pragma once
 #include "host.h"
 #include "kernels_screen8.h"
@@ -26,8 +27,10 @@ static int launch_screen8(int dev, int grid, int variant, hipStream_t st, const 
 // Before the search's first launch: the image covers every row written so far (allocated with the rows' capacity, made anew
 // when an append has grown it), the launch's queries are quantised and the screen's lists emptied - here (quantize_queries),
 // or by the caller's threshold sample, whose launch has room for it (SampleArgs::scr_qimg).
-template <int W>
-static int screen_prepare_w(ts_index* ix, const void* qmat, int nq_launch, bool quantize_queries, hipStream_t st) {
+// quantize_tiles(tile0, nblk): the launch that quantises tiles tile0 .. tile0 + nblk - 1 from the index's rows;
+// quantize_query_rows(): the launch that quantises the queries - both in the storage type of the index.
+template <int W, class QuantizeTiles, class QuantizeQueries>
+static int screen_prepare_with(ts_index* ix, bool quantize_queries, QuantizeTiles&& quantize_tiles, QuantizeQueries&& quantize_query_rows) {
     const int64_t tiles = ix->n_pad / kTileRows;
     if (ix->scr_pad != ix->n_pad) {
         if (ix->scr_rows) HIP_TRY(hipFree(ix->scr_rows));
@@ -44,9 +47,7 @@ static int screen_prepare_w(ts_index* ix, const void* qmat, int nq_launch, bool 
         const int64_t t0 = ix->scr_lo / kTileRows;
         const int64_t t1 = std::min(tiles, (ix->scr_hi + kTileRows - 1) / kTileRows);
         for (int64_t t = t0; t < t1; t += 1 << 20) {
-            const unsigned nblk = (unsigned)std::min<int64_t>(1 << 20, t1 - t);
-            quantize_tiles_kernel<W><<<nblk, 256, 0, st>>>((const unsigned short*)ix->rows, (signed char*)ix->scr_rows,
-                                                        (float4*)ix->scr_tile, t);
+            quantize_tiles(t, (unsigned)std::min<int64_t>(1 << 20, t1 - t));
             HIP_TRY(hipGetLastError());
         }
         ix->scr_lo = ix->scr_hi = 0;
@@ -56,18 +57,30 @@ static int screen_prepare_w(ts_index* ix, const void* qmat, int nq_launch, bool 
     if (!ix->scr_cand) HIP_TRY(hipMalloc((void**)&ix->scr_cand, (size_t)kMfmaQ * kScreenCap * 8));
     if (!ix->scr_count) HIP_TRY(hipMalloc((void**)&ix->scr_count, (size_t)kMfmaQ * 4));
     if (quantize_queries) {
-        quantize_queries_kernel<W><<<kMfmaQ, 64, 0, st>>>((const unsigned short*)qmat, std::min(nq_launch, kMfmaQ), (signed char*)ix->scr_q,
-                                                       (float4*)ix->scr_qmeta, ix->scr_count);
+        quantize_query_rows();
         HIP_TRY(hipGetLastError());
     }
     return TS_OK;
 }
 
-// The full pass, screened: `a` is the bf16 pass's argument block (thresholds, row mask, tile table, the final select's lists).
-// variant: a timing-only form of the screen (variant_screen_diag; diagnostic build; wrong results), or kVariantProduct.  ksplit (W = 1024): the
-// unscreened pass of this call would have been the paired k-split form - the rescore adds its two half-chains as that form does.
 template <int W>
-static int screen_full_pass_w(ts_index* ix, int nb, int nq, int grid, int variant, bool ksplit, hipStream_t st, const MfmaArgs& a) {
+static int screen_prepare_w(ts_index* ix, const void* qmat, int nq_launch, bool quantize_queries, hipStream_t st) {
+    return screen_prepare_with<W>(
+        ix, quantize_queries,
+        [&](int64_t tile0, unsigned nblk) {
+            quantize_tiles_kernel<W><<<nblk, 256, 0, st>>>((const unsigned short*)ix->rows, (signed char*)ix->scr_rows, (float4*)ix->scr_tile, tile0);
+        },
+        [&] {
+            quantize_queries_kernel<W><<<kMfmaQ, 64, 0, st>>>((const unsigned short*)qmat, std::min(nq_launch, kMfmaQ), (signed char*)ix->scr_q,
+                                                           (float4*)ix->scr_qmeta, ix->scr_count);
+        });
+}
+
+// The screen's launch of the full pass: the tile kernel over the image, `a` being the unscreened pass's argument block
+// (thresholds, row mask, tile table); its (row, query) pairs go to the screen's lists.
+// variant: a timing-only form of the screen (variant_screen_diag; diagnostic build; wrong results), or kVariantProduct.
+template <int W>
+static int screen_tile_pass_w(ts_index* ix, int nb, int grid, int variant, hipStream_t st, const MfmaArgs& a) {
     MfmaArgs s = a;
     s.corpus = (const unsigned short*)ix->scr_rows;
     s.q = (const unsigned short*)ix->scr_q;
@@ -76,15 +89,21 @@ static int screen_full_pass_w(ts_index* ix, int nb, int nq, int grid, int varian
     s.cap = kScreenCap;
     s.scr_tile = (const float4*)ix->scr_tile;
     s.scr_q = (const float4*)ix->scr_qmeta;
-    int rc;
     switch (nb) {
-        case 1: rc = launch_screen8<W, 1>(ix->device, grid, variant, st, s); break;
-        case 2: rc = launch_screen8<W, 2>(ix->device, grid, variant, st, s); break;
-        case 3: rc = launch_screen8<W, 3>(ix->device, grid, variant, st, s); break;
-        case 4: rc = launch_screen8<W, 4>(ix->device, grid, variant, st, s); break;
+        case 1: return launch_screen8<W, 1>(ix->device, grid, variant, st, s);
+        case 2: return launch_screen8<W, 2>(ix->device, grid, variant, st, s);
+        case 3: return launch_screen8<W, 3>(ix->device, grid, variant, st, s);
+        case 4: return launch_screen8<W, 4>(ix->device, grid, variant, st, s);
         default: return fail(TS_ERR_INTERNAL, "no int8 screen with %d query blocks per wave", nb);
     }
-    TS_TRY(rc);
+}
+
+// The full pass, screened: `a` is the bf16 pass's argument block (thresholds, row mask, tile table, the final select's lists).
+// ksplit (W = 1024): the unscreened pass of this call would have been the paired k-split form - the rescore adds its two
+// half-chains as that form does.
+template <int W>
+static int screen_full_pass_w(ts_index* ix, int nb, int nq, int grid, int variant, bool ksplit, hipStream_t st, const MfmaArgs& a) {
+    TS_TRY(screen_tile_pass_w<W>(ix, nb, grid, variant, st, a));
     ScreenRescoreArgs r;
     r.rows = (const unsigned short*)ix->rows;
     r.q = a.q;

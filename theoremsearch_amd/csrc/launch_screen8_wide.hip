@@ -9,3 +9,7 @@ int screen_prepare_wide(ts_index* ix, const void* qmat, int nq_launch, bool quan
 int screen_full_pass_wide(ts_index* ix, int nb, int nq, int grid, int variant, bool ksplit, hipStream_t st, const MfmaArgs& a) {
     return screen_full_pass_w<1024>(ix, nb, nq, grid, variant, ksplit, st, a);
 }
+
+int screen_tile_pass_wide(ts_index* ix, int nb, int grid, int variant, hipStream_t st, const MfmaArgs& a) {
+    return screen_tile_pass_w<1024>(ix, nb, grid, variant, st, a);
+}

@@ -49,17 +49,27 @@ static int mfma_target_cands(const Knobs& kn, int64_t n, int kk) {
     return std::min(2048, std::max(64, kn.get(K_MFMA_TARGET_CANDS, target)));
 }
 
+// Rows the sparsest level may hold (it runs unthresholded: every score becomes a candidate, so at most kLevelSortMax rows -
+// what one select sorts - and one tile per workgroup, 16 entries per private list).
+// sample size: 8192 rows for large corpora; below 4M rows half of that estimates the threshold as well (the
+// guaranteed bound k * N / sample stays small) and its pass + select are 13 us shorter - 2 % of a 1.25M-row shard
+static int64_t first_level_rows(const Knobs& kn, int64_t n, bool statistical) {
+    const int first_default = (statistical && n < 4000000) ? kLevelSortMax / 2 : kLevelSortMax;
+    return std::min<int64_t>(kLevelSortMax, (int64_t)kn.get(K_MFMA_FIRST_ROWS, first_default));
+}
+// The full pass of a search on this handle sits behind a threshold: the corpus is more than the sparsest level may hold, so
+// plan_levels makes at least two levels (whatever k is).
+static bool thresholded_pass(const ts_index* ix) {
+    const int64_t T = (ix->n + kTileRows - 1) / kTileRows;
+    return T * kTileRows > first_level_rows(ix->knobs, ix->n, ix->knobs.get(K_MFMA_STAT, 1) != 0);
+}
+
 static std::vector<Level> plan_levels(const Knobs& kn, int64_t n, int kk, bool statistical) {
     const int64_t T = (n + kTileRows - 1) / kTileRows;
     const int target = mfma_target_cands(kn, n, kk);
     auto pow2_ratio = [&](int cands) { int64_t r = 2; while (r * 2 * kk <= cands) r *= 2; return r; };
     const int64_t r_last = pow2_ratio(target);
-    // The sparsest level runs unthresholded: every score becomes a candidate, so it may hold at most
-    // kLevelSortMax rows (what one select sorts) and one tile per workgroup (16 entries per private list).
-    // sample size: 8192 rows for large corpora; below 4M rows half of that estimates the threshold as well (the
-    // guaranteed bound k * N / sample stays small) and its pass + select are 13 us shorter - 2 % of a 1.25M-row shard
-    const int first_default = (statistical && n < 4000000) ? kLevelSortMax / 2 : kLevelSortMax;
-    const int64_t first_rows = std::min<int64_t>(kLevelSortMax, (int64_t)kn.get(K_MFMA_FIRST_ROWS, first_default));
+    const int64_t first_rows = first_level_rows(kn, n, statistical);
     const int64_t r_cap = std::max<int64_t>(2, pow2_ratio(kn.get(K_MFMA_TARGET_SPARSE, 1280)));
     std::vector<Level> lv;
     int64_t stride = 1;
@@ -101,9 +111,30 @@ static bool mfma_pairs(const ts_index* ix, int nq) {
            ix->knobs.get(K_MFMA_PAIR, 1) != 0 && mfma_grid(ix) % 16 == 0;
 }
 
+// TS_MFMA_VARIANT names a timing-only form of the int8 screen (diagnostic build only; launch_screen8*.hip)
+static bool screen_diag_variant(int variant) {
+#ifdef TS_DIAG
+    return variant_screen_diag(variant);
+#else
+    return false;
+#endif
+}
+// This handle's searches run their full pass as the int8 screen + exact rescore (kernels_screen8.h): an index the screen serves
+// (screen_usable), the product kernel (or a timing form of the screen), a full pass behind a threshold.  One predicate for the
+// pass (mfma_plan) and for the queries a launch holds (mfma_block_queries).
+static bool mfma_screened(const ts_index* ix) {
+    const int variant = ix->knobs.get(K_MFMA_VARIANT, 0);
+    return use_shape16(ix) && (variant == kVariantProduct || screen_diag_variant(variant)) && thresholded_pass(ix) && screen_usable(ix);
+}
+
 int mfma_block_queries(const ts_index* ix, int nq) {
     if (mfma_pairs(ix, nq)) return 256;
     if (ix->dtype == TS_F32) {
+        // screened (TS_MFMA_SCREEN_F32): the int8 kernel holds up to four blocks of 16 queries per wave at either width, so the
+        // image crosses HBM once for up to 256 queries; the rescore computes every score as the fp32 pass would have.  Only the
+        // two-level search is screened (screen_usable): its other launch is the dense sample, which takes any batch - no fp32
+        // matrix kernel ever sees more than its one or two blocks
+        if (mfma_screened(ix)) return 64 * std::max(1, (std::min(nq, 256) + 63) / 64);
         if (ix->d == 1024) return 64;                          // one block of 16 queries x 4 waves
         if (use_shape16(ix)) return nq <= 64 ? 64 : 128;       // one or two blocks per wave (d = 384, 512, 768)
         return kMfmaF32Queries;                                // 32x32x2 kernel: 32 queries x 4 waves
@@ -126,7 +157,7 @@ struct MfmaPlan {
     std::vector<Level> lv;      // threshold levels, sparsest first; the last one is the full pass
     int kk, variant;
     bool shape16, statistical, dense_sample, dense0;
-    bool screen_diag, screen, ksplit_form, pair;
+    bool screen_diag, screen, screen_rider, ksplit_form, pair;
     int nq_launch, groups, nb16;
     int grid, wgs, nwriters, priv_cap, pair_lag;
     int stat_cands;
@@ -152,15 +183,13 @@ static MfmaPlan mfma_plan(const ts_index* ix, int nq, int k) {
     p.lv = plan_levels(ix->knobs, ix->n, p.kk, p.statistical);
     const std::vector<Level>& lv = p.lv;
     // TS_MFMA_VARIANT kVariantScreenNoEpilogue .. kVariantScreenTestOnly: the timing-only forms of the int8 screen (diagnostic build only; launch_screen8*.hip)
-#ifdef TS_DIAG
-    p.screen_diag = variant_screen_diag(p.variant);
-#else
-    p.screen_diag = false;
-#endif
-    // bf16 at d = 768 (or, with TS_MFMA_SCREEN_WIDE, d = 1024) behind a threshold: the full pass runs as the int8 screen + exact
-    // rescore (kernels_screen8.h), the same candidates >= thr for the final select
-    p.screen = p.shape16 && (p.variant == kVariantProduct || p.screen_diag) && lv.size() >= 2 && lv.back().stride == 1 && lv.back().run == 1 &&
-               screen_usable(ix);
+    p.screen_diag = screen_diag_variant(p.variant);
+    // bf16 at d = 768 (or, with TS_MFMA_SCREEN_WIDE, d = 1024) and, with TS_MFMA_SCREEN_F32, fp32 at d = 768 / 1024, behind a
+    // threshold: the full pass runs as the int8 screen + exact rescore (kernels_screen8.h), the same candidates >= thr for the
+    // final select
+    p.screen = mfma_screened(ix) && lv.size() >= 2 && lv.back().stride == 1 && lv.back().run == 1;
+    // an fp32 search: the threshold sample carries no rider row for the screen's queries, they get a launch of their own
+    p.screen_rider = p.screen && ix->dtype != TS_F32;
     // d = 1024, 193 .. 256 queries: the unscreened pass is a launch of workgroup pairs, in the k-split form unless TS_MFMA_PAIR=1.
     // The screen holds all 256 queries in ONE unpaired launch (four blocks per wave: an int8 query fragment is half the
     // registers); its rescore adds every score in the form the pairs would have (plain chain or two half-chains), bit for bit.
@@ -285,7 +314,7 @@ static int mfma_sample(ts_index* ix, const MfmaPlan& p, int nq, const void* qmat
         sa.part_gain = (b >= 2 && b <= 10) ? 0.1f * (float)b : 0.7f;
     }
     ix->rebalance_pending = false;
-    if (p.screen) {
+    if (p.screen_rider) {
         sa.scr_qimg = (signed char*)ix->scr_q;
         sa.scr_qmeta = (float4*)ix->scr_qmeta;
         sa.scr_count = ix->scr_count;
@@ -470,7 +499,7 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
                        const void* qmat, bool in_place) {
     const MfmaPlan p = mfma_plan(ix, nq, k);
     TS_TRY(mfma_scratch(ix, p, st));
-    if (p.screen) TS_TRY(screen_prepare(ix, qmat, p.nq_launch, !p.dense0, st));
+    if (p.screen) TS_TRY(screen_prepare(ix, qmat, p.nq_launch, !(p.dense0 && p.screen_rider), st));
     for (size_t i = 0; i < p.lv.size(); ++i) {
         if (i == 0 && p.dense0) TS_TRY(mfma_sample(ix, p, nq, qmat, st));
         else TS_TRY(mfma_level(ix, p, i, nq, k, out_scores, out_idx, qmat, st));
