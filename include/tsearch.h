@@ -382,7 +382,8 @@ int ts_attention_short(int device, const void *qkv, const int64_t *attention_mas
  * heads, value heads) to out [batch][seq][q_heads * head_dim]; grouped-query when kv_heads < q_heads.  attention_mask: int64
  * [batch][seq] key mask or NULL.  pieces (may be NULL): also the bf16 pieces [batch * seq][3 * q_heads * head_dim] of the output
  * (ts_split_pieces pattern 0) for the fp32-class GEMM behind it; out may then be NULL (only the pieces are written).  Replaces torch's scaled_dot_product_attention and the four
- * layout copies around it in the three fused forwards. */
+ * layout copies around it in the three fused forwards.  A query row without a single allowed key (a padding token on the left of
+ * a causal sequence, a sequence whose mask is all zeros) comes back as zeros, in out and in pieces. */
 int ts_attention_float(int device, const void *qkv, const void *qkv_bias, const int64_t *attention_mask, int32_t batch, int32_t seq,
                        int32_t q_heads, int32_t kv_heads, int32_t head_dim, int causal, float scale, void *out, void *pieces, void *stream);
 /* The same for the decoder-style encoder the production app embeds with (Qwen/Qwen3-Embedding-0.6B, streamlit_app.py:55;

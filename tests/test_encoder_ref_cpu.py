@@ -1,0 +1,276 @@
+"""What the GPU tests of the encoder's fp32-path kernels rest on, checked without a GPU (tests/encoder_common.py):
+* the references pass their own bounds: on the inputs of tests/test_encoder_pieces_gpu.py torch's own fp32 evaluation of each
+  formula, split into pieces by split_ref, passes the bound the GPU test uses - with a factor 2 to spare;
+* the checks have teeth: each corrupted answer a wrong kernel could give is rejected;
+* the argument contract of the producers, ts_attention_float and ts_pool_normalize: every refusal returns before the device
+  check (the library loads without a device; a refusal never dereferences a pointer, so aligned fake ones do).
+The measured ratios and the rejected corruptions are printed (also without -s)."""
+import ctypes as C
+
+import pytest
+import torch
+
+import encoder_common as ec
+from conftest import gpu_available
+from theoremsearch_amd import _ffi
+
+P = 0x7F0000001000                                            # a 16-byte aligned address no refusal dereferences
+
+
+def _say(capsys, text):
+    with capsys.disabled():
+        print("\n" + text, end="")
+
+
+# ---- the references pass their own bounds ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ec.ACT_KINDS)
+def test_fp32_activation_split_by_the_reference_passes_half_the_pieces_bound(kind, capsys):
+    worst = {"pieces": 0.0, "hi": 0.0}
+    for n in ec.ACT_WIDTHS:
+        for rows in ec.ACT_ROWS:
+            x, bias = ec.act_inputs(kind, n, rows)
+            for b in (None, bias):
+                r = ec.check_act_pieces(ec.split_ref(ec.act_fp32(x, b, kind)), x, b, kind, bound_scale=0.5)
+                worst = {k: max(worst[k], r[k]) for k in worst}
+    # `pieces` is measured against the halved bound; `hi` against the whole one (half a bf16 ulp reaches 2^-8 of the value by itself)
+    _say(capsys, f"act kind {kind}: torch fp32 + split_ref reaches {worst['pieces'] / 2:.3f} of pieces_bound, hi alone {worst['hi']:.3f} of its bound")
+    assert worst["pieces"] <= 1.0 and worst["hi"] <= 1.0
+
+
+def test_hi_alone_fails_the_pieces_bound_by_two_orders(capsys):
+    """The bound separates two pieces from one: hi alone is off by up to 2^-8 |y|, 256 times what hi + lo may be."""
+    x, bias = ec.act_inputs(1, 1024, 259)
+    y64 = ec.act_ref(x, bias, 1)
+    g, u = ec.act_operands(x, bias, 1)
+    hi = ec.act_fp32(x, bias, 1).bfloat16().double()
+    ratio = (hi - y64).abs() / ec.pieces_bound(y64, g, u)
+    _say(capsys, f"hi alone: worst {float(ratio.max()):.0f} x pieces_bound, over it on {float((ratio > 1).float().mean()):.1%} of elements")
+    assert float(ratio.max()) > 100 and float((ratio > 1).float().mean()) > 0.9
+
+
+def test_fp32_norms_pass_half_the_tolerance_at_every_width(capsys):
+    worst = {"layernorm": 0.0, "layernorm+a_bias": 0.0, "rmsnorm": 0.0, "rmsnorm, no addend": 0.0, "gemma": 0.0, "gemma, no y": 0.0}
+    tol = ec.NORM_TOL[torch.float32]
+    for d in sorted(set(ec.NORM_WIDTHS_F32) | {8}):
+        for rows in ec.NORM_ROWS:
+            a, a_bias, b, gamma, beta = ec.layernorm_inputs(d, rows)
+            worst["layernorm"] = max(worst["layernorm"], ec.norm_ratio(ec.layernorm_fp32(a, None, b, gamma, beta), ec.layernorm_ref(a, None, b, gamma, beta), tol))
+            worst["layernorm+a_bias"] = max(worst["layernorm+a_bias"],
+                                            ec.norm_ratio(ec.layernorm_fp32(a, a_bias, b, gamma, beta), ec.layernorm_ref(a, a_bias, b, gamma, beta), tol))
+            assert torch.equal(ec.layernorm_ref(a, None, b, gamma, beta)[0], beta.double())          # the all-zero row: exactly beta
+            a, b, gamma = ec.rmsnorm_inputs(d, rows)
+            worst["rmsnorm"] = max(worst["rmsnorm"], ec.norm_ratio(ec.rmsnorm_fp32(a, b, gamma), ec.rmsnorm_ref(a, b, gamma)[1], tol))
+            worst["rmsnorm, no addend"] = max(worst["rmsnorm, no addend"], ec.norm_ratio(ec.rmsnorm_fp32(a, None, gamma), ec.rmsnorm_ref(a, None, gamma)[1], tol))
+            assert not ec.rmsnorm_ref(a, b, gamma)[1][0].any()                                      # the all-zero row: zeros
+            y, x, wp, wn = ec.gemma_inputs(d, rows)
+            for yy, name in ((y, "gemma"), (None, "gemma, no y")):
+                s32, h32 = ec.gemma_fp32(yy, x, wp, wn)
+                s64, h64 = ec.gemma_ref(yy, x, wp, wn)
+                worst[name] = max(worst[name], ec.norm_ratio(s32, s64, tol), ec.norm_ratio(h32, h64, tol))
+            assert not ec.gemma_ref(y, x, wp, wn)[1][0].any()
+    _say(capsys, "torch fp32 norms against fp64, worst error / (2e-5 + 2e-5 |want|): " + ", ".join(f"{k} {v:.4f}" for k, v in worst.items()))
+    assert max(worst.values()) <= 0.5
+
+
+def test_fp32_attention_and_pooling_references_agree_with_torch(capsys):
+    """attention_ref against torch's own fp32 attention at half the GPU test's 2e-5, keyless rows exactly zero; pool_ref against
+    the fp32 expression at half of 1e-5."""
+    g = torch.Generator(device="cpu").manual_seed(5)
+    worst = 0.0
+    for hq, hkv, hd, S in ((4, 2, 64, 33), (2, 1, 128, 17), (3, 1, 256, 16)):
+        qkv = torch.randn(3, S, (hq + 2 * hkv) * hd, generator=g) * 1.5
+        for kind, mask in ec.attention_masks(3, S, g).items():
+            for causal in (False, True):
+                want, has_key = ec.attention_ref(qkv, mask, hq, hkv, hd, causal, hd ** -0.5)
+                assert not want[~has_key].any()
+                if kind == "keyless":
+                    assert not has_key[2].any()
+                q = qkv[..., :hq * hd].view(3, S, hq, hd).transpose(1, 2)
+                k = qkv[..., hq * hd:(hq + hkv) * hd].view(3, S, hkv, hd).transpose(1, 2).repeat_interleave(hq // hkv, dim=1)
+                v = qkv[..., (hq + hkv) * hd:].view(3, S, hkv, hd).transpose(1, 2).repeat_interleave(hq // hkv, dim=1)
+                allow = torch.ones(3, 1, S, S, dtype=torch.bool)
+                if causal:
+                    allow = allow & torch.ones(S, S, dtype=torch.bool).tril_()
+                if mask is not None:
+                    allow = allow & (mask[:, None, None, :] != 0)
+                sc = (q @ k.transpose(-1, -2) * hd ** -0.5).masked_fill(~allow, -1e30)
+                got = (torch.softmax(sc, -1) @ v).transpose(1, 2).reshape(3, S, hq * hd)
+                worst = max(worst, float((got.double() - want)[has_key].abs().max()) / 2e-5)
+    _say(capsys, f"torch fp32 attention against attention_ref: worst error {worst:.3f} of 2e-5")
+    assert worst <= 0.5
+    hidden = torch.randn(5, 19, 100, generator=g)
+    left, holes = ec.pool_masks(5, 19, 0)
+    holes[2] = 0                                              # a row without a token: zeros under MEAN
+    for mask in (left, holes):
+        for pooling in (0, 1, 2):
+            for normalize in (False, True):
+                want = ec.pool_ref(hidden, mask, pooling, normalize)
+                m = mask.unsqueeze(-1).float()
+                got = ((hidden * m).sum(1) / m.sum(1).clamp(min=1e-9) if pooling == 0 else
+                       hidden[torch.arange(5), (mask * torch.arange(19)[None]).amax(1)] if pooling == 1 else hidden[:, 0])
+                got = torch.nn.functional.normalize(got, dim=1) if normalize else got
+                assert torch.allclose(got.double(), want, atol=5e-6, rtol=5e-6)
+    assert not ec.pool_ref(hidden, holes, 0, True)[2].any() and not ec.pool_ref(hidden, holes, 0, False)[2].any()
+
+
+# ---- the checks have teeth -------------------------------------------------------------------------------------------------------
+def _thirds(p):
+    n = p.shape[1] // 3
+    return p[:, :n], p[:, n:2 * n], p[:, 2 * n:]
+
+
+def _corrupt_act(name, kind, x, bias):
+    """The pieces a kernel with defect `name` would return for act(x + bias); None where the defect does not exist for `kind`."""
+    y = ec.act_fp32(x, bias, kind)
+    n = y.shape[1]
+    hi, lo, _ = _thirds(ec.split_ref(y))
+    if name == "[hi | hi | lo] in place of [hi | lo | hi]":
+        return torch.cat((hi, hi, lo), dim=1)
+    if name == "lo zeroed":
+        return torch.cat((hi, torch.zeros_like(lo), hi), dim=1)
+    if name == "gate and up halves swapped":
+        return None if kind == 0 else ec.split_ref(ec.act_fp32(torch.cat((x[:, n:], x[:, :n]), dim=1), torch.cat((bias[n:], bias[:n])), kind))
+    if name == "the up half's bias taken from the gate's columns":
+        return None if kind == 0 else ec.split_ref(ec.act_fp32(x, torch.cat((bias[:n], bias[:n])), kind))
+    if name == "one 4-element chunk shifted by one chunk":
+        y = y.clone()
+        y[:, 8:12] = y[:, 4:8].clone()
+        return ec.split_ref(y)
+    if name == "row r written at row r + 1":
+        return ec.split_ref(torch.roll(y, 1, dims=0))
+    raise ValueError(name)
+
+
+CORRUPTIONS = ("[hi | hi | lo] in place of [hi | lo | hi]", "lo zeroed", "gate and up halves swapped",
+               "the up half's bias taken from the gate's columns", "one 4-element chunk shifted by one chunk", "row r written at row r + 1")
+
+
+@pytest.mark.parametrize("name", CORRUPTIONS)
+def test_the_checkers_reject_a_corrupted_answer(name, capsys):
+    rejected = []
+    for kind in ec.ACT_KINDS:
+        x, bias = ec.act_inputs(kind, 252, 5)
+        ec.check_act_pieces(ec.split_ref(ec.act_fp32(x, bias, kind)), x, bias, kind)               # the right answer passes
+        bad = _corrupt_act(name, kind, x, bias)
+        if bad is None:
+            continue
+        with pytest.raises(AssertionError):
+            ec.check_act_pieces(bad, x, bias, kind)
+        rejected.append(f"act kind {kind}")
+    # the norm producers' checker (out against fp64, pieces == split_ref(out)): the defects that exist without a gate / up pair
+    a, a_bias, b, gamma, beta = ec.layernorm_inputs(260, 5)
+    out, want = ec.layernorm_fp32(a, a_bias, b, gamma, beta), ec.layernorm_ref(a, a_bias, b, gamma, beta)
+    ec.check_norm_pieces(out, ec.split_ref(out), want)
+    hi, lo, _ = _thirds(ec.split_ref(out))
+    shifted = out.clone()
+    shifted[:, 8:12] = out[:, 4:8]
+    bad = {"[hi | hi | lo] in place of [hi | lo | hi]": [(out, torch.cat((hi, hi, lo), dim=1))],
+           "lo zeroed": [(out, torch.cat((hi, torch.zeros_like(lo), hi), dim=1))],
+           "one 4-element chunk shifted by one chunk": [(shifted, ec.split_ref(shifted)), (out, ec.split_ref(shifted))],
+           "row r written at row r + 1": [(torch.roll(out, 1, dims=0), ec.split_ref(torch.roll(out, 1, dims=0))),
+                                          (out, ec.split_ref(torch.roll(out, 1, dims=0)))]}.get(name, [])
+    for o, p in bad:
+        with pytest.raises(AssertionError):
+            ec.check_norm_pieces(o, p, want)
+    if bad:
+        rejected.append("norm out / pieces")
+    _say(capsys, f"rejected: {name} ({', '.join(rejected)})")
+    assert rejected
+
+
+def test_an_unwritten_or_overrun_guarded_buffer_is_noticed():
+    t = ec.guarded((5, 12), torch.float32, device="cpu")
+    p = ec.guarded((5, 36), torch.bfloat16, device="cpu", align=8)
+    assert t.data_ptr() % 16 == 0 and p.data_ptr() % 8 == 0 and torch.isnan(t).all() and torch.isnan(p.float()).all()
+    ec.assert_margins(t, p)
+    assert ec.untouched(t[:, 8:])
+    t.zero_()
+    ec.assert_margins(t)
+    assert not ec.untouched(t[:, 8:])
+    raw, margin, body = t._guard
+    raw[margin + body] = 0                                     # one byte past the end
+    with pytest.raises(AssertionError):
+        ec.assert_margins(t)
+    raw, margin, body = p._guard
+    raw[margin - 1] = 0                                        # one byte in front
+    with pytest.raises(AssertionError):
+        ec.assert_margins(p)
+
+
+# ---- the argument contract -------------------------------------------------------------------------------------------------------
+def _p(v):
+    return None if v is None else C.c_void_p(v)
+
+
+def ln_pieces(lib, a=P, a_bias=None, b=P, gamma=P, beta=P, rows=4, d=256, out=P, pieces=P):
+    return lib.ts_add_layernorm_pieces(0, _p(a), _p(a_bias), _p(b), _p(gamma), _p(beta), 1e-12, rows, d, _p(out), _p(pieces), None)
+
+
+def rms_pieces(lib, a=P, b=P, gamma=P, rows=4, d=256, out_sum=P, out_norm=P, pieces=P):
+    return lib.ts_add_rmsnorm_pieces(0, _p(a), _p(b), _p(gamma), 1e-6, rows, d, _p(out_sum), _p(out_norm), _p(pieces), None)
+
+
+def gemma_pieces(lib, y=P, x=P, w_post=P, w_next=P, rows=4, d=256, out_sum=P, out_norm=P, pieces=P):
+    return lib.ts_gemma_norm_pieces(0, _p(y), _p(x), _p(w_post), _p(w_next), 1e-6, rows, d, _p(out_sum), _p(out_norm), _p(pieces), None)
+
+
+def act_pieces(lib, x=P, bias=None, rows=4, n=256, kind=0, pieces=P):
+    return lib.ts_act_pieces(0, _p(x), _p(bias), rows, n, kind, _p(pieces), None)
+
+
+def attention(lib, qkv=P, qkv_bias=None, mask=None, batch=2, seq=16, hq=4, hkv=2, hd=64, causal=0, scale=0.125, out=P, pieces=None):
+    return lib.ts_attention_float(0, _p(qkv), _p(qkv_bias), _p(mask), batch, seq, hq, hkv, hd, causal, scale, _p(out), _p(pieces), None)
+
+
+def pool(lib, hidden=P, mask=P, n=2, seq=8, d=64, out=P, out_ld=64):
+    return lib.ts_pool_normalize(0, _p(hidden), 0, _p(mask), n, seq, d, 0, 1, _p(out), 0, out_ld, None)
+
+
+PRODUCERS = (ln_pieces, rms_pieces, gemma_pieces, act_pieces)
+NORM_PRODUCERS = (ln_pieces, rms_pieces, gemma_pieces)
+
+
+def test_refusals_come_before_the_device_check():
+    lib = _ffi.load()
+    inv, uns = ec.TS_ERR_INVALID, ec.TS_ERR_UNSUPPORTED
+    for f in PRODUCERS:
+        assert f(lib, pieces=None) == inv, f.__name__                                         # NULL pieces
+        assert f(lib, pieces=P + 4) == inv, f.__name__                                        # pieces not 8-byte aligned
+    assert ln_pieces(lib, a_bias=P + 8) == inv                                                # a bias not 16-byte aligned
+    assert act_pieces(lib, bias=P + 8) == inv
+    assert attention(lib, qkv_bias=P + 8) == inv
+    for f in NORM_PRODUCERS:
+        assert f(lib, d=6) == inv and f(lib, d=254) == inv, f.__name__                        # d not a multiple of 4
+        assert f(lib, d=1028) == inv, f.__name__                                              # above the fp32 limit of 1024
+        assert f(lib, d=0) == inv and f(lib, rows=-1) == inv, f.__name__
+    assert act_pieces(lib, n=6) == inv and act_pieces(lib, n=254) == inv and act_pieces(lib, n=0) == inv
+    assert act_pieces(lib, kind=3) == inv and act_pieces(lib, kind=-1) == inv
+    assert gemma_pieces(lib, w_post=None) == inv                                              # y without w_post
+    assert attention(lib, hq=6, hkv=4) == inv                                                 # q_heads % kv_heads != 0
+    assert attention(lib, scale=0.0) == inv and attention(lib, scale=float("nan")) == inv and attention(lib, scale=-0.125) == inv
+    assert attention(lib, out=None, pieces=None) == inv                                       # nothing to write
+    assert attention(lib, out=None, pieces=P + 4) == inv
+    assert pool(lib, out_ld=63) == inv                                                        # out_ld < d
+    for hd, seq in ((64, 513), (128, 257), (256, 129), (32, 16)):
+        assert attention(lib, hd=hd, seq=seq) == uns, (hd, seq)
+    assert b"head size" in lib.ts_last_error()
+    # nothing to do is not an error (and needs no device)
+    for f in PRODUCERS:
+        assert f(lib, rows=0) == 0, f.__name__
+    assert attention(lib, batch=0) == 0 and pool(lib, n=0) == 0
+
+
+@pytest.mark.skipif(gpu_available(), reason="fake pointers: only where the device check refuses the call")
+def test_valid_arguments_reach_the_device_check():
+    """The same calls with nothing to refuse: TS_ERR_NODEVICE, so the refusals above were about the argument they changed."""
+    lib = _ffi.load()
+    nod = ec.TS_ERR_NODEVICE
+    for f in PRODUCERS + (attention, pool):
+        assert f(lib) == nod, f.__name__
+    assert ln_pieces(lib, a_bias=P, d=1024) == nod and rms_pieces(lib, b=None, out_sum=None, d=4) == nod
+    assert gemma_pieces(lib, y=None, w_post=None, out_sum=None) == nod
+    assert act_pieces(lib, bias=P, kind=2, pieces=P + 8) == nod
+    assert attention(lib, qkv_bias=P, mask=P, out=None, pieces=P + 8, causal=1) == nod
+    for hd, seq in ((64, 512), (128, 256), (256, 128)):
+        assert attention(lib, hd=hd, seq=seq) == nod, (hd, seq)
+    assert pool(lib, out_ld=72) == nod

@@ -69,7 +69,7 @@ def act_pieces(x: torch.Tensor, kind: int, bias: Optional[torch.Tensor] = None) 
 
 def attention_float(qkv: torch.Tensor, key_mask: Optional[torch.Tensor], B: int, S: int, hq: int, hkv: int, hd: int, causal: bool,
                     scale: float, want_pieces: bool = False, bias: Optional[torch.Tensor] = None, want_context: bool = True):
-    """fp32 attention of at most 128 tokens on the exact-fp32 matrix instructions, straight from the stacked projection's output
+    """fp32 attention of at most 512 / 256 / 128 tokens (head size 64 / 128 / 256) on the exact-fp32 matrix instructions, straight from the stacked projection's output
     ``qkv [B x S x (hq + 2 hkv) hd]`` (``ts_attention_float``; ``bias``: the projection's bias when its GEMM ran without one):
     ``(context fp32 [B x S x hq hd] - None with ``want_context=False`` - , its bf16 pieces or None)``."""
     import ctypes as C
