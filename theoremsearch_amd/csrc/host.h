@@ -20,6 +20,7 @@
 
 #include "../../include/tsearch.h"
 #include "common.h"
+#include "scan_plan.h"
 
 using namespace ts;
 
@@ -124,9 +125,7 @@ struct Knobs {
 // ---------------------------------------------------------------------------------------------
 // handles
 // ---------------------------------------------------------------------------------------------
-constexpr int kQBlock = 256;          // queries per pass of the search driver
-constexpr int kCandCap = 8192;        // candidate slots per query (MFMA path)
-constexpr int kScanGridPerCU = 4;
+constexpr int kCandCap = 8192;        // candidate slots per query (MFMA path); kQBlock, kScanGridPerCU: scan_plan.h
 constexpr size_t kStageBytes = (size_t)256 << 20;
 
 struct ts_index {
@@ -145,7 +144,8 @@ struct ts_index {
     float* sample = nullptr;                                 // MFMA path: dense [256 x 8192] score matrix of the threshold sample
     bool rebalance_pending = false, rebalance_in_rerun = false; int rebalance_grid = 0;  // the exact re-run's launch also moves the full pass's tile boundaries
     int* fb_list = nullptr;     int* fb_count = nullptr;     u32* stat = nullptr;   // [kQBlock] candidates per query of the last final select
-    u64* partial = nullptr;     u64* partial2 = nullptr;     size_t partial_bytes = 0;
+    u64* partial = nullptr;     size_t partial_bytes = 0;    // scan partials [256 slots][grid][k] keys, and the buffer the
+    u64* partial2 = nullptr;    size_t partial2_bytes = 0;   //   select rounds ping-pong with (scan_plan.h: scan_scratch)
     float* res_scores = nullptr; int64_t* res_idx = nullptr; size_t res_cap = 0;  // device result buffers (entries)
     u32* mask_dev = nullptr;    size_t mask_bytes = 0;       // filtered search: device copy of a host bitmask
     float* bias_dev = nullptr;  size_t bias_bytes = 0;       // biased search: device copy of a host bias array
@@ -331,6 +331,21 @@ int prep_dispatch(int src_dtype, int dst_dtype, bool normalize, const void* src,
 // search.hip: the streaming scan + its select (also the exact re-run of the matrix path: qlist / qcount on the device)
 int scan_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx, const int* qlist, const int* qcount,
                 hipStream_t st, const float* qbuf = nullptr, const unsigned short* qb16 = nullptr);
+// search.hip: the queries of a call, one block of at most kQBlock at a time.  query_feed_open makes sure of ix->qstore (f32copy:
+// and ix->qf32) and, for host queries, sizes the staging buffer once; query_feed_block copies a block of host queries there and
+// prepares it (prep_dispatch: normalise (COS), round to the storage type, zero-pad to 256 rows x ld; f32copy: the fp32 copy the
+// scan kernels read).
+struct QueryFeed {
+    ts_index* ix = nullptr;
+    const char* queries = nullptr;
+    size_t row_bytes = 0;
+    int q_dtype = 0;
+    bool on_device = false, f32copy = false;
+    hipStream_t st = nullptr;
+    const void* at(int q0) const { return queries + (size_t)q0 * row_bytes; }    // where block q0's queries lie, as given
+};
+int query_feed_open(QueryFeed* f, ts_index* ix, const void* queries, int q_dtype, int q_on_device, int nq, bool f32copy, hipStream_t st);
+int query_feed_block(const QueryFeed& f, int q0, int nb);
 // search_mfma.hip: the matrix path (threshold sample, full pass, final select, re-run)
 int mfma_block_queries(const ts_index* ix, int nq);
 int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx, hipStream_t st, ts_search_stats* stats,

@@ -12,11 +12,7 @@ static inline bool rank_many_width(const ts_index* ix) {
 }
 
 static u64 host_key(float s, int64_t row) {
-    s = s + 0.0f;
-    u32 u;
-    memcpy(&u, &s, 4);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((u64)u << 32) | (u64)(0xFFFFFFFFu - (u32)row);
+    return ((u64)host_ord_f32(s) << 32) | (u64)(0xFFFFFFFFu - (u32)row);
 }
 
 template <bool F32, int RB, bool GATHER>
@@ -78,7 +74,8 @@ extern "C" int ts_rank_many(ts_index* ix, const void* queries, int q_dtype, int 
     hipStream_t st;
     StreamScope scope;
     TS_TRY(enter_stream(ix, stream, &st, &scope));
-    if (!ix->qstore) HIP_TRY(hipMalloc(&ix->qstore, (size_t)kQBlock * ix->ld * ix->elem()));
+    QueryFeed feed;
+    TS_TRY(query_feed_open(&feed, ix, queries, q_dtype, q_on_device, nq, false, st));
     constexpr int kSlots = kQBlock * kRankT;
     TS_TRY(ensure(&ix->rank_many_buf, &ix->rank_many_bytes, (size_t)kSlots * (8 + 8 + 4 + 4 + 4) + (size_t)kQBlock * 8));
     int64_t* d_grow = (int64_t*)ix->rank_many_buf;
@@ -89,8 +86,6 @@ extern "C" int ts_rank_many(ts_index* ix, const void* queries, int q_dtype, int 
     int* d_tcount = (int*)(d_counts + kSlots);
     float* d_tworst = (float*)(d_tcount + kQBlock);
 
-    const size_t q_elem = q_dtype == TS_BF16 ? 2 : 4;
-    if (!q_on_device) TS_TRY(ensure_stage(ix, (size_t)std::min(nq, kQBlock) * ix->d * q_elem, 0));
     std::vector<int64_t> grow(kSlots), tslot(kSlots);   // tslot: index of the slot's target in target_rows
     std::vector<int> gquery(kSlots), tcount(kQBlock);
     std::vector<float> gscore(kSlots), tworst(kQBlock);
@@ -104,13 +99,7 @@ extern "C" int ts_rank_many(ts_index* ix, const void* queries, int q_dtype, int 
         int64_t longest = 0;
         for (int i = 0; i < nb; ++i) longest = std::max(longest, target_offsets[q0 + i + 1] - target_offsets[q0 + i]);
         if (longest == 0) continue;
-        const void* qsrc = (const char*)queries + (size_t)q0 * ix->d * q_elem;
-        if (!q_on_device) {
-            HIP_TRY(hipMemcpyAsync(ix->stage, qsrc, (size_t)nb * ix->d * q_elem, hipMemcpyHostToDevice, st));
-            qsrc = ix->stage;
-        }
-        TS_TRY(prep_dispatch(q_dtype, ix->dtype, ix->metric == TS_METRIC_COS, qsrc, ix->d, ix->qstore, nullptr, ix->ld, ix->d, nb,
-                             kQBlock, st));
+        TS_TRY(query_feed_block(feed, q0, nb));
         // pass p: targets p * kRankT .. p * kRankT + kRankT - 1 of every query
         for (int64_t p0 = 0; p0 < longest; p0 += kRankT) {
             // 1. slots: the targets of this pass that are rows of this index
