@@ -2,10 +2,16 @@
 //
 // Replaces the per-call re-normalisation inside sentence_transformers.util.cos_sim (reference
 // call sites compare_embeddings.py:24,61, app_showcase_model.py:93): rows are normalised ONCE
-// when they enter the index, queries once per search.  Rule (same as oracle.l2_normalize):
+// when they enter the index, queries once per search.  Rule:
 //   norm  = (float) sqrt( sum_i (double)x_i^2 )       - fp64 accumulation, one rounding
-//   x_n   = x / max(norm, 1e-12f)                     - correctly rounded fp32 division
-// then, for a bf16 destination, round-to-nearest-even.
+//   x_n   = x / fmaxf(norm, 1e-12f)                   - correctly rounded fp32 division (taken in fp64, rounded once more)
+// then, for a bf16 destination, round-to-nearest-even (NaN stays NaN, quiet bit forced); a bf16 source is widened first.
+// On every row without a NaN this is oracle.l2_normalize (+ oracle.f32_to_bf16_bits) bit for bit, up to the order of the
+// fp64 sum, which is the wave's own (tests/test_prep_rows_gpu.py: rows whose sum is exact in any order, and Gaussian rows
+// whose fp32 norm no order can change).  A row that holds a NaN differs: F.normalize and the oracle make the whole row NaN;
+// here the norm is NaN, fmaxf returns 1e-12f, and the other entries become x / 1e-12f.  The NaN entries stay NaN, so the
+// row can never score either way; the tests assert that much for such rows and no more.  A row whose norm overflows to inf
+// becomes zeros (an Inf entry: NaN); without normalisation the values are stored as given (bf16: rounded).
 #pragma once
 #include "common.h"
 
