@@ -65,7 +65,12 @@ extern "C" {
 
 #define TS_ALGO_AUTO 0
 #define TS_ALGO_SCAN 1 /* streaming dot-product scan with per-wave running top-k (any dtype, any d) */
-#define TS_ALGO_MFMA 2 /* MFMA contraction with thresholded candidate selection (bf16 or fp32 index, d = 384, 512, 768 or 1024) */
+/* MFMA contraction with thresholded candidate selection, bf16 or fp32 index: d = 384, 512, 768 or 1024 on the hand-laid kernels;
+ * any other d that is a multiple of 64, from 128 up to a 4,096-byte row (bf16 d <= 2048, fp32 d <= 960), on the general-width
+ * kernel (256 queries per pass; only under the default two-level search, and for fp32 not with TS_MFMA_F32=0, which takes
+ * fp32 indexes off the matrix path at every width).  Other widths: TS_ERR_UNSUPPORTED.  Scores are reproducible per width and storage type: the
+ * same (query, row) pair gets the same score bits whatever the batch size and the launch shape. */
+#define TS_ALGO_MFMA 2
 
 #define TS_MAX_K 256
 
@@ -180,6 +185,12 @@ int ts_index_download(ts_index *ix, void *host_rows, int64_t row0, int64_t nrows
  * queries: [nq x d] dense, q_dtype TS_F32 or TS_BF16, in host (q_on_device = 0) or device memory.
  * With metric COS the queries are L2-normalised first; with a bf16 index they are rounded to bf16.
  * 1 <= k <= TS_MAX_K.
+ * A batch (more than 4 queries; when k > 64, where the scan serves one query per pass, more than 1 - more than 2 on the fp32
+ * general-width kernel: measured) over at least 16,384
+ * rows runs on the matrix path where the index has one: bf16 / fp32 at d = 384, 512, 768, 1024 (hand-laid kernels), and at
+ * every other multiple of 64 from 128 up to a 4,096-byte row (the general-width kernel); anything else on the streaming scan,
+ * four queries per pass.  Either way the answer is the exact top k; matrix-path scores are reproducible per width and storage
+ * type (the same score bits for a (query, row) pair in any batch) and may differ from the scan's in the last bits.
  */
 int ts_search(ts_index *ix, const void *queries, int q_dtype, int q_on_device, int32_t nq, int32_t k,
               float *out_scores, int64_t *out_idx, int out_on_device, void *stream);
@@ -223,7 +234,10 @@ int ts_search_filtered(ts_index *ix, const void *queries, int q_dtype, int q_on_
                        int out_on_device, void *stream);
 
 /* The same with an algorithm hint (TS_ALGO_SCAN is honoured; TS_ALGO_MFMA is refused with TS_ERR_UNSUPPORTED when the mask is
- * too sparse or lives on the device; TS_ALGO_AUTO decides by the mask's density) and the per-call counters. */
+ * too sparse or lives on the device, or the index has no matrix path - see TS_ALGO_MFMA for the widths served, hand-laid and
+ * general; TS_ALGO_AUTO decides by the mask's density) and the per-call counters.  On the matrix path the mask's bit is tested
+ * where a score passes the threshold, on the hand-laid and on the general-width kernel alike; scores are reproducible per
+ * width and storage type. */
 int ts_search_filtered_ex(ts_index *ix, const void *queries, int q_dtype, int q_on_device, int32_t nq, int32_t k,
                           const uint32_t *row_mask, int mask_on_device, float *out_scores, int64_t *out_idx,
                           int out_on_device, void *stream, int algo, ts_search_stats *stats);

@@ -21,6 +21,7 @@
 #include "../../include/tsearch.h"
 #include "common.h"
 #include "scan_plan.h"
+#include "anyd_plan.h"
 
 using namespace ts;
 
@@ -300,7 +301,14 @@ static inline bool mfma_dim(int d) { return d == 384 || d == 512 || d == 768 || 
 static inline bool two_level_search(const ts_index* ix) {
     return ix->knobs.get(K_MFMA_STAT, 1) != 0 && ix->knobs.get(K_MFMA_SAMPLE, 1) != 0;
 }
+// every other multiple of 64 from 128 up to a 4,096-byte row: the general-width kernel (kernels_mfma_anyd.h; anyd_plan.h holds the
+// rule), a full pass only, so the usual two-level search as for d = 384 / 512; rows must be unpadded (ld == d: d % 64 == 0)
+static inline bool anyd_index(const ts_index* ix) {
+    if (ix->dtype == TS_F32 && ix->knobs.get(K_MFMA_F32, 16) == 0) return false;
+    return ix->ld == ix->d && anyd_served(ix->dtype, ix->d, two_level_search(ix));
+}
 static inline bool mfma_index(const ts_index* ix) {
+    if (anyd_index(ix)) return true;
     if (ix->dtype == TS_BF16) return mfma_dim(ix->d);
     if (ix->knobs.get(K_MFMA_F32, 16) == 0) return false;
     return ix->d == 768 || ix->d == 1024 || ((ix->d == 384 || ix->d == 512) && two_level_search(ix));
@@ -312,6 +320,7 @@ static inline bool use_shape16(const ts_index* ix) {
     // d = 384 / 512 (round 3): the 16x16 kernel has the full pass only for these widths, so it serves them when the search
     // is the usual two-level one (dense threshold sample + full pass); the guaranteed chain (TS_MFMA_STAT=0) and the
     // list-form sample (TS_MFMA_SAMPLE=0) run the 32x32 kernel (bf16) - fp32 at these widths has no other matrix kernel
+    if (!mfma_dim(ix->d)) return false;                     // the general-width kernel is neither shape
     const bool narrow = ix->d == 384 || ix->d == 512;
     const bool two_level = two_level_search(ix);
     // fp32: the 16x16x4 form of the same kernel (10M x 768, 256 queries: 14.1 ms a pass against 14.8 ms of the 32x32x2
@@ -368,5 +377,7 @@ int screen_tile_pass_wide(ts_index* ix, int nb, int grid, int variant, hipStream
 // ... and those of fp32 indexes (launch_screen8_f32.hip): fp32 quantisers, screen_tile_pass, the fp32 rescore
 int screen_prepare_f32(ts_index* ix, const void* qmat, int nq_launch, hipStream_t st);
 int screen_full_pass_f32(ts_index* ix, int nb, int nq, int grid, int variant, hipStream_t st, const ts::MfmaArgs& a);
+// launch_mfma_anyd.hip: the full pass of an index the general-width kernel serves (anyd_index)
+int launch_pass_mfma_anyd(const ts_index* ix, int grid, hipStream_t st, const ts::MfmaArgs& a);
 int launch_pass_mfma32(int dev, int d, int groups, bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);
 int launch_pass_mfma32_f32(int dev, bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);

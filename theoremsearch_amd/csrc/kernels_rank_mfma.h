@@ -70,7 +70,8 @@ __global__ void __launch_bounds__(kRankThreads) rank_many_kernel(RankManyArgs a)
     const int r16 = lane & 15, kq = lane >> 4;
     const int row_bytes = a.ld * kElem;
     const int pitch = row_bytes + kRankRowPad;
-    const int steps = a.ld / kStepElems;                          // a multiple of 4 at every served width
+    const int steps = a.ld / kStepElems;                          // a multiple of 4 at every served width (rank_many.hip admits 384 / 512 / 768 / 1024 only;
+                                                                  // a width with steps % 4 == 2 needs the tail group of kernels_mfma_anyd.h)
     const int nblocks = (a.nq + 15) / 16;
 
     // this workgroup's tiles

@@ -28,7 +28,7 @@ namespace ts {
 struct SampleArgs {
     const void* corpus;       // [n_pad x ld] storage dtype
     int64_t n;                // real rows
-    int ld;                   // elements per row (multiple of 64, at most 1024)
+    int ld;                   // elements per row (multiple of 64, a row of at most 4,096 bytes: mfma_sample checks the LDS)
     int64_t ntiles;           // sample tiles; sample position p = 32 * tile + row
     int64_t tile_stride;      // sample tile j is global tile (j / run) * run * tile_stride + j % run
     int run;
@@ -96,7 +96,7 @@ __global__ void __launch_bounds__(256) sample_scores_kernel(SampleArgs a) {
         const int64_t gt = (a.run == 1) ? j * a.tile_stride : (j / a.run) * a.run * a.tile_stride + j % a.run;
         return gt * kTileRows + (p & 31);
     };
-    // the query fragments of the first segment (bf16: all of them up to d = 1024) are requested BEFORE the rows: they come
+    // the query fragments of the first segment (bf16: all of them up to d = 1024, half of them at d = 2048) are requested BEFORE the rows: they come
     // from L2 and do not depend on anything, so their round trip runs beside the rows' trip to HBM instead of behind it
     const int qrow = (int)blockIdx.y * 64 + wave * 16 + r16;      // this lane's query (B operand) and output column
     const unsigned char* brow = (const unsigned char*)a.q + ((int64_t)qrow * a.ld + (F32 ? 4 : 8) * kq) * kElem;
@@ -137,24 +137,28 @@ __global__ void __launch_bounds__(256) sample_scores_kernel(SampleArgs a) {
     f32x4 acc[RB];
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) acc[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // k in segments of at most kSeg k-steps (bf16: one segment up to d = 1024; fp32: two): a segment's query fragments
-    // are all requested before its first MFMA
+    // k in segments of at most kSeg k-steps (bf16: one segment up to d = 1024, two up to 2048; fp32: one up to d = 512, two up
+    // to 1024): a segment's query fragments are all requested before its first MFMA
     for (int s0 = 0; s0 < steps; s0 += kSeg) {
         if (s0 > 0) {
 #pragma unroll
             for (int s = 0; s < kSeg; ++s)
                 if (s0 + s < steps) bv[s] = *(const uint4*)(brow + (int64_t)(s0 + s) * 64);
         }
-        // groups of 4 k-steps (every served width is a multiple): the 4 RB fragment reads of a group are issued before
-        // its MFMAs, so the LDS latency is paid once per group, not once per MFMA
+        // groups of 4 k-steps: the 4 RB fragment reads of a group are issued before its MFMAs, so the LDS latency is paid once
+        // per group, not once per MFMA.  The step count is even (ld % 64 == 0) and a multiple of 4 at the hand-laid widths and
+        // on fp32; a bf16 width with ld % 128 == 64 ends in a group of TWO: the steps past the row end are never multiplied
+        // (their row fragment is the next row's bytes, their query fragment a register nobody wrote)
 #pragma unroll
         for (int g4 = 0; g4 < kSeg; g4 += 4) {
             if (s0 + g4 < steps) {
+                const bool full = F32 || s0 + g4 + 4 <= steps;
                 uint4 av[4][RB];
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
 #pragma unroll
-                    for (int rb = 0; rb < RB; ++rb) av[s][rb] = *(const uint4*)(arow[rb] + (s0 + g4 + s) * 64);
+                    for (int rb = 0; rb < RB; ++rb)
+                        if (s < 2 || full) av[s][rb] = *(const uint4*)(arow[rb] + (s0 + g4 + s) * 64);
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -165,8 +169,9 @@ __global__ void __launch_bounds__(256) sample_scores_kernel(SampleArgs a) {
 #pragma unroll
                             for (int i = 0; i < 4; ++i) acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i], bf[i], acc[rb], 0, 0, 0);
                         } else {
-                            acc[rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(reinterpret_cast<const bf16x8&>(av[s][rb]),
-                                                                              reinterpret_cast<const bf16x8&>(bv[g4 + s]), acc[rb], 0, 0, 0);
+                            if (s < 2 || full)
+                                acc[rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(reinterpret_cast<const bf16x8&>(av[s][rb]),
+                                                                                  reinterpret_cast<const bf16x8&>(bv[g4 + s]), acc[rb], 0, 0, 0);
                         }
                     }
             }

@@ -219,7 +219,8 @@ static int search_validate(const ts_index* ix, const void* queries, int q_dtype,
     if (k < 1 || k > TS_MAX_K) return fail(TS_ERR_INVALID, "k = %d outside [1, %d]", k, TS_MAX_K);
     if (algo < TS_ALGO_AUTO || algo > TS_ALGO_MFMA) return fail(TS_ERR_INVALID, "algo %d", algo);
     if (algo == TS_ALGO_MFMA && !(mfma_index(ix) && ix->n >= 1))
-        return fail(TS_ERR_UNSUPPORTED, "the MFMA path needs a bf16 or fp32 index with d = 384, 512, 768 or 1024");
+        return fail(TS_ERR_UNSUPPORTED, "the MFMA path needs a bf16 or fp32 index with d = 384, 512, 768 or 1024, or with any other multiple of 64 "
+                                        "from 128 up to a 4,096-byte row (bf16 d <= 2048, fp32 d <= 960) under the default two-level search");
     return TS_OK;
 }
 
@@ -256,7 +257,12 @@ static int search_choose(ts_index* ix, int algo, int nq, int k, const BiasSpec* 
     in.nq = nq;
     in.k = k;
     in.mfma_min_rows = ix->knobs.get(K_MFMA_MIN_ROWS, 16384);
-    in.scan_max_queries = ix->knobs.get(K_SCAN_MAX_QUERIES, 4);
+    // the general-width kernel's limit comes from its own measurement (anyd_plan.h)
+    const bool anyd = anyd_index(ix);
+    in.scan_max_queries = ix->knobs.get(K_SCAN_MAX_QUERIES, anyd ? anyd_scan_max_queries(ix->dtype) : 4);
+    // k > 64 on the fp32 general-width kernel: choose_algo() lets every batch of two through, the measured limit is two
+    // (anyd_scan_limit); the kernel is then not offered to AUTO.  TS_SCAN_MAX_QUERIES, when set, is the only limit.
+    if (anyd && algo == TS_ALGO_AUTO && !ix->knobs.set[K_SCAN_MAX_QUERIES] && nq <= anyd_scan_limit(ix->dtype, k)) in.mfma_ok = false;
     in.bias = bias != nullptr;
     in.subset = ix->id_map != nullptr;
     in.mask = row_mask != nullptr;

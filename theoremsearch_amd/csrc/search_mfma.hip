@@ -128,6 +128,7 @@ static bool mfma_screened(const ts_index* ix) {
 }
 
 int mfma_block_queries(const ts_index* ix, int nq) {
+    if (anyd_index(ix)) return kAnydQueries;
     if (mfma_pairs(ix, nq)) return 256;
     if (ix->dtype == TS_F32) {
         // screened (TS_MFMA_SCREEN_F32): the int8 kernel holds up to four blocks of 16 queries per wave at either width, so the
@@ -156,6 +157,7 @@ int mfma_block_queries(const ts_index* ix, int nq) {
 struct MfmaPlan {
     std::vector<Level> lv;      // threshold levels, sparsest first; the last one is the full pass
     int kk, variant;
+    bool anyd;                  // the general-width kernel (kernels_mfma_anyd.h): full pass only, shared lists only, no screen / pairs / balancing
     bool shape16, statistical, dense_sample, dense0;
     bool screen_diag, screen, screen_rider, ksplit_form, pair;
     int nq_launch, groups, nb16;
@@ -173,7 +175,8 @@ static MfmaPlan mfma_plan(const ts_index* ix, int nq, int k) {
     // lists + spill absorb the run-to-run spread of the candidate count, so no safety margin in the rank
     p.kk = std::max(k, ix->knobs.get(K_MFMA_MIN_RANK, 1));
     p.variant = ix->knobs.get(K_MFMA_VARIANT, 0);
-    p.shape16 = use_shape16(ix);
+    p.anyd = anyd_index(ix);
+    p.shape16 = use_shape16(ix);                          // (false for the general-width form, and with it screen, pair and balance)
     p.nq_launch = mfma_block_queries(ix, nq);
     p.groups = p.shape16 ? 0 : p.nq_launch / 128;
     // Threshold of the full pass: by default extrapolated from ONE unthresholded sample (Gaussian tail of the
@@ -242,7 +245,7 @@ static MfmaPlan mfma_plan(const ts_index* ix, int nq, int k) {
 // The per-handle scratch this plan needs: made on first use, re-made when the grid outgrows it.
 static int mfma_scratch(ts_index* ix, const MfmaPlan& p, hipStream_t st) {
     if (p.dense_sample && !ix->sample) HIP_TRY(hipMalloc((void**)&ix->sample, (size_t)kMfmaQ * kLevelSortMax * 4));
-    if (ix->priv_writers < 4 * p.grid) {
+    if (!p.anyd && ix->priv_writers < 4 * p.grid) {            // (the general-width pass writes the shared lists only)
         if (ix->priv) HIP_TRY(hipFree(ix->priv));
         if (ix->pcount) HIP_TRY(hipFree(ix->pcount));
         ix->priv = nullptr; ix->pcount = nullptr; ix->priv_writers = 0;
@@ -448,11 +451,13 @@ static int mfma_level(ts_index* ix, const MfmaPlan& p, size_t i, int nq, int k, 
     a.scr_tile = nullptr;
     a.scr_q = nullptr;
 #ifdef TS_DIAG
-    if (variant_gets_dbg(p.variant)) a.dbg = ix->dbg;
+    if (variant_gets_dbg(p.variant) && !p.anyd) a.dbg = ix->dbg;
 #endif
+    if (p.anyd && !full_pass) return fail(TS_ERR_INTERNAL, "the general-width matrix kernel has no sparse level");
     hipEvent_t stop = full_pass ? prof_begin(ix, st, ix->n) : nullptr;  // only the full pass is bracketed
     int rc;
-    if (p.screen && full_pass) rc = screen_full_pass(ix, p.nb16, nq, p.grid, p.screen_diag ? p.variant : kVariantProduct, p.ksplit_form, st, a);
+    if (p.anyd) rc = launch_pass_mfma_anyd(ix, p.grid, st, a);
+    else if (p.screen && full_pass) rc = screen_full_pass(ix, p.nb16, nq, p.grid, p.screen_diag ? p.variant : kVariantProduct, p.ksplit_form, st, a);
     else if (ix->dtype == TS_F32 && p.shape16) rc = launch_pass_mfma16_f32(ix->device, ix->d, p.nb16, full_pass, p.grid, st, a);
     else if (ix->dtype == TS_F32) rc = launch_pass_mfma32_f32(ix->device, full_pass, p.variant, p.grid, st, a);
     else if (p.shape16) rc = launch_pass_mfma16(ix->device, ix->d, p.nb16, full_pass, p.variant, p.grid, st, a);
@@ -466,7 +471,8 @@ static int mfma_level(ts_index* ix, const MfmaPlan& p, size_t i, int nq, int k, 
     memset(&l, 0, sizeof(l));
     l.priv = ix->priv;
     l.pcount = ix->pcount;
-    l.nwriters = (p.shape16 && full_pass) ? 0 : p.nwriters;   // the 16x16 full pass stages its candidates in LDS: shared lists only
+    // the 16x16 full pass stages its candidates in LDS, the general-width one appends them directly: shared lists only
+    l.nwriters = ((p.shape16 || p.anyd) && full_pass) ? 0 : p.nwriters;
     l.priv_cap = p.priv_cap;
     l.cand = ix->cand;
     l.count = ix->count;
