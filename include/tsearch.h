@@ -256,6 +256,29 @@ int ts_search_biased(ts_index *ix, const void *queries, int q_dtype, int q_on_de
                      const float *bias, int bias_on_device, float weight, const uint32_t *row_mask, int mask_on_device,
                      float *out_scores, float *out_sims, int64_t *out_idx, int out_on_device, void *stream);
 
+/* The same ranking with an algorithm hint and the per-call counters: the batched form (a page of queries, an evaluation set).
+ * The answer is the exact weighted top k whatever the path.
+ *   TS_ALGO_SCAN  what ts_search_biased runs, bit for bit.
+ *   TS_ALGO_MFMA  the biased matrix search: a dense threshold sample, then ONE pass of the general-width matrix kernel per 256
+ *                 queries with fmaf(weight, bias[row], score) in its epilogue - that value is tested against the query's
+ *                 threshold, written into the key and returned.  Served: a bf16 or fp32 index whose width is a multiple of 64
+ *                 from 128 up to a 4,096-byte row (bf16 d <= 2048, fp32 d <= 1024; 384 / 512 / 768 / 1024 included).
+ *                 TS_ERR_UNSUPPORTED for a subset index, any other width, without the two-level search (TS_MFMA_STAT=0 or
+ *                 TS_MFMA_SAMPLE=0), an fp32 index with TS_MFMA_F32=0, a mask in device memory, or a host mask too sparse by
+ *                 the rule of ts_search_filtered_ex (fewer than a tenth of the rows, or a batch the matrix path does not take).
+ *   TS_ALGO_AUTO  the matrix search for more than 4 queries (fp32 indexes: more than 8; k > 64: more than 1) over at least
+ *                 TS_MFMA_MIN_ROWS rows where it is served, else the scan (measured: DESIGN.md section 3.4).
+ * The threshold is an estimate from the sample (Gaussian similarities plus the KNOWN additive term); a
+ * query that gets fewer than min(k, allowed rows) candidates back is re-run exactly on the scan kernel, so the estimate can
+ * cost time, never an answer.  Matrix-path scores are reproducible per width and storage type: the same bits for a (query,
+ * row) pair in any batch or grid; they may differ from the scan's in the last bits, and re-run queries carry the scan's
+ * arithmetic.  stats as for ts_search_ex: algo, levels (2; 1 on an index so small that the pass runs unthresholded),
+ * fallback_queries (re-run queries), candidates, screened = 0. */
+int ts_search_biased_ex(ts_index *ix, const void *queries, int q_dtype, int q_on_device, int32_t nq, int32_t k,
+                        const float *bias, int bias_on_device, float weight, const uint32_t *row_mask, int mask_on_device,
+                        float *out_scores, float *out_sims, int64_t *out_idx, int out_on_device, void *stream, int algo,
+                        ts_search_stats *stats);
+
 /* Rank of one given row per query in the canonical order of that query's scores over the whole index (0 = best):
  * the number of rows whose (score, -row) beats the target's.  One streaming pass that counts; replaces ranking the
  * full [nq x N] matrix and looking the relevant document up - np.argsort(-sim_matrix) followed by the position of

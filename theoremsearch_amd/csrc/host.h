@@ -22,6 +22,7 @@
 #include "common.h"
 #include "scan_plan.h"
 #include "anyd_plan.h"
+#include "bias_plan.h"
 
 using namespace ts;
 
@@ -150,7 +151,9 @@ struct ts_index {
     float* res_scores = nullptr; int64_t* res_idx = nullptr; size_t res_cap = 0;  // device result buffers (entries)
     u32* mask_dev = nullptr;    size_t mask_bytes = 0;       // filtered search: device copy of a host bitmask
     float* bias_dev = nullptr;  size_t bias_bytes = 0;       // biased search: device copy of a host bias array
+    u32* bias_hist = nullptr;                                // biased matrix search: histogram of w * bias over the call's rows + its range (kernels_sample_biased.h)
     const float* active_bias = nullptr; float active_bias_w = 0.f;   // per-row additive term of the search in progress (under `mu`)
+    bool active_bias_matrix = false;                         // ... which runs on the matrix path (ts_search_biased_ex): the biased general-width pass
     int64_t* id_map = nullptr;                               // subset index: local row -> global id
     bool borrowed = false;                                   // a view: rows / id_map belong to another handle
     bool attached = false;                                   // rows adopted from the caller (ts_index_attach_device): never freed here
@@ -307,6 +310,11 @@ static inline bool anyd_index(const ts_index* ix) {
     if (ix->dtype == TS_F32 && ix->knobs.get(K_MFMA_F32, 16) == 0) return false;
     return ix->ld == ix->d && anyd_served(ix->dtype, ix->d, two_level_search(ix));
 }
+// the biased matrix search (bias_plan.h: bias_served): the general-width rule with the hand-laid widths included
+static inline bool bias_index(const ts_index* ix) {
+    if (ix->dtype == TS_F32 && ix->knobs.get(K_MFMA_F32, 16) == 0) return false;
+    return ix->ld == ix->d && ix->n >= 1 && bias_served(ix->dtype, ix->d, two_level_search(ix));
+}
 static inline bool mfma_index(const ts_index* ix) {
     if (anyd_index(ix)) return true;
     if (ix->dtype == TS_BF16) return mfma_dim(ix->d);
@@ -357,6 +365,8 @@ int query_feed_open(QueryFeed* f, ts_index* ix, const void* queries, int q_dtype
 int query_feed_block(const QueryFeed& f, int q0, int nb);
 // search_mfma.hip: the matrix path (threshold sample, full pass, final select, re-run)
 int mfma_block_queries(const ts_index* ix, int nq);
+// ... the histogram of the call's additive term over all (allowed) rows, once per biased matrix search (ix->active_bias, active_mask)
+int bias_histogram(ts_index* ix, hipStream_t st);
 int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx, hipStream_t st, ts_search_stats* stats,
                 const void* qmat, bool in_place);
 // launch_mfma16.hip / launch_mfma16_f32.hip / launch_mfma32.hip: one launch of a matrix kernel (a full pass or a sparse level)
@@ -379,5 +389,8 @@ int screen_prepare_f32(ts_index* ix, const void* qmat, int nq_launch, hipStream_
 int screen_full_pass_f32(ts_index* ix, int nb, int nq, int grid, int variant, hipStream_t st, const ts::MfmaArgs& a);
 // launch_mfma_anyd.hip: the full pass of an index the general-width kernel serves (anyd_index)
 int launch_pass_mfma_anyd(const ts_index* ix, int grid, hipStream_t st, const ts::MfmaArgs& a);
+// launch_mfma_anyd_biased.hip: the same pass with the call's bias term in the epilogue (ix->active_bias, active_bias_w), at any
+// width of bias_index
+int launch_pass_mfma_anyd_biased(const ts_index* ix, int grid, hipStream_t st, const ts::MfmaArgs& a);
 int launch_pass_mfma32(int dev, int d, int groups, bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);
 int launch_pass_mfma32_f32(int dev, bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);

@@ -121,7 +121,7 @@ extern "C" int ts_index_destroy(ts_index* ix) {
         if (ix->parent) ix->parent->nviews.fetch_sub(1);
     }
     if (ix->attached) ix->rows = nullptr;
-    void* ptrs[] = {ix->rows,  ix->stage,   ix->qstore,   ix->qf32,     ix->cand,       ix->count,  ix->thr, ix->priv, ix->pcount, ix->sample, ix->mask_dev, ix->bias_dev, ix->rank_buf, ix->rank_many_buf, ix->id_map,
+    void* ptrs[] = {ix->rows,  ix->stage,   ix->qstore,   ix->qf32,     ix->cand,       ix->count,  ix->thr, ix->priv, ix->pcount, ix->sample, ix->mask_dev, ix->bias_dev, ix->bias_hist, ix->rank_buf, ix->rank_many_buf, ix->id_map,
                     ix->fb_list, ix->fb_count, ix->stat, ix->partial, ix->partial2, ix->res_scores, ix->res_idx, ix->dbg, ix->part, ix->wg_ticks, ix->pair_pos,
                     ix->scr_rows, ix->scr_tile, ix->scr_q, ix->scr_qmeta, ix->scr_cand, ix->scr_count};
     for (void* p : ptrs)

@@ -185,9 +185,11 @@ inline bool mask_wants_count(const AlgoInputs& in) {
 inline AlgoChoice choose_algo(const AlgoInputs& in) {
     int algo = in.algo;
     if (in.bias) {
-        // the additive term is applied where the row is known and the key is made: the scan kernel (four queries per pass at
-        // the HBM rate).  The matrix kernels test a whole accumulator tile against one threshold per query; a per-row term
-        // of the size of w * ln(citations) (several standard deviations of the scores) leaves no threshold that prunes.
+        // ts_search_biased: the additive term is applied where the row is known and the key is made, in the scan kernel
+        // (four queries per pass at the HBM rate).  A threshold that prunes exists - not the Gaussian estimate of the
+        // weighted scores (a per-row term of the size of w * ln(citations), several standard deviations of the scores, is
+        // not Gaussian), but one that models the similarities and the known term apart: ts_search_biased_ex runs the
+        // general-width matrix pass behind it and decides with choose_bias_algo (bias_plan.h), not here.
         if (in.subset) return {0, "biased search on a subset index"};
         if (algo == TS_ALGO_MFMA) return {0, "the biased search runs on the scan kernel"};
         algo = TS_ALGO_SCAN;

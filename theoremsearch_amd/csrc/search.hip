@@ -208,6 +208,7 @@ struct BiasSpec {       // ts_search_biased: rank by score + weight * bias[row]
     int on_device = 0;
     float weight = 0.f;
     float* out_sims = nullptr;   // optional: raw similarities of the results, where the scores go
+    bool ex = false;             // ts_search_biased_ex: the call may run on the matrix path (bias_plan.h decides)
 };
 
 // ---- search_impl's stages -------------------------------------------------------------------------------------------------
@@ -268,6 +269,18 @@ static int search_choose(ts_index* ix, int algo, int nq, int k, const BiasSpec* 
     in.mask = row_mask != nullptr;
     in.mask_on_device = mask_on_device != 0;
     in.allowed = 0;
+    if (bias && bias->ex) {
+        // ts_search_biased_ex decides with its own rule (bias_plan.h): the biased general-width pass serves the hand-laid
+        // widths too, and its AUTO limit is its own
+        const bool served = bias_index(ix);
+        in.scan_max_queries = ix->knobs.get(K_SCAN_MAX_QUERIES, bias_scan_max_queries(ix->dtype));
+        if (mask_wants_count(bias_algo_inputs(in, served))) ix->active_allowed = in.allowed = count_allowed_rows(row_mask, ix->n);
+        const AlgoChoice c = choose_bias_algo(in, served);
+        if (c.unsupported) return fail(TS_ERR_UNSUPPORTED, "%s", c.unsupported);
+        *use = c.algo;
+        ix->active_bias_matrix = c.algo == TS_ALGO_MFMA;
+        return TS_OK;
+    }
     if (mask_wants_count(in)) ix->active_allowed = in.allowed = count_allowed_rows(row_mask, ix->n);
     const AlgoChoice c = choose_algo(in);
     if (c.unsupported) return fail(TS_ERR_UNSUPPORTED, "%s", c.unsupported);
@@ -384,7 +397,7 @@ static int search_impl(ts_index* ix, const void* queries, int q_dtype, int q_on_
     TS_TRY(ensure_search_scratch(ix, k));
     struct MaskScope {  // the bitmask and the bias are properties of this call only
         ts_index* ix;
-        ~MaskScope() { ix->active_mask = nullptr; ix->active_bias = nullptr; }
+        ~MaskScope() { ix->active_mask = nullptr; ix->active_bias = nullptr; ix->active_bias_matrix = false; }
     } mask_scope{ix};
     if (bias) TS_TRY(install_bias(ix, *bias, st));
     if (row_mask) TS_TRY(install_mask(ix, row_mask, mask_on_device, st));
@@ -397,6 +410,7 @@ static int search_impl(ts_index* ix, const void* queries, int q_dtype, int q_on_
     TS_TRY(result_buffers(ix, (size_t)nq * k, out_on_device, &dscores, &didx));
     QueryFeed feed;
     TS_TRY(query_feed_open(&feed, ix, queries, q_dtype, q_on_device, nq, true, st));
+    if (ix->active_bias_matrix) TS_TRY(bias_histogram(ix, st));
     const int block = (use == TS_ALGO_MFMA) ? mfma_block_queries(ix, nq) : kQBlock;
     TS_TRY(search_blocks(ix, feed, use, block, nq, k, dscores, didx, stats));
     DevBuf sims_tmp;
@@ -444,6 +458,22 @@ extern "C" int ts_search_biased(ts_index* ix, const void* queries, int q_dtype, 
     b.out_sims = out_sims;
     return search_impl(ix, queries, q_dtype, q_on_device, nq, k, out_scores, out_idx, out_on_device, stream, TS_ALGO_AUTO, nullptr,
                        row_mask, mask_on_device, &b);
+}
+
+extern "C" int ts_search_biased_ex(ts_index* ix, const void* queries, int q_dtype, int q_on_device, int32_t nq, int32_t k,
+                                   const float* bias, int bias_on_device, float weight, const uint32_t* row_mask, int mask_on_device,
+                                   float* out_scores, float* out_sims, int64_t* out_idx, int out_on_device, void* stream, int algo,
+                                   ts_search_stats* stats) {
+    if (!bias) return fail(TS_ERR_INVALID, "bias is NULL");
+    if (!(weight == weight) || std::isinf(weight)) return fail(TS_ERR_INVALID, "weight must be finite");
+    BiasSpec b;
+    b.bias = bias;
+    b.on_device = bias_on_device;
+    b.weight = weight;
+    b.out_sims = out_sims;
+    b.ex = true;
+    return search_impl(ix, queries, q_dtype, q_on_device, nq, k, out_scores, out_idx, out_on_device, stream, algo, stats, row_mask,
+                       mask_on_device, &b);
 }
 
 template <int DT, int CH, int G>

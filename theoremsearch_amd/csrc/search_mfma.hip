@@ -1,13 +1,15 @@
 // The matrix path of a search: planning of the threshold levels, the dense threshold sample and its
 // select, the full pass (launch_mfma*.hip hold the kernel instantiations), the final select, the exact re-run.
 // mfma_search runs the stages in order: mfma_plan (what this search is), mfma_scratch (the handle's buffers), then per level
-// mfma_sample (level 0 as the dense sample) or mfma_level (a matrix kernel + its select).
+// mfma_sample (level 0 as the dense sample) or mfma_level (a matrix kernel + its select).  A biased search (ts_search_biased_ex)
+// is the general-width form of all this at any served width, with its own sample select (kernels_sample_biased.h).
 #include "host.h"
 #include "kernels_mfma.h"
 #include "kernels_mfma16.h"
 #include "mfma16_variants.h"
 #include "kernels_mfma_f32.h"
 #include "kernels_sample.h"
+#include "kernels_sample_biased.h"
 #include "kernels_select.h"
 
 struct Level { int64_t stride, ntiles; int run; };
@@ -106,8 +108,12 @@ static std::vector<Level> plan_levels(const Knobs& kn, int64_t n, int kk, bool s
 // pair's second read of a tile is served by the XCD's L2 / the memory-side cache) instead of once per 128 queries.
 constexpr int kMfmaMaxGrid = 2048;   // workgroups of one pass (TS_MFMA_GRID is clamped to it; the pairs' position words are sized by it)
 static int mfma_grid(const ts_index* ix) { return std::max(1, std::min(ix->knobs.get(K_MFMA_GRID, ix->cu_count), kMfmaMaxGrid)); }
+// The search in progress is a biased one on the matrix path: whatever the width, its pass is the general-width kernel (256
+// queries per launch, full pass only, shared lists only; no screen, pairs, balancing or private lists).
+static bool biased_search(const ts_index* ix) { return ix->active_bias_matrix; }
+static bool general_width(const ts_index* ix) { return anyd_index(ix) || biased_search(ix); }
 static bool mfma_pairs(const ts_index* ix, int nq) {
-    return ix->dtype == TS_BF16 && ix->d == 1024 && nq > 192 && use_shape16(ix) && two_level_search(ix) &&
+    return !biased_search(ix) && ix->dtype == TS_BF16 && ix->d == 1024 && nq > 192 && use_shape16(ix) && two_level_search(ix) &&
            ix->knobs.get(K_MFMA_PAIR, 1) != 0 && mfma_grid(ix) % 16 == 0;
 }
 
@@ -124,11 +130,11 @@ static bool screen_diag_variant(int variant) {
 // pass (mfma_plan) and for the queries a launch holds (mfma_block_queries).
 static bool mfma_screened(const ts_index* ix) {
     const int variant = ix->knobs.get(K_MFMA_VARIANT, 0);
-    return use_shape16(ix) && (variant == kVariantProduct || screen_diag_variant(variant)) && thresholded_pass(ix) && screen_usable(ix);
+    return !biased_search(ix) && use_shape16(ix) && (variant == kVariantProduct || screen_diag_variant(variant)) && thresholded_pass(ix) && screen_usable(ix);
 }
 
 int mfma_block_queries(const ts_index* ix, int nq) {
-    if (anyd_index(ix)) return kAnydQueries;
+    if (general_width(ix)) return kAnydQueries;
     if (mfma_pairs(ix, nq)) return 256;
     if (ix->dtype == TS_F32) {
         // screened (TS_MFMA_SCREEN_F32): the int8 kernel holds up to four blocks of 16 queries per wave at either width, so the
@@ -152,12 +158,32 @@ int mfma_block_queries(const ts_index* ix, int nq) {
     return nq <= 128 && ix->knobs.get(K_MFMA_GROUPS, 0) != 2 ? 128 : 256;
 }
 
+// Once per biased matrix search, before its first block of queries: the histogram of w * bias[row] over every row the call may
+// return (kernels_sample_biased.h) - two short passes over the bias array and the mask, n * 4 bytes each.
+int bias_histogram(ts_index* ix, hipStream_t st) {
+    if (!ix->bias_hist) HIP_TRY(hipMalloc((void**)&ix->bias_hist, (size_t)kBiasHistWords * 4));
+    HIP_TRY(hipMemsetAsync(ix->bias_hist, 0, (size_t)kBiasHistWords * 4, st));
+    BiasHistArgs a;
+    a.bias = ix->active_bias;
+    a.w = ix->active_bias_w;
+    a.n = ix->n;
+    a.row_mask = ix->active_mask;
+    a.out = ix->bias_hist;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)ix->cu_count * 4, (ix->n + 255) / 256));
+    bias_range_kernel<<<grid, 256, 0, st>>>(a);
+    HIP_TRY(hipGetLastError());
+    bias_hist_kernel<<<grid, 256, 0, st>>>(a);
+    HIP_TRY(hipGetLastError());
+    return TS_OK;
+}
+
 // What one search of `nq` queries for `k` results on this handle is: every decision, made once (mfma_plan) and read by the
 // stages below.
 struct MfmaPlan {
     std::vector<Level> lv;      // threshold levels, sparsest first; the last one is the full pass
     int kk, variant;
     bool anyd;                  // the general-width kernel (kernels_mfma_anyd.h): full pass only, shared lists only, no screen / pairs / balancing
+    bool biased;                // ... with the call's bias term in its epilogue, and the biased sample select (any served width)
     bool shape16, statistical, dense_sample, dense0;
     bool screen_diag, screen, screen_rider, ksplit_form, pair;
     int nq_launch, groups, nb16;
@@ -175,8 +201,9 @@ static MfmaPlan mfma_plan(const ts_index* ix, int nq, int k) {
     // lists + spill absorb the run-to-run spread of the candidate count, so no safety margin in the rank
     p.kk = std::max(k, ix->knobs.get(K_MFMA_MIN_RANK, 1));
     p.variant = ix->knobs.get(K_MFMA_VARIANT, 0);
-    p.anyd = anyd_index(ix);
-    p.shape16 = use_shape16(ix);                          // (false for the general-width form, and with it screen, pair and balance)
+    p.biased = biased_search(ix);
+    p.anyd = general_width(ix);
+    p.shape16 = !p.anyd && use_shape16(ix);               // (false for the general-width form, and with it screen, pair and balance)
     p.nq_launch = mfma_block_queries(ix, nq);
     p.groups = p.shape16 ? 0 : p.nq_launch / 128;
     // Threshold of the full pass: by default extrapolated from ONE unthresholded sample (Gaussian tail of the
@@ -342,6 +369,25 @@ static int mfma_sample(ts_index* ix, const MfmaPlan& p, int nq, const void* qmat
     const int kl = p.tail_p > 0.0f ? std::max(p.kk, 32) : p.kk;
     const double live = p.sample_rows * (double)p.pop / (double)std::max<int64_t>(ix->n, 1);
     const float z_sel = (float)normal_tail_z(std::min(0.25, 2.0 * kl / std::max(live, 1.0)));
+    if (p.biased) {
+        // the weighted scores are not Gaussian: the select models the similarities and the known term apart (bias_plan.h)
+        BiasSelectArgs b;
+        memset(&b, 0, sizeof(b));
+        b.scores = ix->sample;
+        b.row_stride = sa.row_stride;
+        b.ntiles = lv0.ntiles;
+        b.tile_stride = lv0.stride;
+        b.run = lv0.run;
+        b.bias = ix->active_bias;
+        b.w = ix->active_bias_w;
+        b.kk = p.kk;
+        b.ghist = ix->bias_hist;
+        b.target = (double)p.stat_cands;
+        b.thr = ix->thr;
+        b.count = ix->count;
+        if (p.kk <= 64) return launch_lds<sample_select_biased_kernel<1>>(ix->device, nq, kLevelThreads, kBiasSelectLds, st, b);
+        return launch_lds<sample_select_biased_kernel<4>>(ix->device, nq, kLevelThreads, kBiasSelectLds, st, b);
+    }
     sample_select_fast_kernel<kSelThreads><<<nq, kSelThreads, 0, st>>>(l, ix->sample, sa.row_stride, z_sel);
     HIP_TRY(hipGetLastError());
     return TS_OK;
@@ -456,7 +502,8 @@ static int mfma_level(ts_index* ix, const MfmaPlan& p, size_t i, int nq, int k, 
     if (p.anyd && !full_pass) return fail(TS_ERR_INTERNAL, "the general-width matrix kernel has no sparse level");
     hipEvent_t stop = full_pass ? prof_begin(ix, st, ix->n) : nullptr;  // only the full pass is bracketed
     int rc;
-    if (p.anyd) rc = launch_pass_mfma_anyd(ix, p.grid, st, a);
+    if (p.biased) rc = launch_pass_mfma_anyd_biased(ix, p.grid, st, a);
+    else if (p.anyd) rc = launch_pass_mfma_anyd(ix, p.grid, st, a);
     else if (p.screen && full_pass) rc = screen_full_pass(ix, p.nb16, nq, p.grid, p.screen_diag ? p.variant : kVariantProduct, p.ksplit_form, st, a);
     else if (ix->dtype == TS_F32 && p.shape16) rc = launch_pass_mfma16_f32(ix->device, ix->d, p.nb16, full_pass, p.grid, st, a);
     else if (ix->dtype == TS_F32) rc = launch_pass_mfma32_f32(ix->device, full_pass, p.variant, p.grid, st, a);

@@ -261,10 +261,14 @@ class TheoremIndex:
                                           C.c_void_p(out_scores_ptr), C.c_void_p(out_idx_ptr), 1,
                                           C.c_void_p(stream), _ALGOS[algo], None))
 
-    def search_biased(self, queries, k: int, bias, weight: float, mask=None):
+    def search_biased(self, queries, k: int, bias, weight: float, mask=None, algo: Optional[str] = None,
+                      return_stats: bool = False):
         """Top-k of ``score + weight * bias[row]`` over all rows (all rows ``mask`` allows): the citation-weighted
         ranking of streamlit_app.py:348-364 without its candidate pool.  ``bias``: float32 per row of this index.
-        Returns ``(weighted scores, raw similarities, indices)``, each ``[nq x k]``."""
+        Returns ``(weighted scores, raw similarities, indices)``, each ``[nq x k]``.
+        ``algo=None`` is ``ts_search_biased`` (the scan); ``"scan" | "mfma" | "auto"`` go through ``ts_search_biased_ex``:
+        ``"mfma"`` is the batched matrix search (one corpus pass per 256 queries; refused where it is not served),
+        ``"auto"`` takes it for a batch of more than 4 queries (an fp32 index: more than 8).  ``return_stats`` appends the call's counters."""
         q = _host_rows(queries)
         if q.shape[1] != self.d:
             raise ValueError(f"queries have d={q.shape[1]}, index has d={self.d}")
@@ -283,10 +287,33 @@ class TheoremIndex:
             bits = np.packbits(m, bitorder="little")
             words = np.zeros((self.n + 31) // 32 * 4, dtype=np.uint8)
             words[: bits.shape[0]] = bits
-        _ffi.check(self._lib.ts_search_biased(self._h, _ffi.as_ptr(q), _ffi.np_dtype_code(q), 0, nq, k, _ffi.as_ptr(b), 0,
-                                              float(weight), _ffi.as_ptr(words) if words is not None else None, 0,
-                                              _ffi.as_ptr(scores), _ffi.as_ptr(sims), _ffi.as_ptr(idx), 0, None))
+        if algo is None:
+            _ffi.check(self._lib.ts_search_biased(self._h, _ffi.as_ptr(q), _ffi.np_dtype_code(q), 0, nq, k, _ffi.as_ptr(b), 0,
+                                                  float(weight), _ffi.as_ptr(words) if words is not None else None, 0,
+                                                  _ffi.as_ptr(scores), _ffi.as_ptr(sims), _ffi.as_ptr(idx), 0, None))
+            stats = _ffi.SearchStats()
+            stats.algo = _ffi.TS_ALGO_SCAN
+        else:
+            stats = _ffi.SearchStats()
+            _ffi.check(self._lib.ts_search_biased_ex(self._h, _ffi.as_ptr(q), _ffi.np_dtype_code(q), 0, nq, k, _ffi.as_ptr(b), 0,
+                                                     float(weight), _ffi.as_ptr(words) if words is not None else None, 0,
+                                                     _ffi.as_ptr(scores), _ffi.as_ptr(sims), _ffi.as_ptr(idx), 0, None,
+                                                     _ALGOS[algo], C.byref(stats)))
+        if return_stats:
+            return scores, sims, idx, {"algo": stats.algo, "levels": stats.levels, "fallback_queries": stats.fallback_queries,
+                                       "candidates": stats.candidates, "screened": stats.screened}
         return scores, sims, idx
+
+    def search_biased_device(self, q_ptr: int, q_dtype: str, nq: int, k: int, bias_ptr: int, weight: float, out_scores_ptr: int,
+                             out_sims_ptr: int, out_idx_ptr: int, stream: int = 0, algo: str = "auto") -> None:
+        """Asynchronous `search_biased` on device buffers (queries [nq x d]; bias float32 [n]; outputs [nq x k] f32 / f32 /
+        i64; ``out_sims_ptr`` may be 0), enqueued on ``stream`` (0 = the index's own).  Always ``ts_search_biased_ex``:
+        ``algo`` defaults to ``"auto"`` as in `search_device` - unlike `search_biased`, whose default ``None`` is the scan.
+        Queries of the matrix path's own form are read in place, as by `search_device`."""
+        _ffi.check(self._lib.ts_search_biased_ex(self._h, C.c_void_p(q_ptr), _DTYPES[q_dtype], 1, int(nq), int(k),
+                                                 C.c_void_p(bias_ptr), 1, float(weight), None, 0, C.c_void_p(out_scores_ptr),
+                                                 C.c_void_p(out_sims_ptr) if out_sims_ptr else None, C.c_void_p(out_idx_ptr), 1,
+                                                 C.c_void_p(stream), _ALGOS[algo], None))
 
     def rank_of(self, queries, rows) -> Tuple[np.ndarray, np.ndarray]:
         """0-based rank of ``rows[i]`` among all index rows for query ``i`` (score descending, index ascending)

@@ -129,3 +129,28 @@ def search(index: TheoremIndex, query_vec, top_k: int, citation_weight: float = 
         rows.append({"row": int(i), "similarity": sim, "score": sim + citation_weight * bonus})
     rows.sort(key=lambda r: (-r["score"], -r["similarity"]))
     return rows[: int(top_k)]
+
+
+def search_batch(index: TheoremIndex, query_vecs, top_k: int, citation_weight: float,
+                 citations: Optional[Sequence[Optional[int]]] = None, bias=None, mask=None):
+    """`search` with ``exact=True`` for many queries at once: every (allowed) row ranked by the weighted score, one corpus
+    pass per 256 queries where the index has the biased matrix search (``ts_search_biased_ex`` on ``auto``), the scan
+    otherwise.  Returns one list per query, each shaped like the result of ``search(..., exact=True)``."""
+    q = np.asarray(query_vecs, dtype=np.float32)
+    q = q.reshape(1, -1) if q.ndim == 1 else q
+    if citations is None and bias is None:
+        raise ValueError("citation-weighted search needs the per-row citation counts")
+    b = citation_bias(citations) if bias is None else np.asarray(bias, dtype=np.float32)
+    _, sims, idx = index.search_biased(q, int(top_k), b, float(citation_weight), mask=mask, algo="auto")
+    out = []
+    for srow, irow in zip(sims, idx):
+        rows = []
+        for s, i in zip(srow, irow):
+            if i < 0:
+                continue
+            sim = 1.0 + float(s)
+            rows.append({"row": int(i), "similarity": sim,
+                         "score": sim + citation_weight * float(b[int(i) - index.row_offset])})
+        rows.sort(key=lambda r: (-r["score"], -r["similarity"]))
+        out.append(rows)
+    return out
