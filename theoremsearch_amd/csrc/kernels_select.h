@@ -5,6 +5,22 @@
 // compare_embeddings.py:52), torch.topk(scores, k, sorted=True) (app_showcase_model.py:96) and
 // Postgres' top-N heapsort behind ORDER BY ... LIMIT k (streamlit_app.py:282-283).  Order rule:
 // score descending, then row ascending (unsigned order of the 64-bit keys, common.h).
+//
+// Rules that tests/threshold_common.py (a numpy model of level_threshold and of the plan in search_mfma.hip) and
+// tests/test_final_select_gpu.py hold this file to - on lattice corpora, where every score is exact, the candidate count
+// of a search pins each of them:
+//   * a threshold is max(k-th best of the live sample scores (-inf below k of them), float(mean + z_tail sd) from 256
+//     live scores on, the tail fit from 1,024 on); mean and sd are the population's, in fp64, over LIVE scores only - a
+//     masked row, a NaN row and a position past the sample carry none.  sd = 0 makes the estimate the score itself.
+//   * the tail fit extrapolates only beyond the sample's 32nd best: ratio = (32 / cnt) / tail_p > 1, that is more than
+//     64 allowed rows per live sample row - a sample stride above 64, from 262,145 rows on with the default 4,096-row
+//     sample.  Armed below that (k n / sample > 4096) it never moves a threshold.
+//   * the final level's count is every row at or above the threshold, kept or lost: above cap (8192) or below
+//     min(k, allowed rows) the query re-runs exactly.  NaN rows are never candidates, so k above the number of rows WITH
+//     a score re-runs by design: the select cannot tell "three rows have no score" from "the threshold lost three rows".
+//   * every path - one wave (<= kFinalFast candidates, k <= kFinalFast, shared list only), direct sort (<= kLevelSmall),
+//     histogram cut, streaming (more than kLevelSmall keys in the cut bin: piles of equal scores, sd = 0) - returns the same
+//     keys in the same order; which one ran shows in timing only.
 #pragma once
 #include <math.h>
 

@@ -3,6 +3,13 @@
 // mfma_search runs the stages in order: mfma_plan (what this search is), mfma_scratch (the handle's buffers), then per level
 // mfma_sample (level 0 as the dense sample) or mfma_level (a matrix kernel + its select).  A biased search (ts_search_biased_ex)
 // is the general-width form of all this at any served width, with its own sample select (kernels_sample_biased.h).
+//
+// What the plan fixes, as tests/threshold_common.py restates it and tests/test_threshold_gpu.py observes it: level i visits
+// tiles j * stride_i, so the sample is the rows 32 j stride + r (r < 32) below n - a partial last tile gives its real rows
+// only, and only when its index is a multiple of the stride; ceil(n / 32) * 32 <= first_rows is ONE unthresholded level
+// (every live row a candidate of the final select); pop = the rows a host mask allows.  A host mask reaches this path in
+// batches only (scan_plan.h: choose_algo).  ts_search_stats' candidates and fallback_queries describe the LAST launch
+// block of a call (mfma_block_queries), not the whole batch.
 #include "host.h"
 #include "kernels_mfma.h"
 #include "kernels_mfma16.h"
