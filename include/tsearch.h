@@ -143,7 +143,10 @@ int ts_index_info(const ts_index *ix, int64_t *n, int32_t *d, int32_t *dtype, in
  * kernel, TS_MFMA_F32=32, and only the usual two-level search: not with TS_MFMA_STAT=0 or TS_MFMA_SAMPLE=0) - int8 screen, then an exact fp32 rescore that repeats the fp32 pass's fmaf chain; a screened search
  * holds up to 256 queries per launch instead of 64 or 128.  Opt-in because the image costs d bytes per row on top of the rows
  * (+25 %: 7.68 GB at 10M x 768).  TS_MFMA_SCREEN=0 switches every screen off.
- * Contract of all three: ids and score bits of every search are identical with the option on and off, for every batch size and
+ * "TS_MFMA_SCREEN_LATE" (default 1): the screen's launch of an unmasked bf16 d = 768 search of 193 .. 256 queries runs the
+ * late-test form of the tile kernel (a tile's block tests stand among the next tile's MFMAs); 0 = the kernel that tests every
+ * tile at its own end, which every other screened launch runs either way.  The same pairs, no memory of its own.
+ * Contract of all of them: ids and score bits of every search are identical with the option on and off, for every batch size and
  * whichever form the unscreened pass would take (TS_MFMA_PAIR, TS_MFMA_GRID at bf16 d = 1024) - for every query that neither
  * call sent to the exact re-run, which has the scan's arithmetic either way; views and attached rows are never screened.
  * ts_search_stats.screened tells which pass a call ran. */

@@ -92,14 +92,14 @@ enum Knob {
     K_MFMA_MIN_RANK, K_MFMA_VARIANT, K_MFMA_GROUPS, K_MFMA_GRID, K_MFMA_STAT, K_MFMA_STAT_CANDS, K_MFMA_TAIL_FIT,
     K_MFMA_NO_IDLE, K_MFMA_AHEAD, K_MFMA_TARGET_CANDS, K_MFMA_FIRST_ROWS, K_MFMA_TARGET_SPARSE, K_MFMA_RUN,
     K_MFMA_MIN_ROWS, K_MFMA_SHAPE, K_MFMA_F32, K_SCAN_GENERIC, K_SCAN_MAX_QUERIES, K_MFMA_BALANCE, K_PROBE_SPREAD, K_MFMA_SAMPLE,
-    K_MFMA_PAIR, K_MFMA_PAIR_LAG, K_MFMA_SCREEN, K_MFMA_SCREEN_WIDE, K_MFMA_SCREEN_F32, K_COUNT
+    K_MFMA_PAIR, K_MFMA_PAIR_LAG, K_MFMA_SCREEN, K_MFMA_SCREEN_WIDE, K_MFMA_SCREEN_F32, K_MFMA_SCREEN_LATE, K_COUNT
 };
 inline const char* const kKnobNames[K_COUNT] = {
     "TS_MFMA_MIN_RANK", "TS_MFMA_VARIANT", "TS_MFMA_GROUPS", "TS_MFMA_GRID", "TS_MFMA_STAT", "TS_MFMA_STAT_CANDS",
     "TS_MFMA_TAIL_FIT", "TS_MFMA_NO_IDLE", "TS_MFMA_AHEAD", "TS_MFMA_TARGET_CANDS", "TS_MFMA_FIRST_ROWS",
     "TS_MFMA_TARGET_SPARSE", "TS_MFMA_RUN", "TS_MFMA_MIN_ROWS", "TS_MFMA_SHAPE", "TS_MFMA_F32", "TS_SCAN_GENERIC",
     "TS_SCAN_MAX_QUERIES", "TS_MFMA_BALANCE", "TS_PROBE_SPREAD", "TS_MFMA_SAMPLE", "TS_MFMA_PAIR", "TS_MFMA_PAIR_LAG",
-    "TS_MFMA_SCREEN", "TS_MFMA_SCREEN_WIDE", "TS_MFMA_SCREEN_F32"};
+    "TS_MFMA_SCREEN", "TS_MFMA_SCREEN_WIDE", "TS_MFMA_SCREEN_F32", "TS_MFMA_SCREEN_LATE"};
 struct Knobs {
     int v[K_COUNT];
     bool set[K_COUNT];
@@ -384,6 +384,9 @@ int screen_tile_pass(ts_index* ix, int nb, int grid, int variant, hipStream_t st
 int screen_prepare_wide(ts_index* ix, const void* qmat, int nq_launch, bool quantize_queries, hipStream_t st);
 int screen_full_pass_wide(ts_index* ix, int nb, int nq, int grid, int variant, bool ksplit, hipStream_t st, const ts::MfmaArgs& a);
 int screen_tile_pass_wide(ts_index* ix, int nb, int grid, int variant, hipStream_t st, const ts::MfmaArgs& a);
+// ... the late-test form of the d = 768 tile kernel at four query blocks per wave, unmasked (launch_screen8_late.hip;
+// TS_MFMA_SCREEN_LATE): `a` is the screen's argument block
+int launch_screen8_late(int dev, int grid, hipStream_t st, const ts::MfmaArgs& a);
 // ... and those of fp32 indexes (launch_screen8_f32.hip): fp32 quantisers, screen_tile_pass, the fp32 rescore
 int screen_prepare_f32(ts_index* ix, const void* qmat, int nq_launch, hipStream_t st);
 int screen_full_pass_f32(ts_index* ix, int nb, int nq, int grid, int variant, hipStream_t st, const ts::MfmaArgs& a);

@@ -260,11 +260,21 @@ __device__ __forceinline__ void mfma16_write_probe(unsigned long long* dbg, unsi
 // at both operands: whatever k order the i8 instruction gives the bytes of a lane, both operands share it and the integer dot
 // product is exact) - with the i8 MFMA, an integer threshold per (tile, query) from the tile's scalars and (row, query) pairs
 // as candidates (MfmaArgs::cand / count / cap: the screen's lists).
+// kVariantScreenLate (kLate; D = 384, NB = 4, launch_screen8_late.hip): the same screen with the block tests off the path behind a
+// tile's last MFMA, where one wave per SIMD has nothing to hide them behind.  Two accumulator sets, accL[tile parity] (the loop runs
+// two tiles per trip, as for the k-split), and the integer thresholds per parity: tile t multiplies into its own set while twelve
+// two-instruction pieces (TS16_LATE) in the gaps behind the MFMAs of query block 3 of its k-steps 0 .. 5 test the other set - tile
+// t - 1, last written a tile ago - and leave four lane masks in SGPRs.  The end of tile t is the ring's drain, one OR of the masks
+// and a branch; the rare path stages the pairs of tile t - 1 from the other set with that tile's row base (the checked form from
+// the first tile with padding rows on).  The last tile is tested behind the loop as the other form tests every tile.  The same
+// pairs in another order within a wave's list.  Registers: 24 query fragments in VGPRs, 24 in AGPRs, as the k-split.
 template <int D, int NB, int VARIANT, bool SPARSE, bool F32 = false, bool PAIR = false, bool KSPLIT = false>
 __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a) {
     static_assert(!PAIR || (!SPARSE && !F32), "pairs exist for the bf16 full pass");
     constexpr bool I8 = variant_is_screen(VARIANT);
     constexpr bool kMasked8 = variant_masked(VARIANT);       // the row mask is looked at (kVariantScreen: the unmasked product)
+    constexpr bool kLate = variant_late(VARIANT);            // the late-test screen: tile t - 1 is tested among the MFMAs of tile t
+    static_assert(!kLate || (D == 384 && NB == 4), "the late-test screen is the d = 768 screen with four query blocks per wave");
     static_assert(!I8 || ((D == 384 || D == 512) && !SPARSE && !F32 && !PAIR), "the screen is the full pass over 768- or 1,024-byte int8 rows");
     static_assert(!KSPLIT || (PAIR && NB == 4 && variant_ksplit_form(VARIANT) && D == 1024), "the k-split is the paired pass of d = 1024 with four query blocks per wave");
     constexpr int Deq = F32 ? 2 * D : D;                 // row length in 2-byte elements
@@ -295,7 +305,8 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     // (k-split: the exchange holds 32 registers more - the kept blocks and the partner's sums; with the queries' share left at 32
     // fragments hipcc parks two of them in AGPRs and copies them back right in front of their MFMA inside the asm stream, where
     // its hazard recognizer sees no MFMA: the k-steps of those two fragments came out wrong on the GPU)
-    constexpr int kQVmax = KSPLIT ? 24 : 36 - 2 * (kA - 2);   // the ring's registers come out of the VGPR share of the queries
+    // (late-test screen: a second accumulator set and a second set of thresholds, 36 registers more - the same share as the k-split)
+    constexpr int kQVmax = (KSPLIT || kLate) ? 24 : 36 - 2 * (kA - 2);   // the ring's registers come out of the VGPR share of the queries
     constexpr int kQV = kFrags < kQVmax ? kFrags : kQVmax;   // ... the first kQV of them in VGPRs, the rest in AGPRs
     // cache policy of the corpus stream: non-temporal (read once per search) - except in the paired pass, where the first
     // of a pair's two reads of a tile must leave its lines in the XCD's L2 for the second (with nt on both the fabric
@@ -460,6 +471,22 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
 
     f32x4 acc[2][NB];
     f32x4 accK[2][2][2] = {};                            // k-split: [tile parity][row block][kept block]
+    // late-test screen: [tile parity][row block][query block] - tile t multiplies into its parity's set while its MFMA gaps test
+    // the other one (tile t - 1), against that tile's thresholds lthr[parity ^ 1].  The odd set starts as "nothing passes":
+    // tile 0 tests it.
+    f32x4 accL[kLate ? 2 : 1][2][kLate ? NB : 1];
+    int lthr[kLate ? 2 : 1][kLate ? NB : 1];
+    int lbest = 0;
+    u64 lhit[kLate ? NB : 1];
+    if constexpr (kLate) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            accL[1][0][b] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            accL[1][1][b] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            lthr[1][b] = 0x7fffffff;
+            asm volatile("" : "+v"(accL[1][0][b]), "+v"(accL[1][1][b]), "+v"(lthr[1][b]));
+        }
+    }
     u32 cnt[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) cnt[b] = 0;
@@ -480,7 +507,12 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
 #define TS16_MMA(RB_, B_, KS_, AF_)                                                                        \
     do {                                                                                                   \
         constexpr int f_ = (B_) * kSteps + (KS_);                                                          \
-        if constexpr (I8) {                                                                                \
+        if constexpr (kLate) {                                                                             \
+            if constexpr ((KS_) == 0 && f_ < kQV) mfma8_v_first(accL[par_][RB_][B_], AF_, qv[f_ < kQV ? f_ : 0]);  \
+            else if constexpr ((KS_) == 0) mfma8_a_first(accL[par_][RB_][B_], AF_, qa[f_ >= kQV ? f_ - kQV : 0]); \
+            else if constexpr (f_ < kQV) mfma8_v(accL[par_][RB_][B_], AF_, qv[f_ < kQV ? f_ : 0]);         \
+            else mfma8_a(accL[par_][RB_][B_], AF_, qa[f_ >= kQV ? f_ - kQV : 0]);                          \
+        } else if constexpr (I8) {                                                                         \
             if constexpr ((KS_) == 0 && f_ < kQV) mfma8_v_first(acc[RB_][B_], AF_, qv[f_ < kQV ? f_ : 0]);  \
             else if constexpr ((KS_) == 0) mfma8_a_first(acc[RB_][B_], AF_, qa[f_ >= kQV ? f_ - kQV : 0]); \
             else if constexpr (f_ < kQV) mfma8_v(acc[RB_][B_], AF_, qv[f_ < kQV ? f_ : 0]);                \
@@ -557,8 +589,25 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
             constexpr int gpk_ = NB >= 3 ? 4 : 2;                                                          \
             constexpr int g_ = NB == 1 ? (G_) + 2 : (G_);                                                  \
             constexpr int P_ = ((KS_) / 2) * gpk_ + g_;                                                    \
-            if constexpr ((KS_) % 2 == 0 && g_ >= 0 && g_ < gpk_ && (NB == 1) == ((G_) < 0) && P_ < 4 * NB) \
-                screen_thr_piece<P_ & 3>(ithr[P_ >> 2], tmc, fq1[P_ >> 2], fq2[P_ >> 2], fq3[P_ >> 2]);       \
+            if constexpr ((KS_) % 2 == 0 && g_ >= 0 && g_ < gpk_ && (NB == 1) == ((G_) < 0) && P_ < 4 * NB) { \
+                if constexpr (kLate) screen_thr_piece<P_ & 3>(lthr[par_][P_ >> 2], tmc, fq1[P_ >> 2], fq2[P_ >> 2], fq3[P_ >> 2]); \
+                else screen_thr_piece<P_ & 3>(ithr[P_ >> 2], tmc, fq1[P_ >> 2], fq2[P_ >> 2], fq3[P_ >> 2]);   \
+            }                                                                                              \
+        }                                                                                                  \
+    } while (0)
+    // late-test screen: piece 3 b + p of the block tests of the PREVIOUS tile (late_test_a / b / c, kernels_screen8_tile.h) in gap G_
+    // (0, 1) behind the two MFMAs of query block 3 of k-step KS_ - gaps that hold nothing else in any k-step: k-steps 0 .. 5.  The
+    // pieces read the other parity's accumulators and thresholds; the four lane masks stay in SGPRs to the end of the tile.
+#define TS16_LATE(KS_, G_)                                                                                 \
+    do {                                                                                                   \
+        if constexpr (kLate) {                                                                             \
+            constexpr int p_ = (KS_) * 2 + (G_);                                                           \
+            if constexpr (p_ < 3 * NB) {                                                                   \
+                constexpr int b_ = p_ / 3;                                                                 \
+                if constexpr (p_ % 3 == 0) late_test_a(lbest, accL[par_ ^ 1][0][b_], accL[par_ ^ 1][1][b_]); \
+                if constexpr (p_ % 3 == 1) late_test_b(lbest, accL[par_ ^ 1][1][b_]);                      \
+                if constexpr (p_ % 3 == 2) late_test_c(lhit[b_], lbest, lthr[par_ ^ 1][b_]);               \
+            }                                                                                              \
         }                                                                                                  \
     } while (0)
 #ifndef TS16_ORDER_A
@@ -586,7 +635,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
             TS16_MMA(0, 2, KS_, af[R0_]); TS16_THR8(KS_, 2);                                               \
             TS16_MMA(1, 2, KS_, af[R0_ + 1]); TS16_THR8(KS_, 3);                                           \
         }                                                                                                  \
-        if constexpr (NB > 3) { TS16_MMA(0, 3, KS_, af[R0_]); TS16_MMA(1, 3, KS_, af[R0_ + 1]); }          \
+        if constexpr (NB > 3) { TS16_MMA(0, 3, KS_, af[R0_]); TS16_LATE(KS_, 0); TS16_MMA(1, 3, KS_, af[R0_ + 1]); TS16_LATE(KS_, 1); } \
     } while (0)
 #else   /* A/B build: row-block major - the corpus fragment stays put for NB consecutive MFMAs */
 #define TS16_BF16_ORDER(KS_, R0_, N_, S_)                                                                  \
@@ -848,6 +897,31 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
             for (int b = 0; b < NB; ++b) asm volatile("" ::"v"(acc[0][b]), "v"(acc[1][b]));
             return;
         }
+        if constexpr (kLate) {
+            // what is left of the tail: the masks the fillers left, one branch, the scalars' rotation.  The pairs of tile t - 1 come
+            // out of the other parity's set, which nobody writes before the next tile's first MFMAs.
+            asm volatile("" : "+s"(tmn));
+            const u64 lany = (lhit[0] | lhit[1]) | (lhit[2] | lhit[3]);
+            if (__builtin_expect(lany != 0, 0)) {
+                const u32 tp = (u32)t0 + (u32)t - 1u;    // (tile 0 tests the "nothing passes" start of the odd set: never here)
+                const u32 row_base = tp * kTileRows + 4 * kq;
+                if (t - 1 >= t_chk) {
+                    const u32 live = screen_tile_live<false>(tp * kTileRows, s_n, s_mask) >> (4 * kq);
+#pragma unroll
+                    for (int b = 0; b < NB; ++b)
+                        if (lhit[b] != 0)
+                            mfma8_append_block<true>(accL[par_ ^ 1][0][b], accL[par_ ^ 1][1][b], lthr[par_ ^ 1][b], qid[b], row_base, scnt, stage8, live, s_nq, s_count, s_cand);
+                } else {
+#pragma unroll
+                    for (int b = 0; b < NB; ++b)
+                        if (lhit[b] != 0)
+                            mfma8_append_block<false>(accL[par_ ^ 1][0][b], accL[par_ ^ 1][1][b], lthr[par_ ^ 1][b], qid[b], row_base, scnt, stage8, 0u, s_nq, s_count, s_cand);
+                }
+            }
+            tmc = tmn;
+            screen_tile_scalars(tmn, scr_tile, t0 + (t + 2 < nt ? t + 2 : nt - 1));
+            return;
+        }
         if constexpr (I8) {
             // tile t + 1's scalars: landed behind the drain above
             asm volatile("" : "+s"(tmn));
@@ -880,7 +954,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
         }
         mfma16_tile_tail<NB, VARIANT, kStaged>(acc, thr, qid, cnt, t0, t, kq, writer, nwriters, a, stage, stage_cnt);
     };
-    if constexpr (KSPLIT) {
+    if constexpr (KSPLIT || kLate) {
         for (int t = 0; t < nt; t += 2) {
             tile(std::integral_constant<int, 0>{}, t);
             if (t + 1 < nt) tile(std::integral_constant<int, 1>{}, t + 1);
@@ -911,6 +985,37 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
         hit_[1] = mfma16_block_test(sum_[0][1], sum_[1][1], thr[1], best_[1]);
         TS16_KSPLIT_APPEND(nt - 1);
     }
+    if constexpr (kLate) {
+        // the last tile, tested and staged the present way: wait states behind its last MFMAs, then the block tests on its parity's set
+        mfma16_settle<NB>(accL[0]);
+        mfma16_settle<NB>(accL[1]);
+        const bool odd = ((nt - 1) & 1) != 0;
+        f32x4 fin[2][NB];
+        int fthr[NB];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            fin[0][b] = odd ? accL[1][0][b] : accL[0][0][b];
+            fin[1][b] = odd ? accL[1][1][b] : accL[0][1][b];
+            fthr[b] = odd ? lthr[1][b] : lthr[0][b];
+        }
+        u64 fhit[NB];
+        const u64 fany = screen_tile_test<NB>(fin, fthr, fhit);
+        if (fany != 0) {
+            const u32 tp = (u32)t0 + (u32)(nt - 1);
+            const u32 row_base = tp * kTileRows + 4 * kq;
+            if (nt - 1 >= t_chk) {
+                const u32 live = screen_tile_live<false>(tp * kTileRows, s_n, s_mask) >> (4 * kq);
+#pragma unroll
+                for (int b = 0; b < NB; ++b)
+                    if (fhit[b] != 0) mfma8_append_block<true>(fin[0][b], fin[1][b], fthr[b], qid[b], row_base, scnt, stage8, live, s_nq, s_count, s_cand);
+            } else {
+#pragma unroll
+                for (int b = 0; b < NB; ++b)
+                    if (fhit[b] != 0) mfma8_append_block<false>(fin[0][b], fin[1][b], fthr[b], qid[b], row_base, scnt, stage8, 0u, s_nq, s_count, s_cand);
+            }
+        }
+    }
+#undef TS16_LATE
 #undef TS16_KSPLIT_APPEND
 #undef TS16_KSPLIT_FETCH
 #undef TS16_UNIT

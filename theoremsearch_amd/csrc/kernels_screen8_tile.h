@@ -26,6 +26,19 @@ __device__ __forceinline__ u64 mfma8_block_test(const f32x4& a0, const f32x4& a1
     return mask;
 }
 
+// The same test in three pieces of at most two instructions, for the late-test screen (kVariantScreenLate): placed one by one in
+// MFMA gaps of the NEXT tile (TS16_LATE, kernels_mfma16.h), where the matrix pipe leaves the vector issue free.  They read the
+// other tile parity's accumulators, last written a tile ago: no wait states to add.
+__device__ __forceinline__ void late_test_a(int& m, const f32x4& a0, const f32x4& a1) {
+    asm volatile("v_max3_i32 %0, %1, %2, %3\n\tv_max3_i32 %0, %0, %4, %5" : "=&v"(m) : "v"(a0[0]), "v"(a0[1]), "v"(a0[2]), "v"(a0[3]), "v"(a1[0]));
+}
+__device__ __forceinline__ void late_test_b(int& m, const f32x4& a1) {
+    asm volatile("v_max3_i32 %0, %0, %1, %2\n\tv_max_i32 %0, %0, %3" : "+v"(m) : "v"(a1[1]), "v"(a1[2]), "v"(a1[3]));
+}
+__device__ __forceinline__ void late_test_c(u64& mask, int m, int thr) {
+    asm volatile("v_cmp_ge_i32 %0, %1, %2" : "=s"(mask) : "v"(m), "v"(thr));
+}
+
 // Integer thresholds of the int8 screen (kernels_screen8.h has the derivation and the rounding argument): every row of a tile
 // whose exact fp32 score can reach the query's `thr` has an int8 dot product >= the (tile, query) threshold.  The query's side
 // is folded once per launch: with rq = 1 / s_q, eq = |e_q|, qn = |q| (rq = NaN: the query holds a non-finite value) and

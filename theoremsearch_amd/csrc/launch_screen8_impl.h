@@ -79,8 +79,10 @@ static int screen_prepare_w(ts_index* ix, const void* qmat, int nq_launch, bool 
 // The screen's launch of the full pass: the tile kernel over the image, `a` being the unscreened pass's argument block
 // (thresholds, row mask, tile table); its (row, query) pairs go to the screen's lists.
 // variant: a timing-only form of the screen (variant_screen_diag; diagnostic build; wrong results), or kVariantProduct.
+// late: the bf16 full pass of d = 768 may take the late-test form of the kernel (TS_MFMA_SCREEN_LATE, launch_screen8_late.hip) -
+// which exists for four query blocks per wave, no row mask and the product only; every other launch takes the kernels of this unit.
 template <int W>
-static int screen_tile_pass_w(ts_index* ix, int nb, int grid, int variant, hipStream_t st, const MfmaArgs& a) {
+static int screen_tile_pass_w(ts_index* ix, int nb, int grid, int variant, hipStream_t st, const MfmaArgs& a, bool late = false) {
     MfmaArgs s = a;
     s.corpus = (const unsigned short*)ix->scr_rows;
     s.q = (const unsigned short*)ix->scr_q;
@@ -89,6 +91,8 @@ static int screen_tile_pass_w(ts_index* ix, int nb, int grid, int variant, hipSt
     s.cap = kScreenCap;
     s.scr_tile = (const float4*)ix->scr_tile;
     s.scr_q = (const float4*)ix->scr_qmeta;
+    if constexpr (W == 768)
+        if (late && nb == 4 && variant == kVariantProduct && s.row_mask == nullptr) return launch_screen8_late(ix->device, grid, st, s);
     switch (nb) {
         case 1: return launch_screen8<W, 1>(ix->device, grid, variant, st, s);
         case 2: return launch_screen8<W, 2>(ix->device, grid, variant, st, s);
@@ -103,7 +107,7 @@ static int screen_tile_pass_w(ts_index* ix, int nb, int grid, int variant, hipSt
 // half-chains as that form does.
 template <int W>
 static int screen_full_pass_w(ts_index* ix, int nb, int nq, int grid, int variant, bool ksplit, hipStream_t st, const MfmaArgs& a) {
-    TS_TRY(screen_tile_pass_w<W>(ix, nb, grid, variant, st, a));
+    TS_TRY(screen_tile_pass_w<W>(ix, nb, grid, variant, st, a, W == 768 && ix->dtype == TS_BF16 && ix->knobs.get(K_MFMA_SCREEN_LATE, 1) != 0));
     ScreenRescoreArgs r;
     r.rows = (const unsigned short*)ix->rows;
     r.q = a.q;

@@ -44,10 +44,15 @@ constexpr int kVariantScreenTestOnly = 13;
 // 14 = the screen of a search with a row mask (a product kernel): 8 holds no code that reads MfmaArgs::row_mask; 14 and the
 // product-with-instruments forms 10, 11 test the mask (when there is one) before a pair is staged.
 constexpr int kVariantScreenMasked = 14;
+// 15 = the late-test screen (a product kernel; TS_MFMA_SCREEN_LATE, launch_screen8_late.hip): the unmasked screen of d = 768 with
+// four query blocks per wave, whose block tests of tile t - 1 stand in MFMA gaps of tile t (two accumulator sets by tile parity)
+// and whose admitted pairs are staged one tile late.  The same pairs as 8.
+constexpr int kVariantScreenLate = 15;
 
-constexpr bool variant_is_screen(int v) { return v >= kVariantScreen && v <= kVariantScreenMasked; }                  // I8
+constexpr bool variant_is_screen(int v) { return v >= kVariantScreen && v <= kVariantScreenLate; }                    // I8
 constexpr bool variant_screen_diag(int v) { return v >= kVariantScreenNoEpilogue && v <= kVariantScreenTestOnly; }    // the screen's timing-only forms
-constexpr bool variant_masked(int v) { return variant_is_screen(v) && v != kVariantScreen; }    // the row mask is looked at (8: the unmasked product)
+constexpr bool variant_masked(int v) { return variant_is_screen(v) && v != kVariantScreen && v != kVariantScreenLate; }    // the row mask is looked at (8, 15: the unmasked products)
+constexpr bool variant_late(int v) { return v == kVariantScreenLate; }                           // block tests one tile late
 constexpr bool variant_no_epilogue(int v) { return v == kVariantNoEpilogue || v == kVariantNoDma || v == kVariantScreenNoEpilogue; }
 constexpr bool variant_no_mma(int v) { return v == kVariantDmaOnly || v == kVariantScreenDmaOnly; }
 constexpr bool variant_no_dma(int v) { return v == kVariantNoDma; }
