@@ -2,8 +2,8 @@
 * the references pass their own bounds: on the inputs of tests/test_encoder_pieces_gpu.py torch's own fp32 evaluation of each
   formula, split into pieces by split_ref, passes the bound the GPU test uses - with a factor 2 to spare;
 * the checks have teeth: each corrupted answer a wrong kernel could give is rejected;
-* the argument contract of the producers, ts_attention_float and ts_pool_normalize: every refusal returns before the device
-  check (the library loads without a device; a refusal never dereferences a pointer, so aligned fake ones do).
+* the argument contract of every encoder entry point: every refusal returns before the device check (the library loads
+  without a device; a refusal never dereferences a pointer, so aligned fake ones do).
 The measured ratios and the rejected corruptions are printed (also without -s)."""
 import ctypes as C
 
@@ -226,8 +226,65 @@ def pool(lib, hidden=P, mask=P, n=2, seq=8, d=64, out=P, out_ld=64):
     return lib.ts_pool_normalize(0, _p(hidden), 0, _p(mask), n, seq, d, 0, 1, _p(out), 0, out_ld, None)
 
 
+def add_ln(lib, a=P, b=P, gamma=P, beta=P, rows=4, d=256, dtype=0, out=P):
+    return lib.ts_add_layernorm(0, _p(a), _p(b), _p(gamma), _p(beta), 1e-12, rows, d, dtype, _p(out), None)
+
+
+def embed_ln(lib, ids=P, type_ids=P, word=P, pos=P, type=P, n_word=100, n_pos=64, n_type=2, gamma=P, beta=P, tokens=32, seq=16, d=256, dtype=0, out=P):
+    return lib.ts_embed_layernorm(0, _p(ids), _p(type_ids), _p(word), _p(pos), _p(type), n_word, n_pos, n_type, _p(gamma), _p(beta), 1e-12,
+                                  tokens, seq, d, dtype, _p(out), None)
+
+
+def add_rms(lib, a=P, b=P, gamma=P, rows=4, d=256, dtype=0, out_sum=P, out_norm=P):
+    return lib.ts_add_rmsnorm(0, _p(a), _p(b), _p(gamma), 1e-6, rows, d, dtype, _p(out_sum), _p(out_norm), None)
+
+
+def gemma_norm(lib, y=P, x=P, w_post=P, w_next=P, rows=4, d=256, dtype=0, out_sum=P, out_norm=P):
+    return lib.ts_gemma_norm(0, _p(y), _p(x), _p(w_post), _p(w_next), 1e-6, rows, d, dtype, _p(out_sum), _p(out_norm), None)
+
+
+def attn_short(lib, qkv=P, mask=None, batch=2, seq=16, heads=4, hd=64, out=P):
+    return lib.ts_attention_short(0, _p(qkv), _p(mask), batch, seq, heads, hd, _p(out), None)
+
+
+def attn_gqa(lib, qkv=P, mask=None, batch=2, seq=16, hq=4, hkv=2, hd=128, causal=1, out=P):
+    return lib.ts_attention_gqa(0, _p(qkv), _p(mask), batch, seq, hq, hkv, hd, causal, _p(out), None)
+
+
+def qk_rope(lib, qkv=P, qw=P, kw=P, cos=P, sin=P, tokens=32, seq=16, hq=4, hkv=2, hd=128, dtype=0):
+    return lib.ts_qk_norm_rope(0, _p(qkv), _p(qw), _p(kw), _p(cos), _p(sin), 1e-6, tokens, seq, hq, hkv, hd, dtype, None)
+
+
+def gemma_qk_rope(lib, qkv=P, qw=P, kw=P, cos=P, sin=P, tokens=32, seq=16, hq=4, hkv=2, hd=256, dtype=0):
+    return lib.ts_gemma_qk_norm_rope(0, _p(qkv), _p(qw), _p(kw), _p(cos), _p(sin), 1e-6, tokens, seq, hq, hkv, hd, dtype, None)
+
+
+def swiglu(lib, gate_up=P, rows=4, inter=256, dtype=0, out=P):
+    return lib.ts_swiglu(0, _p(gate_up), rows, inter, dtype, _p(out), None)
+
+
+def geglu(lib, gate_up=P, rows=4, inter=256, dtype=0, out=P):
+    return lib.ts_geglu(0, _p(gate_up), rows, inter, dtype, _p(out), None)
+
+
+def split3(lib, x=P, rows=4, k=256, pattern=0, out=P):
+    return lib.ts_split_pieces(0, _p(x), rows, k, pattern, _p(out), None)
+
+
 PRODUCERS = (ln_pieces, rms_pieces, gemma_pieces, act_pieces)
 NORM_PRODUCERS = (ln_pieces, rms_pieces, gemma_pieces)
+NORMS = (add_ln, embed_ln, add_rms, gemma_norm)                # the storage-typed entry points of the norm family
+# every pointer each of the other entry points refuses as NULL, and every one it wants 16-byte aligned
+REQUIRED = {add_ln: ("a", "b", "gamma", "beta", "out"), embed_ln: ("ids", "word", "pos", "type", "gamma", "beta", "out"),
+            add_rms: ("a", "gamma", "out_norm"), gemma_norm: ("x", "w_next", "out_norm"), attn_short: ("qkv", "out"),
+            attn_gqa: ("qkv", "out"), qk_rope: ("qkv", "qw", "kw", "cos", "sin"), gemma_qk_rope: ("qkv", "qw", "kw", "cos", "sin"),
+            swiglu: ("gate_up", "out"), geglu: ("gate_up", "out"), split3: ("x", "out")}
+ALIGNED16 = {add_ln: ("a", "b", "gamma", "beta", "out"), embed_ln: ("word", "pos", "type", "gamma", "beta", "out"),
+             add_rms: ("a", "b", "gamma", "out_sum", "out_norm"), gemma_norm: ("y", "x", "w_post", "w_next", "out_sum", "out_norm"),
+             attn_short: ("qkv", "out"), attn_gqa: ("qkv", "out"), qk_rope: ("qkv", "qw", "kw", "cos", "sin"),
+             gemma_qk_rope: ("qkv", "qw", "kw", "cos", "sin"), swiglu: ("gate_up", "out"), geglu: ("gate_up", "out"), split3: ("x",)}
+EMPTY = {add_ln: "rows", embed_ln: "tokens", add_rms: "rows", gemma_norm: "rows", attn_short: "batch", attn_gqa: "batch",
+         qk_rope: "tokens", gemma_qk_rope: "tokens", swiglu: "rows", geglu: "rows", split3: "rows"}
 
 
 def test_refusals_come_before_the_device_check():
@@ -258,6 +315,43 @@ def test_refusals_come_before_the_device_check():
     for f in PRODUCERS:
         assert f(lib, rows=0) == 0, f.__name__
     assert attention(lib, batch=0) == 0 and pool(lib, n=0) == 0
+    # the other entry points: NULL and misaligned pointers, one at a time
+    for f, names in REQUIRED.items():
+        for name in names:
+            assert f(lib, **{name: None}) == inv, (f.__name__, name)
+    for f, names in ALIGNED16.items():
+        for name in names:
+            assert f(lib, **{name: P + 8}) == inv, (f.__name__, name)
+    assert split3(lib, out=P + 4) == inv                                                      # out: 8-byte aligned
+    assert gemma_norm(lib, w_post=None) == inv                                                # y without w_post
+    # storage types
+    for f in NORMS + (qk_rope, gemma_qk_rope, swiglu, geglu):
+        assert f(lib, dtype=2) == inv and f(lib, dtype=-1) == inv, f.__name__
+    assert b"dtype" in lib.ts_last_error()
+    # shape limits
+    for f in NORMS:
+        assert f(lib, d=6) == inv and f(lib, d=1028) == inv and f(lib, d=0) == inv, f.__name__          # fp32: multiples of 4 up to 1024
+        assert f(lib, dtype=1, d=4) == inv and f(lib, dtype=1, d=12) == inv and f(lib, dtype=1, d=2056) == inv, f.__name__   # bf16: of 8 up to 2048
+        assert f(lib, **{EMPTY[f]: -1}) == inv, f.__name__
+    assert b"must be a multiple of 4 and at most 1024" in lib.ts_last_error()
+    assert embed_ln(lib, seq=0) == inv and embed_ln(lib, n_word=0) == inv and embed_ln(lib, n_pos=0) == inv and embed_ln(lib, n_type=0) == inv
+    for f in (attn_short, attn_gqa):
+        assert f(lib, batch=-1) == inv and f(lib, seq=0) == inv, f.__name__
+        assert f(lib, seq=129) == uns and f(lib, hd=32) == uns and f(lib, hd=256) == uns, f.__name__
+        assert b"at most 128 tokens" in lib.ts_last_error()
+    assert attn_short(lib, heads=0) == inv and attn_short(lib, hd=128) == uns
+    assert attn_gqa(lib, hq=0) == inv and attn_gqa(lib, hkv=0) == inv and attn_gqa(lib, hq=6, hkv=4) == inv and attn_gqa(lib, hd=64) == uns
+    for f, other in ((qk_rope, 256), (gemma_qk_rope, 128)):
+        assert f(lib, tokens=-1) == inv and f(lib, seq=0) == inv and f(lib, hq=0) == inv and f(lib, hkv=0) == inv, f.__name__
+        assert f(lib, hd=other) == uns and f(lib, hd=64) == uns, f.__name__
+        assert b"head size" in lib.ts_last_error()
+    for f in (swiglu, geglu):
+        assert f(lib, inter=6) == inv and f(lib, inter=0) == inv and f(lib, dtype=1, inter=12) == inv and f(lib, rows=-1) == inv, f.__name__
+    assert split3(lib, k=6) == inv and split3(lib, k=0) == inv and split3(lib, pattern=2) == inv and split3(lib, pattern=-1) == inv
+    assert split3(lib, rows=-1) == inv
+    # the empty call
+    for f, name in EMPTY.items():
+        assert f(lib, **{name: 0}) == 0, f.__name__
 
 
 @pytest.mark.skipif(gpu_available(), reason="fake pointers: only where the device check refuses the call")
@@ -274,3 +368,35 @@ def test_valid_arguments_reach_the_device_check():
     for hd, seq in ((64, 512), (128, 256), (256, 128)):
         assert attention(lib, hd=hd, seq=seq) == nod, (hd, seq)
     assert pool(lib, out_ld=72) == nod
+    for f in REQUIRED:
+        assert f(lib) == nod, f.__name__
+    for f in NORMS:
+        assert f(lib, d=4) == nod and f(lib, d=1024) == nod and f(lib, dtype=1, d=8) == nod and f(lib, dtype=1, d=2048) == nod, f.__name__
+    assert embed_ln(lib, type_ids=None) == nod and add_rms(lib, b=None, out_sum=None) == nod
+    assert gemma_norm(lib, y=None, w_post=None, out_sum=None) == nod
+    for seq in (1, 64, 65, 128):
+        assert attn_short(lib, seq=seq, mask=P) == nod and attn_gqa(lib, seq=seq, mask=P, causal=0) == nod, seq
+    assert attn_gqa(lib, seq=128, hq=3, hkv=1) == nod and attn_gqa(lib, seq=128, hq=8, hkv=2) == nod
+    assert qk_rope(lib, dtype=1) == nod and gemma_qk_rope(lib, dtype=1) == nod
+    assert swiglu(lib, dtype=1, inter=8) == nod and geglu(lib, inter=4) == nod
+    assert split3(lib, pattern=1, out=P + 8, k=4) == nod
+
+
+@pytest.mark.skipif(gpu_available(), reason="fake pointers: only where the device check refuses the call")
+def test_the_fused_forwards_named_limits_are_the_librarys_refusal_boundaries():
+    """fused_forward.py decides by these names whether a model or a batch takes a kernel; the library holds the limits themselves
+    (csrc/encoder_plan.h).  At each named limit a call gets as far as the device check; one step past it, it is refused."""
+    from theoremsearch_amd import fused_forward as ff
+    lib = _ffi.load()
+    nod, refused = ec.TS_ERR_NODEVICE, (ec.TS_ERR_INVALID, ec.TS_ERR_UNSUPPORTED)
+    assert attn_short(lib, hd=ff._SHORT_HEAD, seq=ff._SHORT_MAX_SEQ) == nod
+    assert attn_short(lib, hd=ff._SHORT_HEAD, seq=ff._SHORT_MAX_SEQ + 1) in refused and attn_short(lib, hd=ff._SHORT_HEAD + 1, seq=ff._SHORT_MAX_SEQ) in refused
+    assert attn_gqa(lib, hd=ff._GQA_HEAD, seq=ff._GQA_MAX_SEQ) == nod
+    assert attn_gqa(lib, hd=ff._GQA_HEAD, seq=ff._GQA_MAX_SEQ + 1) in refused and attn_gqa(lib, hd=ff._GQA_HEAD + 1, seq=ff._GQA_MAX_SEQ) in refused
+    for hd, seq in ff._FLOAT_ATTENTION_MAX_SEQ.items():
+        assert attention(lib, hd=hd, seq=seq) == nod and attention(lib, hd=hd, seq=seq + 1) in refused, (hd, seq)
+    assert attention(lib, hd=max(ff._FLOAT_ATTENTION_MAX_SEQ) * 2) in refused
+    for dtype, vec in ((0, 4), (1, 8)):
+        for f in NORMS:
+            assert f(lib, dtype=dtype, d=ff._NORM_MAX_VECS * vec) == nod, (f.__name__, dtype)
+            assert f(lib, dtype=dtype, d=(ff._NORM_MAX_VECS + 1) * vec) in refused, (f.__name__, dtype)

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import sys
 import threading
 
 import numpy as np
@@ -155,7 +156,6 @@ def _preload_torch_hip_runtime() -> None:
     its device discovery fails ("No HIP GPUs are available").  So when torch is installed but not imported yet,
     load its bundled runtime first (globally): libtsearch then resolves against it, exactly as it does when the
     application imported torch first."""
-    import sys
     if "torch" in sys.modules:
         return
     try:
@@ -209,6 +209,20 @@ def load() -> C.CDLL:
 def check(rc: int) -> None:
     if rc != TS_OK:
         raise TSearchError(rc, load().ts_last_error().decode("utf-8", "replace"))
+
+
+_PLAIN = (int, float, bool, type(None))        # what ctypes converts by the entry point's argtypes
+
+
+def encoder_op(name: str, on, *args) -> None:
+    """One call of an encoder entry point (``int device`` first, ``void* stream`` last, as all of them are) on the device of
+    tensor ``on`` and that device's current stream.  ``args``: what lies between; numbers go as they are, None as NULL, anything
+    else is a tensor and goes as its ``data_ptr()``.  Tensors by duck typing: this module does not import torch - whoever holds
+    a tensor has.  About a dozen calls per encoder layer come through here: an argument is told by its class, not by probing for
+    attributes, and no lock is taken once the library is loaded."""
+    stream = sys.modules["torch"].cuda.current_stream(on.device).cuda_stream
+    check(getattr(_lib or load(), name)(on.device.index or 0, *[a if a.__class__ in _PLAIN else C.c_void_p(a.data_ptr()) for a in args],
+                                        C.c_void_p(stream)))
 
 
 def device_count() -> int:

@@ -23,6 +23,7 @@
 #include "scan_plan.h"
 #include "anyd_plan.h"
 #include "bias_plan.h"
+#include "encoder_plan.h"
 
 using namespace ts;
 
@@ -84,6 +85,15 @@ template <int V> using variant_c = std::integral_constant<int, V>;
 template <int... Vs, class Go>
 inline bool launch_variant(int variant, int* rc, Go&& go) {
     return ((variant == Vs && ((*rc = go(variant_c<Vs>{})), true)) || ...);
+}
+
+// A run-time value an entry point has validated, as the template argument it selects: go(variant_c<V>{}) for the V of Vs...
+// equal to `v`, its result returned.  Nested for several values (storage type x accesses per lane, tiles x causal x R).
+template <int... Vs, class Go>
+inline int dispatch_value(int v, Go&& go) {
+    int rc = TS_ERR_INVALID;
+    if (!launch_variant<Vs...>(v, &rc, go)) return fail(rc, "internal: no kernel for the value %d", v);
+    return rc;
 }
 
 // Tuning / diagnostic knobs.  Read from the environment ONCE per handle (ts_index_create / ts_index_view /

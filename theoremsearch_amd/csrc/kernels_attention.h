@@ -18,16 +18,12 @@
 //   * O^T leaves the accumulators as [d = 4 (l >> 4) + r][q = l & 15]: four consecutive d per lane, staged through the same LDS and
 //     written as whole 128-byte rows.
 #pragma once
+#include "encoder_plan.h"
 #include "kernels_mfma16_ops.h"
 
 namespace ts {
 
-constexpr int kAttnMaxSeq = 64;
-constexpr int attn_wave_lds(int T) {
-    const int sp = 16 * T, ks = (sp + 31) / 32;
-    const int p_bytes = sp * (32 * ks + 8) * 2, o_bytes = sp * (64 + 8) * 2;
-    return (p_bytes > o_bytes ? p_bytes : o_bytes) + 64 * (32 * ks + 8) * 2;      // + V^T [64][keys]
-}
+// kAttnMaxSeq, attn_wave_lds: encoder_plan.h
 constexpr int attn_vt_offset(int T) {
     const int sp = 16 * T, ks = (sp + 31) / 32;
     const int p_bytes = sp * (32 * ks + 8) * 2, o_bytes = sp * (64 + 8) * 2;
@@ -193,11 +189,7 @@ __global__ void __launch_bounds__(256) attention_short_kernel(const unsigned sho
 // LDS per wave: V^T [64][PP] bf16 (17 KB at T = 8) - and nothing else: once the V^T fragments are in registers the image is
 // dead, and the P tile [16][PP] and the O tile [16][72] of the query loop live in its place.  Two workgroups per CU instead of
 // one (the first cut kept all three: 22.5 KB per wave, one wave per SIMD, every latency of the serial chain exposed).
-constexpr int kAttnRowsMaxSeq = 128;
-constexpr int attn_rows_wave_lds(int T) {
-    const int sp = 16 * T, ks = (sp + 31) / 32, pp = 32 * ks + 8;
-    return 64 * pp * 2;
-}
+// kAttnRowsMaxSeq, attn_rows_wave_lds: encoder_plan.h
 
 template <int T>
 __global__ void __launch_bounds__(256) attention_rows_kernel(const unsigned short* __restrict__ qkv, const int64_t* __restrict__ mask,
@@ -365,11 +357,7 @@ __global__ void __launch_bounds__(256) attention_rows_kernel(const unsigned shor
 // ts_qk_norm_rope's launch: the transform took the kernel from two or three waves per SIMD to one, and the step of the
 // Qwen3-shaped encoder did not move - 14.60 against 14.65 ms.  Removed; profiles/HISTORY.md, round 4.)
 // LDS per wave: V^T image + P image; the O tile reuses the V^T image once its fragments are in registers.
-constexpr int kAttnGqaMaxSeq = 64;
-constexpr int attn_gqa_wave_lds(int T) {
-    const int sp = 16 * T, ks = (sp + 31) / 32, pp = 32 * ks + 8;
-    return 128 * pp * 2 + sp * pp * 2;
-}
+// kAttnGqaMaxSeq, attn_gqa_wave_lds: encoder_plan.h
 
 template <int T, bool CAUSAL>
 __global__ void __launch_bounds__(256, (T <= 2 ? 2 : 1)) attention_gqa_kernel(const unsigned short* __restrict__ qkv,
@@ -534,15 +522,7 @@ __global__ void __launch_bounds__(256, (T <= 2 ? 2 : 1)) attention_gqa_kernel(co
 // the whole sequence (T x 4 x 4 registers) stay in registers, V^T [128][keys] stays in LDS (its fragments are read per query
 // tile: 128 more registers do not exist), the wave walks the query tiles; causal: tile qi multiplies key tiles 0 .. qi only.
 // LDS: one V^T image per workgroup + per wave ONE tile that is the P tile first and the O tile after P's fragments have been read.
-constexpr int kAttnGqaRowsMaxSeq = 128;
-constexpr int attn_gqa_rows_tile_bytes(int T) {
-    const int sp = 16 * T, ks = (sp + 31) / 32, pp = 32 * ks + 8;
-    return 16 * (pp > 136 ? pp : 136) * 2;
-}
-constexpr int attn_gqa_rows_lds(int T, int R) {            // one V^T image per workgroup + one tile per wave
-    const int sp = 16 * T, ks = (sp + 31) / 32, pp = 32 * ks + 8;
-    return 128 * pp * 2 + R * attn_gqa_rows_tile_bytes(T);
-}
+// kAttnGqaRowsMaxSeq, attn_gqa_rows_tile_bytes, attn_gqa_rows_lds: encoder_plan.h
 
 // R = query heads per key / value head served by ONE workgroup of R waves (1, 2 or 4; grid = B * HKV * (HQ / HKV / R)): the
 // waves share the V^T image of their key / value head - each transposes its share of the rows - instead of building one each
@@ -726,9 +706,7 @@ __global__ void __launch_bounds__(64 * R) attention_gqa_rows_kernel(const unsign
 //     [d r16][those four keys] = ONE ds_read_b128 of the transposed image (pitch SP + 4 floats: conflict-free);
 //     D[d 4 g + r][query r16]: four consecutive d per lane, stored as 16 bytes.
 // HD = head size (64 BERT, 128 Qwen3, 256 Gemma3); CAUSAL skips key tiles past the query tile; grouped-query: KV head = h / (HQ / HKV).
-constexpr int kAttnF32MaxSeq = 128;                                  // every head size; smaller heads go further:
-constexpr int attn_f32_max_seq(int HD) { return HD == 64 ? 512 : HD == 128 ? 256 : 128; }   // V^T must fit the CU's LDS (<= 133 KB)
-constexpr int attn_f32_lds(int HD, int T) { return HD * (16 * T + 4) * 4; }
+// kAttnF32MaxSeq, attn_f32_max_seq, attn_f32_lds: encoder_plan.h
 
 // The key tiles are walked as a RUNNING softmax (one tile's scores in registers at a time: running maximum m, running sum l,
 // O rescaled by 2^(m - m') when the maximum moves), so the loop over key tiles is a plain run-time loop over fixed registers: the

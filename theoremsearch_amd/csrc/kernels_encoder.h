@@ -4,6 +4,7 @@
 // parsed_papers_to_vector_rds/embeddings.py:31-37, ec2/generate_embeddings/embeddings.py:24-30, streamlit_app.py:173.
 #pragma once
 #include "common.h"
+#include "encoder_plan.h"      // the limits: kPoolVecSeq, kLnMax
 
 namespace ts {
 
@@ -78,7 +79,6 @@ __global__ void __launch_bounds__(256) pool_normalize_kernel(const void* __restr
 // seq / G independent loads in flight, the mask counted by the whole workgroup.  The kernel above walks the tokens with one
 // 2-byte load per thread and token behind a serial scan of the mask by thread 0: 32 us for 256 x 32 x 768 bf16 (12.6 MB),
 // this one is bound by the read.  Partial sums are combined in group order (deterministic).
-constexpr int kPoolVecSeq = 1024;
 template <int HDT, int ODT>
 __global__ void __launch_bounds__(256) pool_normalize_vec_kernel(const void* __restrict__ hidden, const int64_t* __restrict__ mask,
                                                                   int seq, int d, int pooling, int normalize, void* __restrict__ out,
@@ -171,7 +171,6 @@ __global__ void __launch_bounds__(256) pool_normalize_vec_kernel(const void* __r
 // (bf16) or 4 (fp32) per 16-byte access; d a multiple of that, at most 64 * kLnMax accesses per row.
 // LN = 16-byte accesses per lane (1, 2 or 4, the smallest that covers the row): the BERT-base width (96 accesses per row)
 // takes 2 and a third of the registers of the 4-access form, so every row of a launch is resident at once.
-constexpr int kLnMax = 4;
 template <int DT, int LN = kLnMax>
 __global__ void __launch_bounds__(256) add_layernorm_kernel(const void* a, const void* b,      // `out` may alias a or b: no restrict
                                                              const void* __restrict__ gamma, const void* __restrict__ beta, float eps,

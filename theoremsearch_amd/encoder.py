@@ -376,18 +376,14 @@ class SentenceEncoder:
         if out_dtype == torch.bfloat16 and not (fused and not self.pipeline.dense):
             return self.pool(hidden, attention_mask, normalize).to(torch.bfloat16)
         if fused:
-            import ctypes as C
             from . import _ffi
             hidden = hidden.contiguous()
             mask = attention_mask.to(torch.int64).contiguous()
             n, seq, d = hidden.shape
             emb = torch.empty((n, d), dtype=out_dtype, device=hidden.device)
             norm_here = normalize and not self.pipeline.dense
-            _ffi.check(_ffi.load().ts_pool_normalize(
-                hidden.device.index or 0, C.c_void_p(hidden.data_ptr()), 1 if hidden.dtype == torch.bfloat16 else 0,
-                C.c_void_p(mask.data_ptr()), n, seq, d, _POOL_CODES[self.pooling], 1 if norm_here else 0,
-                C.c_void_p(emb.data_ptr()), 1 if out_dtype == torch.bfloat16 else 0, d,
-                C.c_void_p(torch.cuda.current_stream(hidden.device).cuda_stream)))
+            _ffi.encoder_op("ts_pool_normalize", hidden, hidden, 1 if hidden.dtype == torch.bfloat16 else 0, mask, n, seq, d,
+                            _POOL_CODES[self.pooling], 1 if norm_here else 0, emb, 1 if out_dtype == torch.bfloat16 else 0, d)
             if not self.pipeline.dense:
                 return emb
         else:

@@ -17,17 +17,16 @@ from typing import Optional
 
 import torch
 
+from . import _ffi
+
 
 def split_pieces(x: torch.Tensor, pattern: int) -> torch.Tensor:
     """``x`` fp32 ``[rows x k]`` -> bf16 ``[rows x 3k]``: ``[hi | lo | hi]`` (pattern 0, activations) or ``[hi | hi | lo]``
     (pattern 1, weights), hi = bf16(x), lo = bf16(x - hi) (``ts_split_pieces``)."""
-    import ctypes as C
-    from . import _ffi
     x = x.contiguous()
     rows, k = x.shape
     out = torch.empty((rows, 3 * k), dtype=torch.bfloat16, device=x.device)
-    _ffi.check(_ffi.load().ts_split_pieces(x.device.index or 0, C.c_void_p(x.data_ptr()), rows, k, pattern, C.c_void_p(out.data_ptr()),
-                                           C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+    _ffi.encoder_op("ts_split_pieces", x, x, rows, k, pattern, out)
     return out
 
 
@@ -56,14 +55,11 @@ def pieces_mm(x_pieces: torch.Tensor, w_pieces: torch.Tensor, bias: Optional[tor
 def act_pieces(x: torch.Tensor, kind: int, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp32 activation straight into pieces (``ts_act_pieces``): kind 0 = gelu (erf) of ``[rows x n]``; 1 = silu(gate) * up,
     2 = gelu_tanh(gate) * up of ``[rows x 2n]``; ``bias`` (over the input's width) is added first.  Returns bf16 ``[rows x 3n]``."""
-    import ctypes as C
-    from . import _ffi
     x = x.contiguous()
     rows = x.numel() // x.shape[-1]
     n = x.shape[-1] if kind == 0 else x.shape[-1] // 2
     out = torch.empty((rows, 3 * n), dtype=torch.bfloat16, device=x.device)
-    _ffi.check(_ffi.load().ts_act_pieces(x.device.index or 0, C.c_void_p(x.data_ptr()), C.c_void_p(bias.data_ptr()) if bias is not None else None,
-                                         rows, n, kind, C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+    _ffi.encoder_op("ts_act_pieces", x, x, bias, rows, n, kind, out)
     return out
 
 
@@ -72,21 +68,18 @@ def attention_float(qkv: torch.Tensor, key_mask: Optional[torch.Tensor], B: int,
     """fp32 attention of at most 512 / 256 / 128 tokens (head size 64 / 128 / 256) on the exact-fp32 matrix instructions, straight from the stacked projection's output
     ``qkv [B x S x (hq + 2 hkv) hd]`` (``ts_attention_float``; ``bias``: the projection's bias when its GEMM ran without one):
     ``(context fp32 [B x S x hq hd] - None with ``want_context=False`` - , its bf16 pieces or None)``."""
-    import ctypes as C
-    from . import _ffi
     qkv = qkv.contiguous()
     ctx = torch.empty((B, S, hq * hd), dtype=torch.float32, device=qkv.device) if (want_context or not want_pieces) else None
     pieces = torch.empty((B * S, 3 * hq * hd), dtype=torch.bfloat16, device=qkv.device) if want_pieces else None
-    _ffi.check(_ffi.load().ts_attention_float(
-        qkv.device.index or 0, C.c_void_p(qkv.data_ptr()), C.c_void_p(bias.data_ptr()) if bias is not None else None,
-        C.c_void_p(key_mask.data_ptr()) if key_mask is not None else None, B, S, hq,
-        hkv, hd, 1 if causal else 0, float(scale), C.c_void_p(ctx.data_ptr()) if ctx is not None else None,
-        C.c_void_p(pieces.data_ptr()) if pieces is not None else None,
-        C.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream)))
+    _ffi.encoder_op("ts_attention_float", qkv, qkv, bias, key_mask, B, S, hq, hkv, hd, 1 if causal else 0, float(scale), ctx, pieces)
     return ctx, pieces
 
 
-_FLOAT_ATTENTION_MAX_SEQ = {64: 512, 128: 256, 256: 128}      # what fits the CU's LDS as V^T (attn_f32_max_seq, kernels_attention.h)
+# The limits of the library's kernels (csrc/encoder_plan.h; tests/test_encoder_ref_cpu.py holds each against the library's refusals)
+_FLOAT_ATTENTION_MAX_SEQ = {64: 512, 128: 256, 256: 128}      # what fits the CU's LDS as V^T (attn_f32_max_seq)
+_SHORT_HEAD, _SHORT_MAX_SEQ = 64, 128                         # ts_attention_short (bf16): head size, tokens (kAttnRowsMaxSeq)
+_GQA_HEAD, _GQA_MAX_SEQ = 128, 128                            # ts_attention_gqa (bf16): head size, tokens (kAttnGqaRowsMaxSeq)
+_NORM_MAX_VECS = 256                                          # the norm kernels: 16-byte accesses per row (64 lanes x kLnMax)
 
 
 def float_attention_applies(x: torch.Tensor, S: int, hd: int) -> bool:
@@ -158,15 +151,13 @@ class FusedBertForward:
         if getattr(cfg, "position_embedding_type", "absolute") != "absolute" or getattr(cfg, "is_decoder", False):
             return False
         p = next(model.parameters())
-        return (p.is_cuda and p.dtype in (torch.float32, torch.bfloat16) and cfg.hidden_size % 8 == 0 and cfg.hidden_size <= 1024
+        return (p.is_cuda and p.dtype in (torch.float32, torch.bfloat16) and cfg.hidden_size % 8 == 0 and cfg.hidden_size <= _NORM_MAX_VECS * 4
                 and cfg.hidden_size % cfg.num_attention_heads == 0)
 
     def _embed(self, input_ids: torch.Tensor, token_type_ids: Optional[torch.Tensor]) -> torch.Tensor:
         """BertEmbeddings (word + token type + position, LayerNorm; dropout is the identity in eval) as ONE HIP kernel
         (``ts_embed_layernorm``) instead of three gathers, two adds and a layer_norm launch.  Anything the kernel's form does not
         cover (a sequence longer than the position table, a module without the three tables) runs the module itself."""
-        import ctypes as C
-        from . import _ffi
         emb = self.model.embeddings
         tables = [getattr(emb, n, None) for n in ("word_embeddings", "position_embeddings", "token_type_embeddings")]
         ln = getattr(emb, "LayerNorm", None)
@@ -178,50 +169,31 @@ class FusedBertForward:
         tt = token_type_ids.contiguous().to(torch.int64) if token_type_ids is not None else None
         H = w.shape[1]
         out = torch.empty((B, S, H), dtype=w.dtype, device=w.device)
-        _ffi.check(_ffi.load().ts_embed_layernorm(
-            w.device.index or 0, C.c_void_p(ids.data_ptr()), C.c_void_p(tt.data_ptr()) if tt is not None else None,
-            C.c_void_p(w.data_ptr()), C.c_void_p(p.data_ptr()), C.c_void_p(t.data_ptr()), w.shape[0], p.shape[0], t.shape[0],
-            C.c_void_p(ln.weight.data_ptr()), C.c_void_p(ln.bias.data_ptr()), self.eps, B * S, S, H,
-            1 if w.dtype == torch.bfloat16 else 0, C.c_void_p(out.data_ptr()),
-            C.c_void_p(torch.cuda.current_stream(w.device).cuda_stream)))
+        _ffi.encoder_op("ts_embed_layernorm", w, ids, tt, w, p, t, w.shape[0], p.shape[0], t.shape[0], ln.weight, ln.bias, self.eps,
+                        B * S, S, H, 1 if w.dtype == torch.bfloat16 else 0, out)
         return out
 
     def _attention(self, qkv: torch.Tensor, key_mask: Optional[torch.Tensor], B: int, S: int) -> torch.Tensor:
-        import ctypes as C
-        from . import _ffi
         qkv = qkv.contiguous()
-        out = torch.empty((B, S, self.heads * 64), dtype=torch.bfloat16, device=qkv.device)
-        _ffi.check(_ffi.load().ts_attention_short(
-            qkv.device.index or 0, C.c_void_p(qkv.data_ptr()), C.c_void_p(key_mask.data_ptr()) if key_mask is not None else None,
-            B, S, self.heads, 64, C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream)))
+        out = torch.empty((B, S, self.heads * _SHORT_HEAD), dtype=torch.bfloat16, device=qkv.device)
+        _ffi.encoder_op("ts_attention_short", qkv, qkv, key_mask, B, S, self.heads, _SHORT_HEAD, out)
         return out
 
     def _add_ln_pieces(self, a: torch.Tensor, b: torch.Tensor, ln, a_bias: Optional[torch.Tensor] = None):
         """`_add_ln` of fp32 operands (``a + a_bias + b``) that also writes the pieces of its output: ``(out fp32, pieces bf16
         [rows x 3d])``."""
-        import ctypes as C
-        from . import _ffi
         a, b = a.contiguous(), b.contiguous()
         out = torch.empty_like(a)
         rows, d = a.numel() // a.shape[-1], a.shape[-1]
         pieces = torch.empty((rows, 3 * d), dtype=torch.bfloat16, device=a.device)
-        _ffi.check(_ffi.load().ts_add_layernorm_pieces(
-            a.device.index or 0, C.c_void_p(a.data_ptr()), C.c_void_p(a_bias.data_ptr()) if a_bias is not None else None,
-            C.c_void_p(b.data_ptr()), C.c_void_p(ln.weight.data_ptr()),
-            C.c_void_p(ln.bias.data_ptr()), self.eps, rows, d, C.c_void_p(out.data_ptr()), C.c_void_p(pieces.data_ptr()),
-            C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)))
+        _ffi.encoder_op("ts_add_layernorm_pieces", a, a, a_bias, b, ln.weight, ln.bias, self.eps, rows, d, out, pieces)
         return out, pieces
 
     def _add_ln(self, a: torch.Tensor, b: torch.Tensor, ln) -> torch.Tensor:
-        import ctypes as C
-        from . import _ffi
         a, b = a.contiguous(), b.contiguous()
         out = torch.empty_like(a)
         rows, d = a.numel() // a.shape[-1], a.shape[-1]
-        _ffi.check(_ffi.load().ts_add_layernorm(
-            a.device.index or 0, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(ln.weight.data_ptr()),
-            C.c_void_p(ln.bias.data_ptr()), self.eps, rows, d, 1 if a.dtype == torch.bfloat16 else 0, C.c_void_p(out.data_ptr()),
-            C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)))
+        _ffi.encoder_op("ts_add_layernorm", a, a, b, ln.weight, ln.bias, self.eps, rows, d, 1 if a.dtype == torch.bfloat16 else 0, out)
         return out
 
     def __call__(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, token_type_ids: Optional[torch.Tensor] = None,
@@ -236,7 +208,7 @@ class FusedBertForward:
         # padding (every sequence as long as the batch: 50 instead of 60 us per layer for projections + attention)
         # short sequences (one sentence per query: app_showcase_model.py:92) of a bf16 model with 64-wide heads: the attention as
         # ONE wave per (sequence, head), straight from the fused projection to the context layout (``ts_attention_short``)
-        short = x.dtype == torch.bfloat16 and hd == 64 and S <= 128 and os.environ.get("TS_ENCODER_ATTENTION", "1") != "0"
+        short = x.dtype == torch.bfloat16 and hd == _SHORT_HEAD and S <= _SHORT_MAX_SEQ and os.environ.get("TS_ENCODER_ATTENTION", "1") != "0"
         # (the most negative finite value, not -inf: a sequence without a single token would otherwise soften to NaN)
         short32 = float_attention_applies(x, S, hd)          # fp32: the library's fp32 attention (ts_attention_float)
         mask = None if (no_padding or short or short32) else torch.zeros((B, 1, 1, S), dtype=x.dtype, device=x.device).masked_fill_(
@@ -350,36 +322,25 @@ class FusedQwen3Forward:
         p = next(model.parameters())
         vec = 8 if p.dtype == torch.bfloat16 else 4
         return (p.is_cuda and p.dtype in (torch.float32, torch.bfloat16) and cfg.hidden_size % vec == 0 and
-                cfg.hidden_size <= 256 * vec and cfg.intermediate_size % vec == 0 and
+                cfg.hidden_size <= _NORM_MAX_VECS * vec and cfg.intermediate_size % vec == 0 and
                 cfg.num_attention_heads % cfg.num_key_value_heads == 0)
 
     def _add_rmsnorm(self, a: torch.Tensor, b: Optional[torch.Tensor], gamma: torch.Tensor, want_sum: bool):
-        import ctypes as C
-        from . import _ffi
         d = a.shape[-1]
         rows = a.numel() // d
         out = torch.empty_like(a)
         new_res = torch.empty_like(a) if (want_sum and b is not None) else None
-        _ffi.check(_ffi.load().ts_add_rmsnorm(
-            a.device.index or 0, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()) if b is not None else None,
-            C.c_void_p(gamma.data_ptr()), self.eps, rows, d, 1 if a.dtype == torch.bfloat16 else 0,
-            C.c_void_p(new_res.data_ptr()) if new_res is not None else None, C.c_void_p(out.data_ptr()),
-            C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)))
+        _ffi.encoder_op("ts_add_rmsnorm", a, a, b, gamma, self.eps, rows, d, 1 if a.dtype == torch.bfloat16 else 0, new_res, out)
         return (new_res if new_res is not None else a), out
 
     def _add_rmsnorm_pieces(self, a: torch.Tensor, b: Optional[torch.Tensor], gamma: torch.Tensor, want_sum: bool):
         """`_add_rmsnorm` of fp32 operands that also writes the pieces of the normalised rows: ``(residual, normed, pieces)``."""
-        import ctypes as C
-        from . import _ffi
         d = a.shape[-1]
         rows = a.numel() // d
         out = torch.empty_like(a)
         new_res = torch.empty_like(a) if (want_sum and b is not None) else None
         pieces = torch.empty((rows, 3 * d), dtype=torch.bfloat16, device=a.device)
-        _ffi.check(_ffi.load().ts_add_rmsnorm_pieces(
-            a.device.index or 0, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()) if b is not None else None,
-            C.c_void_p(gamma.data_ptr()), self.eps, rows, d, C.c_void_p(new_res.data_ptr()) if new_res is not None else None,
-            C.c_void_p(out.data_ptr()), C.c_void_p(pieces.data_ptr()), C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)))
+        _ffi.encoder_op("ts_add_rmsnorm_pieces", a, a, b, gamma, self.eps, rows, d, new_res, out, pieces)
         return (new_res if new_res is not None else a), out, pieces
 
     def _sdpa(self, qkv: torch.Tensor, mask: Optional[torch.Tensor], B: int, S: int, nq: int, nkv: int, hd: int) -> torch.Tensor:
@@ -402,23 +363,18 @@ class FusedQwen3Forward:
 
     def __call__(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, token_type_ids: Optional[torch.Tensor] = None,
                  no_padding: bool = False):
-        import ctypes as C
-        from . import _ffi
         F = torch.nn.functional
-        lib = _ffi.load()
         self._refresh()
         m = self.model
         x = m.embed_tokens(input_ids).contiguous()
         B, S, H = x.shape
         dt = 1 if x.dtype == torch.bfloat16 else 0
-        dev = x.device.index or 0
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         pos = torch.arange(S, device=x.device).unsqueeze(0)              # positions count from the left edge, padding included
         cos, sin = m.rotary_emb(x, pos)                                  # [1 x S x 128] of the model's type
         cos, sin = cos[0].contiguous(), sin[0].contiguous()
         mask = None
         # short sequences in bf16: the library's own causal grouped-query attention (TS_ENCODER_ATTENTION=0 keeps torch's)
-        short = (x.dtype == torch.bfloat16 and self.hd == 128 and S <= 128 and x.is_contiguous() and
+        short = (x.dtype == torch.bfloat16 and self.hd == _GQA_HEAD and S <= _GQA_MAX_SEQ and x.is_contiguous() and
                  os.environ.get("TS_ENCODER_ATTENTION", "1") != "0")
         short32 = float_attention_applies(x, S, self.hd)      # fp32: the library's fp32 attention (causal, grouped-query)
         key_mask = None if (no_padding or not (short or short32)) else attention_mask.to(torch.int64).contiguous()
@@ -436,9 +392,7 @@ class FusedQwen3Forward:
             _, h, hp = self._add_rmsnorm_pieces(x, None, self.layers[0]["ln1"], False)
             for li, L in enumerate(self.layers):
                 qkv = pieces_mm(hp, L["wqkv_p"]).view(B, S, -1)
-                _ffi.check(lib.ts_qk_norm_rope(dev, C.c_void_p(qkv.data_ptr()), C.c_void_p(L["qn"].data_ptr()), C.c_void_p(L["kn"].data_ptr()),
-                                               C.c_void_p(cos.data_ptr()), C.c_void_p(sin.data_ptr()), self.eps, B * S, S, self.hq, self.hkv,
-                                               hd, dt, stream))
+                _ffi.encoder_op("ts_qk_norm_rope", x, qkv, L["qn"], L["kn"], cos, sin, self.eps, B * S, S, self.hq, self.hkv, hd, dt)
                 if short32:
                     cp = attention_float(qkv, key_mask, B, S, self.hq, self.hkv, hd, True, hd ** -0.5, want_pieces=True, want_context=False)[1]
                 else:
@@ -452,14 +406,11 @@ class FusedQwen3Forward:
         h = self._add_rmsnorm(x, None, self.layers[0]["ln1"], False)[1]
         for li, L in enumerate(self.layers):
             qkv = F.linear(h, L["wqkv"])
-            _ffi.check(lib.ts_qk_norm_rope(dev, C.c_void_p(qkv.data_ptr()), C.c_void_p(L["qn"].data_ptr()), C.c_void_p(L["kn"].data_ptr()),
-                                           C.c_void_p(cos.data_ptr()), C.c_void_p(sin.data_ptr()), self.eps, B * S, S, self.hq, self.hkv,
-                                           hd, dt, stream))
+            _ffi.encoder_op("ts_qk_norm_rope", x, qkv, L["qn"], L["kn"], cos, sin, self.eps, B * S, S, self.hq, self.hkv, hd, dt)
             if short:
                 # one wave per (sequence, query head), straight from the stacked projection's output (ts_attention_gqa)
                 ctx = torch.empty((B, S, nq), dtype=x.dtype, device=x.device)
-                _ffi.check(lib.ts_attention_gqa(dev, C.c_void_p(qkv.data_ptr()), C.c_void_p(key_mask.data_ptr()) if key_mask is not None else None,
-                                               B, S, self.hq, self.hkv, hd, 1, C.c_void_p(ctx.data_ptr()), stream))
+                _ffi.encoder_op("ts_attention_gqa", x, qkv, key_mask, B, S, self.hq, self.hkv, hd, 1, ctx)
             elif short32:
                 ctx = attention_float(qkv, key_mask, B, S, self.hq, self.hkv, hd, True, hd ** -0.5)[0]
             else:
@@ -468,7 +419,7 @@ class FusedQwen3Forward:
             gu = F.linear(h, L["wgu"])
             inter = gu.shape[-1] // 2
             act = torch.empty((B, S, inter), dtype=x.dtype, device=x.device)
-            _ffi.check(lib.ts_swiglu(dev, C.c_void_p(gu.data_ptr()), B * S, inter, dt, C.c_void_p(act.data_ptr()), stream))
+            _ffi.encoder_op("ts_swiglu", x, gu, B * S, inter, dt, act)
             last = li + 1 == len(self.layers)
             gamma = m.norm.weight if last else self.layers[li + 1]["ln1"]
             x, h = self._add_rmsnorm(x, F.linear(act, L["wd"]), gamma, not last)
@@ -542,21 +493,15 @@ class FusedGemma3Forward:
         p = next(model.parameters())
         vec = 8 if p.dtype == torch.bfloat16 else 4
         return (p.is_cuda and p.dtype in (torch.float32, torch.bfloat16) and cfg.hidden_size % vec == 0 and
-                cfg.hidden_size <= 256 * vec and cfg.intermediate_size % vec == 0 and
+                cfg.hidden_size <= _NORM_MAX_VECS * vec and cfg.intermediate_size % vec == 0 and
                 cfg.num_attention_heads % cfg.num_key_value_heads == 0)
 
     def _norm(self, y: Optional[torch.Tensor], x: torch.Tensor, w_post: Optional[torch.Tensor], w_next: torch.Tensor, want_sum: bool):
-        import ctypes as C
-        from . import _ffi
         d = x.shape[-1]
         rows = x.numel() // d
         out = torch.empty_like(x)
         new_res = torch.empty_like(x) if (want_sum and y is not None) else None
-        _ffi.check(_ffi.load().ts_gemma_norm(
-            x.device.index or 0, C.c_void_p(y.data_ptr()) if y is not None else None, C.c_void_p(x.data_ptr()),
-            C.c_void_p(w_post.data_ptr()) if w_post is not None else None, C.c_void_p(w_next.data_ptr()), self.eps, rows, d,
-            1 if x.dtype == torch.bfloat16 else 0, C.c_void_p(new_res.data_ptr()) if new_res is not None else None,
-            C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+        _ffi.encoder_op("ts_gemma_norm", x, y, x, w_post, w_next, self.eps, rows, d, 1 if x.dtype == torch.bfloat16 else 0, new_res, out)
         return (new_res if new_res is not None else x), out
 
     def _sdpa(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor]) -> torch.Tensor:
@@ -573,35 +518,24 @@ class FusedGemma3Forward:
 
     def _norm_pieces(self, y: Optional[torch.Tensor], x: torch.Tensor, w_post: Optional[torch.Tensor], w_next: torch.Tensor, want_sum: bool):
         """`_norm` of fp32 operands that also writes the pieces of the pre-normed rows: ``(residual, normed, pieces)``."""
-        import ctypes as C
-        from . import _ffi
         d = x.shape[-1]
         rows = x.numel() // d
         out = torch.empty_like(x)
         new_res = torch.empty_like(x) if (want_sum and y is not None) else None
         pieces = torch.empty((rows, 3 * d), dtype=torch.bfloat16, device=x.device)
-        _ffi.check(_ffi.load().ts_gemma_norm_pieces(
-            x.device.index or 0, C.c_void_p(y.data_ptr()) if y is not None else None, C.c_void_p(x.data_ptr()),
-            C.c_void_p(w_post.data_ptr()) if w_post is not None else None, C.c_void_p(w_next.data_ptr()), self.eps, rows, d,
-            C.c_void_p(new_res.data_ptr()) if new_res is not None else None, C.c_void_p(out.data_ptr()), C.c_void_p(pieces.data_ptr()),
-            C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+        _ffi.encoder_op("ts_gemma_norm_pieces", x, y, x, w_post, w_next, self.eps, rows, d, new_res, out, pieces)
         return (new_res if new_res is not None else x), out, pieces
 
     def __call__(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, token_type_ids: Optional[torch.Tensor] = None,
                  no_padding: bool = False):
-        import ctypes as C
-        from . import _ffi
         F = torch.nn.functional
         B, S = input_ids.shape
         if S >= int(self.cfg.sliding_window):                        # the sliding layers would hide keys: the model's own masks
             return self.model(input_ids=input_ids, attention_mask=attention_mask).last_hidden_state
-        lib = _ffi.load()
         self._refresh()
         m = self.model
         x = m.embed_tokens(input_ids).contiguous()                    # scaled by sqrt(hidden) in the storage type, as the module does
         dt = 1 if x.dtype == torch.bfloat16 else 0
-        dev = x.device.index or 0
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         pos = torch.arange(S, device=x.device).unsqueeze(0)
         tables = {}
         for lt in set(self.cfg.layer_types):
@@ -624,9 +558,7 @@ class FusedGemma3Forward:
         for li, L in enumerate(self.layers):
             qkv = pieces_mm(hp, L["wqkv_p"]).view(B, S, -1) if pieces else F.linear(h, L["wqkv"])
             cos, sin = tables[L["type"]]
-            _ffi.check(lib.ts_gemma_qk_norm_rope(dev, C.c_void_p(qkv.data_ptr()), C.c_void_p(L["qn"].data_ptr()), C.c_void_p(L["kn"].data_ptr()),
-                                                 C.c_void_p(cos.data_ptr()), C.c_void_p(sin.data_ptr()), self.eps, B * S, S, self.hq, self.hkv,
-                                                 hd, dt, stream))
+            _ffi.encoder_op("ts_gemma_qk_norm_rope", x, qkv, L["qn"], L["kn"], cos, sin, self.eps, B * S, S, self.hq, self.hkv, hd, dt)
             cp = None
             if short32:
                 ctx, cp = attention_float(qkv, key_mask, B, S, self.hq, self.hkv, hd, False, self.scaling, want_pieces=pieces, want_context=not pieces)
@@ -649,6 +581,6 @@ class FusedGemma3Forward:
             gu = F.linear(h, L["wgu"])
             inter = gu.shape[-1] // 2
             act = torch.empty((B, S, inter), dtype=x.dtype, device=x.device)
-            _ffi.check(lib.ts_geglu(dev, C.c_void_p(gu.data_ptr()), B * S, inter, dt, C.c_void_p(act.data_ptr()), stream))
+            _ffi.encoder_op("ts_geglu", x, gu, B * S, inter, dt, act)
             x, h = self._norm(F.linear(act, L["wd"]), x, L["ln_post_ffn"], w_next, not last)
         return h
