@@ -1,7 +1,7 @@
 """References, bounds, inputs and guarded buffers for the direct tests of the encoder's fp32-path kernels
-(tests/test_encoder_ref_cpu.py, test_encoder_pieces_gpu.py, test_encoder_edges_gpu.py).  Plain torch, no library: everything
-here runs without a GPU, and test_encoder_ref_cpu.py shows that a correct fp32 implementation passes each bound with room and
-that each checker rejects the corruptions a wrong kernel would produce.
+(tests/test_encoder_ref_cpu.py, test_encoder_pieces_gpu.py, test_encoder_edges_gpu.py, test_encoder_rope_act_gpu.py).  Plain
+torch, no library: everything here runs without a GPU, and test_encoder_ref_cpu.py shows that a correct fp32 implementation
+passes each bound with room and that each checker rejects the corruptions a wrong kernel would produce.
 
 Bounds (none of them comes from what the kernels return):
 * pieces of an activation: |hi + lo - y64| <= 2^-16 |y64| + 2^-20 max(1, |g|) max(1, |u|).  The first term is what two
@@ -12,6 +12,11 @@ Bounds (none of them comes from what the kernels return):
   value itself, not a truncated or a neighbouring one).  Exact rounding reaches this bound by itself just above a power of
   two, so it has no factor to spare: only the floor separates it from a correct kernel.
 * norms: atol = rtol = 2e-5 (fp32) / 2e-2 (bf16) against fp64, the project's tolerances for these kernels.
+* per-head norm + rotary (ts_qk_norm_rope, ts_gemma_qk_norm_rope): per element, against A + B = y cos + rot sin in fp64,
+  |got - (A + B)| <= (K u (1 + 2^-6) [+ 2^-20]) (|A| + |B|): K roundings of u each (ROPE_K), second-order terms in the 2^-6,
+  and for bf16 2^-20 for the fp32 arithmetic in between (rsqrtf, the 128 / 256-term sum).  An all-zero head has bound 0.
+* gated activations (ts_swiglu, ts_geglu): K u |y| [(1 + 2^-6) for bf16] + pieces_floor(g, u), K = 2 roundings in bf16 (the
+  activation, the product), GATED_K_F32 in fp32; the floor is the activation's own fp32 error, as for the pieces.
 """
 import math
 
@@ -39,6 +44,37 @@ ACT_SPECIALS = (0.0, -0.0, 1e-30, -1e-30, 5.5, -5.5, 8.0, -8.0, 30.0, -30.0, 100
 GRID_CAP_THREADS = 16384 * 256
 GRID_STRIDE_ROWS, GRID_STRIDE_N = 8192, 4096                 # rows * n / 4 = 8,388,608 = 2 * GRID_CAP_THREADS
 assert GRID_STRIDE_ROWS * (GRID_STRIDE_N // 4) == 2 * GRID_CAP_THREADS
+
+# per-head norm + rotary: a head is hd / VEC lanes of a wave (16 or 32 in bf16, 32 or 64 in fp32), so a wave holds 4, 2 or 1
+# (token, head) items and a workgroup of four waves 16, 8 or 4.  (tokens, seq, q heads, kv heads):
+ROPE_SHAPES = ((1, 1, 1, 1),        # 2 items: idle groups or idle waves in the only workgroup
+               (3, 3, 2, 1),        # 9 items: one live group in the last wave
+               (7, 7, 2, 1),        # 21 items: a second, partial workgroup that ends in idle groups
+               (5, 8, 3, 1),        # seq > tokens
+               (10, 4, 2, 2),       # tokens not a multiple of seq, hq == hkv
+               (6, 1, 4, 4),        # seq == 1
+               (259, 7, 3, 1),      # Gemma3's own head counts
+               (185, 37, 16, 8))    # Qwen3's own head counts
+ROPE_HEAD = {False: 128, True: 256}                          # by `gemma`: ts_qk_norm_rope serves 128, ts_gemma_qk_norm_rope 256
+ROPE_EPS = 1e-6
+ROPE_HEAD_SCALES = {"zero": 0.0, "small": 1e-4, "big": 300.0}
+ROPE_PREFIX_SHAPE, ROPE_PREFIXES = (23, 7, 2, 1), (1, 2, 3, 5, 6, 7, 22)      # 3 heads a token: 3, 6, 9, 15, ... items
+UNIT = {torch.float32: 2.0 ** -24, torch.bfloat16: 2.0 ** -8}
+# roundings of u each between the stored operands and the stored answer, by (gemma, storage type).
+# bf16: Qwen3 x r | w . | the product with cos / sin | the sum;  Gemma3 the norm (rounded once) | the product | the sum.
+# fp32: twice what torch's fp32 evaluation of the kernel's sequence (rope_emulate) reaches against rope_ref over ROPE_SHAPES'
+# inputs, rounded up: measured 4.83 u (Qwen3) and 5.48 u (Gemma3) of |A| + |B| (tests/test_encoder_ref_cpu.py prints them)
+ROPE_K = {(False, torch.bfloat16): 4, (True, torch.bfloat16): 3, (False, torch.float32): 10, (True, torch.float32): 11}
+
+# gated activations: inter of one access (VEC), one access short of a wave's (fp32) / half a wave's (bf16), two ordinary ones
+GATED_WIDTHS = {torch.float32: (4, 252, 1024, 3072), torch.bfloat16: (8, 248, 1024, 3072)}
+GATED_ROWS = (1, 5, 259)
+GATED_STRIDE = {torch.float32: (8192, 4096), torch.bfloat16: (8192, 8192)}   # rows, inter: rows * inter / VEC = 2 * GRID_CAP_THREADS
+assert all(r * (n // (16 // torch.empty((), dtype=t).element_size())) == 2 * GRID_CAP_THREADS for t, (r, n) in GATED_STRIDE.items())
+# fp32: K u |y| + pieces_floor.  On gated_inputs act_fp32 never leaves the floor (measured: 0 u beyond it, 0.147 (SwiGLU) and
+# 0.144 (GeGLU) of the bound below; tests/test_encoder_ref_cpu.py prints them), so twice the measurement would be K = 0.  K is
+# the two fp32 roundings the kernel adds to the activation's own error instead: the activation's result and the product.
+GATED_K_F32 = {1: 2, 2: 2}
 
 
 # ---- bf16 pieces ----------------------------------------------------------------------------------------------------------
@@ -194,6 +230,124 @@ def act_inputs(kind: int, n: int, rows: int):
     x[:, cols] = torch.tensor(ACT_SPECIALS, dtype=torch.float32)[pick]
     bias = torch.randn(width, generator=g)
     return x, bias
+
+
+def gated_inputs(kind: int, inter: int, rows: int, dtype) -> torch.Tensor:
+    """gate_up [rows x 2 inter] of the storage type: act_inputs' values (the specials in gate and up columns alike), no bias."""
+    return act_inputs(kind, inter, rows)[0].to(dtype)
+
+
+def rope_special_heads(tokens: int, hq: int, hkv: int) -> dict:
+    """Where rope_inputs puts its special heads: name -> (token, head), head counted over queries then keys.  The all-zero
+    head is the last item (the one live group of a last wave), and item 0 stays ordinary; two items hold two specials."""
+    heads = hq + hkv
+    items = tokens * heads
+    at = {"zero": items - 1, "small": items // 2, "big": 1} if items >= 4 else {"zero": 1, "small": 0}
+    return {name: divmod(i, heads) for name, i in at.items()}
+
+
+def rope_inputs(tokens: int, seq: int, hq: int, hkv: int, gemma: bool, dtype):
+    """qkv [tokens x (hq + 2 hkv) hd] ~ N(0, 1.3^2) with the heads of rope_special_heads scaled by ROPE_HEAD_SCALES (at 1e-4
+    eps = 1e-6 dominates the mean square), wq, wk [hd] = 1 + 0.3 N (Qwen3) / 0.3 N (Gemma3: the kernel adds the 1), cos, sin
+    [seq x hd] of an independent uniform angle per (position, element): the two halves of a row differ and no sin is
+    systematically small.  All of the storage type."""
+    hd = ROPE_HEAD[gemma]
+    g = _gen(6, tokens, seq, hq, hkv, int(gemma))
+    qkv = torch.randn((tokens, hq + 2 * hkv, hd), generator=g) * 1.3
+    for name, (tok, h) in rope_special_heads(tokens, hq, hkv).items():
+        qkv[tok, h] = qkv[tok, h] * ROPE_HEAD_SCALES[name] if ROPE_HEAD_SCALES[name] else 0.0      # (+0, not randn's signs)
+    wq, wk = ((0.0 if gemma else 1.0) + 0.3 * torch.randn(hd, generator=g) for _ in range(2))
+    ang = torch.rand((seq, hd), generator=g) * (2.0 * math.pi)
+    return tuple(t.to(dtype).contiguous() for t in (qkv.view(tokens, -1), wq, wk, torch.cos(ang), torch.sin(ang)))
+
+
+def rope_operands(qkv, wq, wk, cos, sin, seq, hq, hkv, hd, to):
+    """x [tokens x heads x hd] (queries, then keys), w [heads x hd], cos / sin [tokens x 1 x hd] at pos = tok % seq, in `to`."""
+    tokens = qkv.shape[0]
+    x = qkv.view(tokens, hq + 2 * hkv, hd)[:, :hq + hkv].to(to)
+    w = torch.cat((wq.to(to).expand(hq, hd), wk.to(to).expand(hkv, hd)))
+    pos = torch.arange(tokens, device=qkv.device) % seq
+    return x, w, cos.to(to)[pos][:, None, :], sin.to(to)[pos][:, None, :]
+
+
+def rope_ref(qkv, wq, wk, cos, sin, seq: int, hq: int, hkv: int, hd: int, eps: float, gemma: bool):
+    """fp64 on the stored operands, no intermediate rounding: r = rsqrt(mean_hd(x^2) + eps), y = x r w (Qwen3) / x r (1 + w)
+    (Gemma3), rot = (-y[hd/2:], y[:hd/2]), A = y cos[pos], B = rot sin[pos], pos = tok % seq.  eps as the fp32 the entry takes.
+    Returns (A + B, |A| + |B|) [tokens x (hq + hkv) x hd] fp64 and the value heads [tokens x hkv hd] as stored."""
+    eps = float(torch.tensor(eps, dtype=torch.float32))
+    x, w, c, s = rope_operands(qkv, wq, wk, cos, sin, seq, hq, hkv, hd, torch.float64)
+    y = x * torch.rsqrt((x * x).mean(-1, keepdim=True) + eps) * (1.0 + w if gemma else w)
+    rot = torch.cat((-y[..., hd // 2:], y[..., :hd // 2]), dim=-1)
+    A, B = y * c, rot * s
+    return A + B, A.abs() + B.abs(), qkv[:, (hq + hkv) * hd:]
+
+
+def rope_emulate(qkv, wq, wk, cos, sin, seq: int, hq: int, hkv: int, hd: int, eps: float, gemma: bool) -> torch.Tensor:
+    """The kernel's own sequence in torch (kernels_encoder.h, qk_norm_rope_kernel): fp32 arithmetic, rounded to the storage type
+    where the kernel rounds - y = round(w round(x r)) (Qwen3) / round((x r)(1 + w)) (Gemma3), out = round(round(y cos) +
+    round(rot sin)).  Returns the whole qkv in the storage type, value heads copied."""
+    def rd(t):
+        return t.to(qkv.dtype).float()
+    x, w, c, s = rope_operands(qkv, wq, wk, cos, sin, seq, hq, hkv, hd, torch.float32)
+    r = torch.rsqrt((x * x).sum(-1, keepdim=True) / float(hd) + torch.tensor(eps, dtype=torch.float32))
+    y = rd((x * r) * (1.0 + w)) if gemma else rd(w * rd(x * r))
+    rot = torch.cat((-y[..., hd // 2:], y[..., :hd // 2]), dim=-1)
+    out = qkv.clone()
+    out.view(qkv.shape[0], hq + 2 * hkv, hd)[:, :hq + hkv] = (rd(y * c) + rd(rot * s)).to(qkv.dtype)
+    return out
+
+
+def rope_bound(mag: torch.Tensor, dtype, gemma: bool) -> torch.Tensor:
+    rel = ROPE_K[(bool(gemma), dtype)] * UNIT[dtype] * (1.0 + 2.0 ** -6)
+    return (rel + (2.0 ** -20 if dtype == torch.bfloat16 else 0.0)) * mag     # fp32: ROPE_K is measured with the fp32 parts in it
+
+
+def rope_ratio(got, qkv, wq, wk, cos, sin, seq: int, hq: int, hkv: int, hd: int, eps: float, gemma: bool) -> torch.Tensor:
+    """error / bound per query / key element [tokens x (hq + hkv) x hd]; 0 where a zero bound is met exactly, 1e30 where the
+    error is not finite or a zero bound is missed."""
+    got, qkv, wq, wk, cos, sin = (t.detach().cpu() for t in (got, qkv, wq, wk, cos, sin))
+    want, mag, _ = rope_ref(qkv, wq, wk, cos, sin, seq, hq, hkv, hd, eps, gemma)
+    err = (got.view(got.shape[0], hq + 2 * hkv, hd)[:, :hq + hkv].double() - want).abs()
+    ratio = (err / rope_bound(mag, qkv.dtype, gemma)).nan_to_num(nan=1e30, posinf=1e30)
+    return torch.where((mag == 0) & (err == 0), torch.zeros_like(ratio), ratio)
+
+
+def check_rope(got, qkv, wq, wk, cos, sin, seq: int, hq: int, hkv: int, hd: int, eps: float, gemma: bool, bound_scale: float = 1.0) -> float:
+    """Assert that `got` is the in-place answer for `qkv`: every query / key element within rope_bound, the value heads bit for
+    bit the input's, no NaN, the all-zero head zeros.  Returns the worst error / bound."""
+    assert got.shape == qkv.shape and got.dtype == qkv.dtype, (got.shape, got.dtype)
+    assert not torch.isnan(got).any(), f"{int(torch.isnan(got).sum())} NaN"
+    assert same_bits(got[:, (hq + hkv) * hd:], qkv[:, (hq + hkv) * hd:]), "the value heads changed"
+    ratio = rope_ratio(got, qkv, wq, wk, cos, sin, seq, hq, hkv, hd, eps, gemma) / bound_scale
+    worst = float(ratio.max())
+    assert worst <= 1.0, f"{int((ratio > 1).sum())} of {ratio.numel()} elements off, worst error / bound {worst:.3g}, first at (token, head, element) {tuple(int(i) for i in (ratio > 1).nonzero()[0])}"
+    tok, h = rope_special_heads(qkv.shape[0], hq, hkv)["zero"]
+    assert not got.view(got.shape[0], hq + 2 * hkv, hd)[tok, h].any(), "the all-zero head is not zeros"
+    return worst
+
+
+def gated_bound(y64: torch.Tensor, g: torch.Tensor, u: torch.Tensor, kind: int, dtype) -> torch.Tensor:
+    rel = 2.0 * UNIT[dtype] * (1.0 + 2.0 ** -6) if dtype == torch.bfloat16 else GATED_K_F32[kind] * UNIT[dtype]
+    return rel * y64.abs() + pieces_floor(g, u)
+
+
+def gated_ratio(out: torch.Tensor, gate_up: torch.Tensor, kind: int) -> torch.Tensor:
+    """error / bound per element of `out` [rows x inter] for gate_up [rows x 2 inter] (both of the storage type), kind 1 SwiGLU /
+    2 GeGLU; 1e30 where the error is not finite."""
+    out, gate_up = out.detach().cpu(), gate_up.detach().cpu()
+    assert out.dtype == gate_up.dtype and tuple(out.shape) == (gate_up.shape[0], gate_up.shape[1] // 2), (out.dtype, out.shape)
+    y64 = act_ref(gate_up, None, kind)
+    g, u = act_operands(gate_up, None, kind)
+    return ((out.double() - y64).abs() / gated_bound(y64, g, u, kind, out.dtype)).nan_to_num(nan=1e30, posinf=1e30)
+
+
+def check_gated(out: torch.Tensor, gate_up: torch.Tensor, kind: int, bound_scale: float = 1.0) -> float:
+    """Assert that every element of `out` is within gated_bound of the fp64 activation and none is NaN.  Returns the worst ratio."""
+    assert not torch.isnan(out).any(), f"{int(torch.isnan(out).sum())} NaN"
+    ratio = gated_ratio(out, gate_up, kind) / bound_scale
+    worst = float(ratio.max())
+    assert worst <= 1.0, f"{int((ratio > 1).sum())} of {ratio.numel()} elements off, worst error / bound {worst:.3g}"
+    return worst
 
 
 # ---- fp64 references of the norms ------------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 """What the GPU tests of the encoder's fp32-path kernels rest on, checked without a GPU (tests/encoder_common.py):
 * the references pass their own bounds: on the inputs of tests/test_encoder_pieces_gpu.py torch's own fp32 evaluation of each
-  formula, split into pieces by split_ref, passes the bound the GPU test uses - with a factor 2 to spare;
+  formula, split into pieces by split_ref, passes the bound the GPU test uses - with a factor 2 to spare; so do the gated
+  activations cast to the storage type and, in fp32, torch's emulation of the rotary kernel's arithmetic on the inputs of
+  tests/test_encoder_rope_act_gpu.py (in bf16 that emulation performs every rounding the bound counts and passes the bound);
 * the checks have teeth: each corrupted answer a wrong kernel could give is rejected;
 * the argument contract of every encoder entry point: every refusal returns before the device check (the library loads
   without a device; a refusal never dereferences a pointer, so aligned fake ones do).
@@ -113,6 +115,52 @@ def test_fp32_attention_and_pooling_references_agree_with_torch(capsys):
     assert not ec.pool_ref(hidden, holes, 0, True)[2].any() and not ec.pool_ref(hidden, holes, 0, False)[2].any()
 
 
+F32, BF16 = torch.float32, torch.bfloat16
+ROPE_CASES = [(gemma, dtype) for gemma in (False, True) for dtype in (F32, BF16)]
+ROPE_IDS = [f"{'gemma3' if gemma else 'qwen3'}-{'fp32' if dtype == F32 else 'bf16'}" for gemma, dtype in ROPE_CASES]
+
+
+@pytest.mark.parametrize("gemma,dtype", ROPE_CASES, ids=ROPE_IDS)
+def test_the_kernels_arithmetic_in_torch_passes_the_rotary_bound(gemma, dtype, capsys):
+    """rope_emulate (the kernel's sequence and rounding points, torch's fp32) against rope_ref on every input of the GPU test.
+    fp32: half the bound - ROPE_K is twice what this test measures, and the printed figure is that measurement.  bf16: the
+    bound itself.  It counts the K roundings of the sequence at their worst case of u each and the emulation performs all K,
+    so it comes close (0.79 Qwen3, 0.90 Gemma3) and nothing like a factor 2 is left; the corruptions below miss by far more."""
+    hd = ec.ROPE_HEAD[gemma]
+    worst, heads = 0.0, {}
+    for tokens, seq, hq, hkv in ec.ROPE_SHAPES + (ec.ROPE_PREFIX_SHAPE,):
+        ins = ec.rope_inputs(tokens, seq, hq, hkv, gemma, dtype)
+        got = ec.rope_emulate(*ins, seq, hq, hkv, hd, ec.ROPE_EPS, gemma)
+        worst = max(worst, ec.check_rope(got, *ins, seq, hq, hkv, hd, ec.ROPE_EPS, gemma))
+        ratio = ec.rope_ratio(got, *ins, seq, hq, hkv, hd, ec.ROPE_EPS, gemma)
+        for name, (tok, h) in ec.rope_special_heads(tokens, hq, hkv).items():
+            heads[name] = max(heads.get(name, 0.0), float(ratio[tok, h].max()))
+    K = ec.ROPE_K[(gemma, dtype)]
+    _say(capsys, f"rotary {ROPE_IDS[ROPE_CASES.index((gemma, dtype))]}: torch's emulation reaches {worst:.3f} of the bound (K = {K}) = "
+                 f"{worst * K * (1 + 2.0 ** -6):.2f} u (|A| + |B|); heads scaled by 1e-4 {heads['small']:.3f}, by 300 {heads['big']:.3f}, zero {heads['zero']:.0f}")
+    assert set(heads) == {"zero", "small", "big"} and heads["zero"] == 0.0
+    assert worst <= (0.5 if dtype == F32 else 1.0)
+
+
+@pytest.mark.parametrize("kind", (1, 2))
+def test_fp32_gated_activation_cast_to_the_storage_type_passes_half_the_bound(kind, capsys):
+    worst = {F32: 0.0, BF16: 0.0}
+    beyond = 0.0
+    for dtype in worst:
+        for inter in ec.GATED_WIDTHS[dtype]:
+            for rows in ec.GATED_ROWS:
+                x = ec.gated_inputs(kind, inter, rows, dtype)
+                out = ec.act_fp32(x, None, kind).to(dtype)
+                worst[dtype] = max(worst[dtype], ec.check_gated(out, x, kind, bound_scale=0.5) / 2.0)
+                if dtype == F32:                              # what GATED_K_F32 would be measured from: the error the floor leaves over
+                    y64 = ec.act_ref(x, None, kind)
+                    over = ((out.double() - y64).abs() - ec.pieces_floor(*ec.act_operands(x, None, kind))).clamp(min=0.0)
+                    beyond = max(beyond, float((over / (ec.UNIT[F32] * y64.abs()).clamp(min=1e-300)).max()))
+    _say(capsys, f"{'SwiGLU' if kind == 1 else 'GeGLU'}: torch fp32 cast to the storage type reaches {worst[F32]:.3f} (fp32, K = {ec.GATED_K_F32[kind]}; "
+                 f"{beyond:.2f} u |y| beyond the floor) and {worst[BF16]:.3f} (bf16) of the bound")
+    assert max(worst.values()) <= 0.5
+
+
 # ---- the checks have teeth -------------------------------------------------------------------------------------------------------
 def _thirds(p):
     n = p.shape[1] // 3
@@ -195,6 +243,97 @@ def test_an_unwritten_or_overrun_guarded_buffer_is_noticed():
     raw[margin - 1] = 0                                        # one byte in front
     with pytest.raises(AssertionError):
         ec.assert_margins(p)
+
+
+ROPE_TEETH_SHAPE = (10, 4, 2, 2)                               # tok // seq differs from tok % seq; all three special heads
+ROPE_CORRUPTIONS = ("rotation sign flipped", "cos / sin of the partner element (i +- hd / 2)", "eps dropped", "pos = tok // seq",
+                    "the key weight on the query heads", "w and 1 + w exchanged", "one value element changed")
+
+
+def _corrupt_rope(name, qkv, wq, wk, cos, sin, seq, hq, hkv, hd, gemma):
+    """The answer (fp64, rounded once to the storage type) of a kernel with defect `name`; None: of a correct one."""
+    tokens, heads = qkv.shape[0], hq + hkv
+    x, w, c, s = ec.rope_operands(qkv, wq, wk, cos, sin, seq, hq, hkv, hd, torch.float64)
+    eps, sign, one = float(torch.tensor(ec.ROPE_EPS, dtype=F32)), 1.0, 1.0 if gemma else 0.0
+    if name == "rotation sign flipped":
+        sign = -1.0
+    elif name == "cos / sin of the partner element (i +- hd / 2)":
+        c, s = c.roll(hd // 2, -1), s.roll(hd // 2, -1)
+    elif name == "eps dropped":
+        eps = 0.0
+    elif name == "pos = tok // seq":
+        pos = torch.arange(tokens) // seq
+        c, s = cos.double()[pos][:, None, :], sin.double()[pos][:, None, :]
+    elif name == "the key weight on the query heads":
+        w = wk.double().expand(heads, hd)
+    elif name == "w and 1 + w exchanged":
+        one = 1.0 - one
+    y = x * torch.rsqrt((x * x).mean(-1, keepdim=True) + eps) * (one + w)
+    rot = sign * torch.cat((-y[..., hd // 2:], y[..., :hd // 2]), dim=-1)
+    out = qkv.clone()
+    out.view(tokens, hq + 2 * hkv, hd)[:, :heads] = (y * c + rot * s).to(qkv.dtype)
+    if name == "one value element changed":
+        ec.bits(out)[tokens // 2, heads * hd + 5] ^= 1         # the last bit of one element of the first value head
+    return out
+
+
+@pytest.mark.parametrize("name", ROPE_CORRUPTIONS)
+def test_the_rotary_check_rejects_a_corrupted_answer(name, capsys):
+    tokens, seq, hq, hkv = ROPE_TEETH_SHAPE
+    scored = []
+    for gemma, dtype in ROPE_CASES:
+        hd = ec.ROPE_HEAD[gemma]
+        ins = ec.rope_inputs(tokens, seq, hq, hkv, gemma, dtype)
+        shape = (seq, hq, hkv, hd, ec.ROPE_EPS, gemma)
+        ec.check_rope(_corrupt_rope(None, *ins, *shape[:4], gemma), *ins, *shape)                    # the right answer passes
+        bad = _corrupt_rope(name, *ins, *shape[:4], gemma)
+        with pytest.raises(AssertionError):
+            ec.check_rope(bad, *ins, *shape)
+        ratio = ec.rope_ratio(bad, *ins, *shape)
+        if name == "eps dropped":                             # the head where eps dominates the mean square must show it
+            tok, h = ec.rope_special_heads(tokens, hq, hkv)["small"]
+            ratio = ratio[tok, h]
+        if name == "one value element changed":
+            assert float(ratio.max()) <= 1.0                   # (the value heads' own check caught it)
+            scored.append("the value heads' comparison")
+            continue
+        assert float(ratio.max()) > 1.0
+        scored.append(f"{float(ratio.max()):.3g} x bound, {float((ratio > 1).float().mean()):.0%} of elements")
+    _say(capsys, f"rotary, rejected: {name} (" + "; ".join(f"{i}: {s}" for i, s in zip(ROPE_IDS, scored)) + ")")
+
+
+GATED_CORRUPTIONS = ("gate and up columns swapped", "erf GELU in place of the tanh form", "SiLU without its g factor")
+
+
+@pytest.mark.parametrize("name", GATED_CORRUPTIONS)
+def test_the_gated_check_rejects_a_corrupted_answer(name, capsys):
+    scored = []
+    for kind in (1, 2):
+        for dtype in (F32, BF16):
+            inter = ec.GATED_WIDTHS[dtype][1]
+            x = ec.gated_inputs(kind, inter, 5, dtype)
+            ec.check_gated(ec.act_fp32(x, None, kind).to(dtype), x, kind)                        # the right answer passes
+            g, u = ec.act_operands(x, None, kind)
+            keep = torch.ones_like(g, dtype=torch.bool)
+            if name == "gate and up columns swapped":
+                bad = ec.act_fp32(torch.cat((x[:, inter:], x[:, :inter]), dim=1), None, kind)
+            elif name == "erf GELU in place of the tanh form":
+                if kind != 2:
+                    continue
+                bad, keep = torch.nn.functional.gelu(g) * u, g.abs() <= 3.0                      # must show at ordinary gate values
+            else:
+                if kind != 1:
+                    continue
+                bad = torch.sigmoid(g) * u
+            bad = bad.to(dtype)
+            with pytest.raises(AssertionError):
+                ec.check_gated(bad, x, kind)
+            ratio = ec.gated_ratio(bad, x, kind)[keep]
+            assert float(ratio.max()) > 1.0
+            scored.append(f"{'SwiGLU' if kind == 1 else 'GeGLU'} {'fp32' if dtype == F32 else 'bf16'}: {float(ratio.max()):.3g} x bound, "
+                          f"{float((ratio > 1).float().mean()):.0%} of elements")
+    _say(capsys, f"gated, rejected: {name} (" + "; ".join(scored) + ")")
+    assert scored
 
 
 # ---- the argument contract -------------------------------------------------------------------------------------------------------
@@ -352,6 +491,48 @@ def test_refusals_come_before_the_device_check():
     # the empty call
     for f, name in EMPTY.items():
         assert f(lib, **{name: 0}) == 0, f.__name__
+
+
+def test_rotary_and_gated_refusals_at_their_edges():
+    """What the loop above leaves out for ts_qk_norm_rope / ts_gemma_qk_norm_rope / ts_swiglu / ts_geglu: both storage types, the
+    widths on either side of one 16-byte access, negative counts, every misalignment of every pointer, and the empty call with
+    everything else in order - all without a device."""
+    lib = _ffi.load()
+    inv, uns = ec.TS_ERR_INVALID, ec.TS_ERR_UNSUPPORTED
+    for f in (swiglu, geglu):
+        for dtype, vec in ((0, 4), (1, 8)):
+            for inter in (vec - 1, vec // 2, 1, 0, -vec, vec + 1, 2 * vec - 1, 31 * vec + vec // 2, 3072 + vec // 2):
+                assert f(lib, dtype=dtype, inter=inter) == inv, (f.__name__, dtype, inter)
+            assert b"must be a multiple of %d" % vec in lib.ts_last_error()
+            assert f(lib, dtype=dtype, inter=vec, rows=-1) == inv, (f.__name__, dtype)
+            assert f(lib, dtype=dtype, inter=vec, rows=0) == 0 and f(lib, dtype=dtype, inter=3072, rows=0) == 0, (f.__name__, dtype)
+            for name in ALIGNED16[f]:
+                for off in (1, 2, 4, 8, 12):
+                    assert f(lib, dtype=dtype, inter=vec, **{name: P + off}) == inv, (f.__name__, dtype, name, off)
+            assert b"16-byte aligned" in lib.ts_last_error()
+        assert f(lib, dtype=1, inter=4) == inv                                                  # one fp32 access is half a bf16 one
+    for f, own, other in ((qk_rope, 128, 256), (gemma_qk_rope, 256, 128)):
+        for dtype in (0, 1):
+            for seq in (0, -1, -16):
+                assert f(lib, dtype=dtype, seq=seq) == inv, (f.__name__, dtype, seq)
+            for heads in (0, -1):
+                assert f(lib, dtype=dtype, hq=heads) == inv and f(lib, dtype=dtype, hkv=heads) == inv, (f.__name__, dtype, heads)
+                assert f(lib, dtype=dtype, hq=heads, hkv=heads) == inv, (f.__name__, dtype, heads)
+            assert f(lib, dtype=dtype, tokens=-1) == inv, (f.__name__, dtype)
+            for hd in (other, 64, 0, -own, own + 8, 4 * own):
+                assert f(lib, dtype=dtype, hd=hd) == uns, (f.__name__, dtype, hd)
+                assert b"head size %d: this kernel serves head size %d" % (hd, own) in lib.ts_last_error()
+            for name in ALIGNED16[f]:
+                for off in (1, 2, 4, 8, 12):
+                    assert f(lib, dtype=dtype, **{name: P + off}) == inv, (f.__name__, dtype, name, off)
+            assert b"16-byte aligned" in lib.ts_last_error()
+            # nothing to do: OK whatever the other counts are, as long as they are valid ...
+            assert f(lib, dtype=dtype, tokens=0) == 0 and f(lib, dtype=dtype, tokens=0, seq=1, hq=1, hkv=1) == 0, (f.__name__, dtype)
+            # ... and a refusal still comes first
+            assert f(lib, dtype=dtype, tokens=0, seq=0) == inv and f(lib, dtype=dtype, tokens=0, hd=other) == uns, (f.__name__, dtype)
+            assert f(lib, dtype=dtype, tokens=0, qkv=P + 8) == inv and f(lib, dtype=dtype, tokens=0, cos=None) == inv, (f.__name__, dtype)
+    for f in (swiglu, geglu):
+        assert f(lib, rows=0, inter=6) == inv and f(lib, rows=0, out=P + 8) == inv and f(lib, rows=0, gate_up=None) == inv, f.__name__
 
 
 @pytest.mark.skipif(gpu_available(), reason="fake pointers: only where the device check refuses the call")
