@@ -1,4 +1,5 @@
-"""Every regime of the matrix path's final select (level_select_kernel, lds_select_top), entered on purpose.
+"""Every regime of the matrix path's final select (level_select_kernel in kernels_level.h, lds_select_top in
+kernels_select.h), entered on purpose.
 
 A corpus that fits the first level (n <= 4096 rows, or 8192 with TS_MFMA_FIRST_ROWS=8192) runs as ONE unthresholded level:
 every live row is a candidate, so the select sees exactly n_live keys and n picks the regime -

@@ -1,6 +1,6 @@
 """A numpy / fp64 model of what the matrix path's threshold estimate must come out as, and the lattice cases the CPU and GPU
 threshold tests share.  No library call: the planning half of mfma_plan / plan_levels and level_threshold, restated from
-their comments and formulas (search_mfma.hip, kernels_select.h).
+their comments and formulas (search_mfma.hip, kernels_level.h).
 
 Why the estimate is observable: on the lattice corpora of tests/exact_common.py every score is a multiple of 2^-8, exact
 in bf16 and fp32 in any summation order.  The sample's scores, their fp64 mean and sd and their k-th best are then the same

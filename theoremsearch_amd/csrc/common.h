@@ -130,6 +130,17 @@ struct WaveTopK {
             if ((last >> 6) == r) t = shfl_u64(key[r], last & 63);
         thr = t;
     }
+    // Every lane offers one key (0 = none): the keys above the threshold are inserted one by one, in lane order; a key
+    // that an earlier insert of the same offer pushed below the threshold is dropped.
+    __device__ __forceinline__ void offer(u64 key, int k, int lane) {
+        u64 m = __ballot(key > thr);
+        while (m) {
+            const int src = __ffsll((long long)m) - 1;
+            m &= m - 1;
+            const u64 K = shfl_u64(key, src);
+            if (K > thr) insert(K, k, lane);
+        }
+    }
 };
 
 // Descending bitonic sort of n (power of two) keys in LDS by `nthreads` threads of one workgroup.

@@ -1,6 +1,6 @@
 // The threshold sample of the batched search: scores of every query against a sparse sample of the corpus (every
 // `tile_stride`-th tile of 32 rows, at most 8192 rows), written as a dense [query][sample position] fp32 matrix that
-// sample_select_kernel (kernels_select.h) turns into the pass thresholds of the full-corpus pass.
+// sample_select_fast_kernel (kernels_level.h) turns into the pass thresholds of the full-corpus pass.
 //
 // Round 2 ran the full-pass kernel itself over the sample (SPARSE instantiation: 393 KB of query fragments per workgroup
 // for ONE tile of work, every score appended to lane-private lists that the select then gathered from 1,024 writers):

@@ -21,7 +21,7 @@
 // The estimate is not a bound: the final select re-runs a query exactly when fewer than min(k, rows) candidates came back.
 #pragma once
 #include "bias_plan.h"
-#include "kernels_select.h"
+#include "kernels_level.h"
 
 namespace ts {
 
@@ -102,11 +102,7 @@ template <int KR>   // 1: kk <= 64, 4: kk <= 256 (as level_select_kernel)
 __global__ void __launch_bounds__(kLevelThreads) sample_select_biased_kernel(BiasSelectArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NW = kLevelThreads / 64;
-    u64* keys = (u64*)smem;                                   // weighted sample scores keyed by position
-    u64* small = (u64*)(smem + kLevelSortMax * 8);
-    u64* wlists = small + kLevelSmall;
-    u32* hist = (u32*)(wlists + NW * TS_MAX_K_INTERNAL);      // lds_select_top's own histogram
-    u32* ctr = hist + kLevelBins;                             // ctr[0]: keys made; ctr[3], ctr[4], ctr[8..11]: lds_select_top's
+    const SelectLds lds = SelectLds::carve(smem, kLevelSortMax);   // keys: weighted sample scores keyed by position
     u32* bhist = (u32*)(smem + kLevelLds);                    // the call's histogram of w * bias, copied from a.ghist
     double* red = (double*)(bhist + kBiasBins);               // [2][NW] sums of the bisection
     double* stat = red + 2 * NW;                              // [NW][4]: sum, sum of squares, live rows, -
@@ -115,10 +111,10 @@ __global__ void __launch_bounds__(kLevelThreads) sample_select_biased_kernel(Bia
     const int npos = (int)min(a.ntiles * (int64_t)kTileRows, (int64_t)kLevelSortMax);
     if (threadIdx.x == 0) {
         a.count[q] = 0;
-        ctr[0] = 0;
-        ctr[3] = 0;
+        lds.ctr[kSelFill] = 0;                                // keys made
+        lds.ctr[kSelShort] = 0;
     }
-    for (int i = threadIdx.x; i < kLevelBins; i += blockDim.x) hist[i] = 0;
+    for (int i = threadIdx.x; i < kLevelBins; i += blockDim.x) lds.hist[i] = 0;
     for (int i = threadIdx.x; i < kBiasBins; i += blockDim.x) bhist[i] = a.ghist[i];
     __syncthreads();
     auto row_of = [&](int p) -> int64_t {
@@ -145,13 +141,13 @@ __global__ void __launch_bounds__(kLevelThreads) sample_select_biased_kernel(Bia
         }
         const u64 made = __ballot(key != 0ull);
         u32 base = 0;
-        if (lane == 0 && made) base = atomicAdd(&ctr[0], (u32)__popcll(made));
+        if (lane == 0 && made) base = atomicAdd(&lds.ctr[kSelFill], (u32)__popcll(made));
         base = (u32)__shfl((int)base, 0, 64);
-        if (key != 0ull) keys[base + __popcll(made & ((1ull << lane) - 1ull))] = key;
+        if (key != 0ull) lds.keys[base + __popcll(made & ((1ull << lane) - 1ull))] = key;
     }
-    s1 = wave_sum_f64_sel(s1);
-    s2 = wave_sum_f64_sel(s2);
-    const double dn = wave_sum_f64_sel((double)nl);
+    s1 = wave_sum_f64(s1);
+    s2 = wave_sum_f64(s2);
+    const double dn = wave_sum_f64((double)nl);
     if (lane == 0) {
         stat[4 * wave] = s1;
         stat[4 * wave + 1] = s2;
@@ -171,11 +167,11 @@ __global__ void __launch_bounds__(kLevelThreads) sample_select_biased_kernel(Bia
     const bool any_term = a.ghist[kBiasBins + 1] != 0u;
     const float lo = any_term ? unord_f32(~a.ghist[kBiasBins]) : INFINITY, hi = any_term ? unord_f32(a.ghist[kBiasBins + 1]) : -INFINITY;
     const float width = hi > lo ? (hi - lo) / (float)kBiasBins : 0.0f;
-    const int cnt = (int)ctr[0];
+    const int cnt = (int)lds.ctr[kSelFill];
 
     // the guaranteed bound: the kk-th best weighted score of the sample
     double m_unused, sd_unused;
-    const u64* best = lds_select_top<KR>(keys, cnt, a.kk, small, wlists, hist, ctr, false, m_unused, sd_unused);
+    const u64* best = lds_select_top<KR>(lds, cnt, a.kk, false, m_unused, sd_unused);
     const u64 kth = best[a.kk - 1];
     const float bound = kth ? key_score(kth) : -INFINITY;
 
@@ -184,7 +180,7 @@ __global__ void __launch_bounds__(kLevelThreads) sample_select_biased_kernel(Bia
     if (live_rows >= 256.0) {
         int flip = 0;
         auto total = [&](double x) -> double {
-            x = wave_sum_f64_sel(x);
+            x = wave_sum_f64(x);
             if (lane == 0) red[flip * NW + wave] = x;
             __syncthreads();
             double t = 0.0;

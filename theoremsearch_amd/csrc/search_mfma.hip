@@ -17,7 +17,7 @@
 #include "kernels_mfma_f32.h"
 #include "kernels_sample.h"
 #include "kernels_sample_biased.h"
-#include "kernels_select.h"
+#include "kernels_level.h"
 
 struct Level { int64_t stride, ntiles; int run; };
 
@@ -259,7 +259,7 @@ static MfmaPlan mfma_plan(const ts_index* ix, int nq, int k) {
     p.z_tail = (p.statistical && lv.size() == 2)
                    ? (float)normal_tail_z(std::min(0.25, (double)p.stat_cands / (double)std::max<int64_t>(p.pop, 1)))
                    : 0.0f;
-    // Second estimate (exponential tail fit of the sample's order statistics, kernels_select.h), for score distributions
+    // Second estimate (exponential tail fit of the sample's order statistics, level_threshold in kernels_level.h), for score distributions
     // with heavier tails than a Gaussian.  Only where it is needed: when the guaranteed bound alone (the kk-th best of
     // the sample admits ~kk * N / sample rows) would swamp the candidate buffer - large corpora; it aims at
     // max(2048, 8 kk) expected candidates, a quarter of the buffer.
@@ -269,7 +269,7 @@ static MfmaPlan mfma_plan(const ts_index* ix, int nq, int k) {
                    ? (float)std::min(0.25, (double)std::max(2048, 8 * p.kk) / (double)std::max<int64_t>(p.pop, 1))
                    : 0.0f;
     // Feedback partition of the full pass (16x16 kernel): the final select moves the workgroups' tile boundaries towards
-    // equal finishing times for the next search (kernels_select.h, rebalance_tiles).  The table starts as equal shares and
+    // equal finishing times for the next search (common.h, rebalance_tiles).  The table starts as equal shares and
     // is re-made whenever the grid or the number of tiles changes.
     p.balance = p.shape16 && ix->knobs.get(K_MFMA_BALANCE, 1) != 0 && p.wgs >= 8 && p.wgs <= 256 && lv.back().stride == 1 &&
                 lv.back().run == 1 && lv.back().ntiles >= 32 * (int64_t)p.wgs && (p.variant == kVariantProduct || p.variant == kVariantClockProbe || p.screen_diag);

@@ -1,29 +1,68 @@
 // libtsearch.so - C ABI (include/tsearch.h), part 4: merging partial top-k lists and the row-sharded search over RCCL.
 #include "host.h"
-#include "kernels_select.h"
+#include "kernels_merge.h"
+
+namespace {
+
+// The one place that fills MergeArgs.  Split form: part p at scores + p * nq * k_in, idx + p * nq * k_in.
+MergeArgs merge_args(const float* scores, const int64_t* idx, int64_t stride_f32, int64_t stride_i64, int nparts, int nq, int k_in,
+                     int k_out, float* out_scores, int64_t* out_idx) {
+    MergeArgs a;
+    a.scores = scores; a.idx = idx;
+    a.part_stride = stride_f32; a.part_stride_idx = stride_i64;
+    a.nparts = nparts; a.nq = nq; a.k_in = k_in; a.k_out = k_out;
+    a.out_scores = out_scores; a.out_idx = out_idx;
+    return a;
+}
+MergeArgs merge_args_split(const float* scores, const int64_t* idx, int nparts, int nq, int k_in, int k_out, float* out_scores,
+                           int64_t* out_idx) {
+    return merge_args(scores, idx, (int64_t)nq * k_in, (int64_t)nq * k_in, nparts, nq, k_in, k_out, out_scores, out_idx);
+}
+// Packed form: part p is the block at packed + p * part_stride_bytes, scores at 0 and ids at idx_off of each block.
+MergeArgs merge_args_packed(const void* packed, int64_t part_stride_bytes, int64_t idx_off, int nparts, int nq, int k_in, int k_out,
+                            float* out_scores, int64_t* out_idx) {
+    return merge_args((const float*)packed, (const int64_t*)((const char*)packed + idx_off), part_stride_bytes / 4,
+                      part_stride_bytes / 8, nparts, nq, k_in, k_out, out_scores, out_idx);
+}
+
+// The one refusal of a merge that merge_kernel's LDS does not hold ...
+int merge_fits(int nparts, int k_in) {
+    if ((int64_t)nparts * k_in > kMergeMax)
+        return fail(TS_ERR_UNSUPPORTED, "nparts * k_in = %lld exceeds %d", (long long)nparts * k_in, kMergeMax);
+    return TS_OK;
+}
+// ... and the one checked launch every merge goes through.  (The two entry points below also ask merge_fits up front: they
+// refuse before they look at the device or return for an empty batch, as they always did.)
+int merge_launch(const MergeArgs& a, hipStream_t st) {
+    TS_TRY(merge_fits(a.nparts, a.k_in));
+    launch_merge(a, st);
+    HIP_TRY(hipGetLastError());
+    return TS_OK;
+}
+
+// Device results [n = nq x k] -> host, and the stream is synchronised: the tail of every call that answers in host memory.
+int results_to_host(float* out_scores, int64_t* out_idx, const float* dev_scores, const int64_t* dev_idx, size_t n, hipStream_t st) {
+    HIP_TRY(hipMemcpyAsync(out_scores, dev_scores, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out_idx, dev_idx, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return TS_OK;
+}
+
+}  // namespace
 
 extern "C" int ts_merge_topk(int device, const float* scores, const int64_t* idx, int32_t nparts, int32_t nq, int32_t k_in,
                              int32_t k_out, float* out_scores, int64_t* out_idx, int on_device, void* stream) {
     if (!scores || !idx || !out_scores || !out_idx) return fail(TS_ERR_INVALID, "NULL argument");
     if (nparts < 1 || nq < 0 || k_in < 1 || k_out < 1 || k_out > TS_MAX_K)
         return fail(TS_ERR_INVALID, "bad merge shape");
-    if ((int64_t)nparts * k_in > kMergeMax)
-        return fail(TS_ERR_UNSUPPORTED, "nparts * k_in = %lld exceeds %d", (long long)nparts * k_in, kMergeMax);
+    TS_TRY(merge_fits(nparts, k_in));
     if (nq == 0) return TS_OK;
     TS_TRY(check_device(device));
     HIP_TRY(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
-    MergeArgs a;
-    a.nparts = nparts; a.nq = nq; a.k_in = k_in; a.k_out = k_out;
-    a.part_stride = a.part_stride_idx = (int64_t)nq * k_in;
-    const size_t nin = (size_t)nparts * nq * k_in, nout = (size_t)nq * k_out;
-    if (on_device) {
-        a.scores = scores; a.idx = idx; a.out_scores = out_scores; a.out_idx = out_idx;
-        launch_merge(a, st);
-        HIP_TRY(hipGetLastError());
-        return TS_OK;
-    }
+    if (on_device) return merge_launch(merge_args_split(scores, idx, nparts, nq, k_in, k_out, out_scores, out_idx), st);
     // one temporary block (freed on every return path): ids in | ids out | scores in | scores out
+    const size_t nin = (size_t)nparts * nq * k_in, nout = (size_t)nq * k_out;
     DevBuf tmp;
     HIP_TRY(tmp.alloc(nin * 12 + nout * 12));
     int64_t* di = tmp.as<int64_t>();
@@ -32,13 +71,8 @@ extern "C" int ts_merge_topk(int device, const float* scores, const int64_t* idx
     float* dos = ds + nin;
     HIP_TRY(hipMemcpyAsync(ds, scores, nin * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(di, idx, nin * 8, hipMemcpyHostToDevice, st));
-    a.scores = ds; a.idx = di; a.out_scores = dos; a.out_idx = doi;
-    launch_merge(a, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out_scores, dos, nout * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out_idx, doi, nout * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return TS_OK;
+    TS_TRY(merge_launch(merge_args_split(ds, di, nparts, nq, k_in, k_out, dos, doi), st));
+    return results_to_host(out_scores, out_idx, dos, doi, nout, st);
 }
 
 extern "C" int ts_merge_topk_packed(int device, const void* packed, int64_t part_stride_bytes, int64_t idx_offset_bytes,
@@ -46,8 +80,7 @@ extern "C" int ts_merge_topk_packed(int device, const void* packed, int64_t part
                                     int64_t* out_idx, void* stream) {
     if (!packed || !out_scores || !out_idx) return fail(TS_ERR_INVALID, "NULL argument");
     if (nparts < 1 || nq < 0 || k_in < 1 || k_out < 1 || k_out > TS_MAX_K) return fail(TS_ERR_INVALID, "bad merge shape");
-    if ((int64_t)nparts * k_in > kMergeMax)
-        return fail(TS_ERR_UNSUPPORTED, "nparts * k_in = %lld exceeds %d", (long long)nparts * k_in, kMergeMax);
+    TS_TRY(merge_fits(nparts, k_in));
     if (part_stride_bytes % 8 || idx_offset_bytes % 8 || idx_offset_bytes < (int64_t)nq * k_in * 4 ||
         part_stride_bytes < idx_offset_bytes + (int64_t)nq * k_in * 8)
         return fail(TS_ERR_INVALID, "bad packed layout (stride %lld, idx offset %lld)", (long long)part_stride_bytes,
@@ -55,17 +88,8 @@ extern "C" int ts_merge_topk_packed(int device, const void* packed, int64_t part
     if (nq == 0) return TS_OK;
     TS_TRY(check_device(device));
     HIP_TRY(hipSetDevice(device));
-    MergeArgs a;
-    a.nparts = nparts; a.nq = nq; a.k_in = k_in; a.k_out = k_out;
-    a.scores = (const float*)packed;
-    a.idx = (const int64_t*)((const char*)packed + idx_offset_bytes);
-    a.part_stride = part_stride_bytes / 4;
-    a.part_stride_idx = part_stride_bytes / 8;
-    a.out_scores = out_scores;
-    a.out_idx = out_idx;
-    launch_merge(a, (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    return TS_OK;
+    return merge_launch(merge_args_packed(packed, part_stride_bytes, idx_offset_bytes, nparts, nq, k_in, k_out, out_scores, out_idx),
+                        (hipStream_t)stream);
 }
 
 // Row-sharded search behind the C ABI (SURVEY.md section 8b "ts_shards_*", section 8e): the exchange of the per-shard
@@ -149,22 +173,8 @@ RcclApi* rccl_api() {
 inline int64_t packed_idx_off(int nq, int k) { return ((int64_t)nq * k * 4 + 7) / 8 * 8; }
 inline int64_t packed_bytes(int nq, int k) { return packed_idx_off(nq, k) + (int64_t)nq * k * 8; }
 
-int launch_merge_packed(const void* packed, int64_t part_stride_bytes, int64_t idx_off, int nparts, int nq, int k_in, int k_out,
-                        float* out_scores, int64_t* out_idx, hipStream_t st) {
-    if ((int64_t)nparts * k_in > kMergeMax)
-        return fail(TS_ERR_UNSUPPORTED, "nparts * k_in = %lld exceeds %d", (long long)nparts * k_in, kMergeMax);
-    MergeArgs a;
-    a.nparts = nparts; a.nq = nq; a.k_in = k_in; a.k_out = k_out;
-    a.scores = (const float*)packed;
-    a.idx = (const int64_t*)((const char*)packed + idx_off);
-    a.part_stride = part_stride_bytes / 4;
-    a.part_stride_idx = part_stride_bytes / 8;
-    a.out_scores = out_scores;
-    a.out_idx = out_idx;
-    launch_merge(a, st);
-    HIP_TRY(hipGetLastError());
-    return TS_OK;
-}
+// What every entry point that needs RCCL answers when the library cannot be bound.
+int no_rccl() { return fail(TS_ERR_UNSUPPORTED, "%s", "RCCL is not available in this process"); }
 
 }  // namespace
 
@@ -185,7 +195,7 @@ struct ts_comm {
 extern "C" int ts_comm_unique_id(void* id_out, int32_t id_bytes) {
     if (!id_out || id_bytes < (int32_t)sizeof(ncclUniqueId)) return fail(TS_ERR_INVALID, "id buffer must hold %zu bytes", sizeof(ncclUniqueId));
     RcclApi* api = rccl_api();
-    if (!api) return fail(TS_ERR_UNSUPPORTED, "%s", "RCCL is not available in this process");
+    if (!api) return no_rccl();
     ncclUniqueId id;
     NCCL_TRY(api, api->GetUniqueId(&id));
     memset(id_out, 0, (size_t)id_bytes);
@@ -200,7 +210,7 @@ extern "C" int ts_comm_create(int device, int32_t world, int32_t rank, const voi
     if (!id || id_bytes < (int32_t)sizeof(ncclUniqueId)) return fail(TS_ERR_INVALID, "id must hold %zu bytes (ts_comm_unique_id)", sizeof(ncclUniqueId));
     TS_TRY(check_device(device));
     RcclApi* api = rccl_api();
-    if (!api) return fail(TS_ERR_UNSUPPORTED, "%s", "RCCL is not available in this process");
+    if (!api) return no_rccl();
     HIP_TRY(hipSetDevice(device));
     ts_comm* c = new (std::nothrow) ts_comm();
     if (!c) return fail(TS_ERR_NOMEM, "host allocation failed");
@@ -244,7 +254,7 @@ extern "C" int ts_comm_allgather(ts_comm* c, const void* send_dev, void* recv_de
     if (!c || !send_dev || !recv_dev || bytes < 0) return fail(TS_ERR_INVALID, "bad argument");
     if (bytes == 0) return TS_OK;
     RcclApi* api = rccl_api();
-    if (!api) return fail(TS_ERR_UNSUPPORTED, "%s", "RCCL is not available in this process");
+    if (!api) return no_rccl();
     std::lock_guard<std::mutex> lock(c->mu);         // one thread at a time per communicator
     HIP_TRY(hipSetDevice(c->device));
     NCCL_TRY(api, api->AllGather(send_dev, recv_dev, (size_t)bytes, ncclUint8, c->comm, (hipStream_t)stream));
@@ -261,7 +271,7 @@ extern "C" int ts_comm_search(ts_comm* c, ts_index* shard, const void* queries, 
     if (nq < 0 || k < 1 || k > TS_MAX_K) return fail(TS_ERR_INVALID, "bad shape");
     if (nq == 0) return TS_OK;
     RcclApi* api = rccl_api();
-    if (!api) return fail(TS_ERR_UNSUPPORTED, "%s", "RCCL is not available in this process");
+    if (!api) return no_rccl();
     std::lock_guard<std::mutex> lock(c->mu);
     HIP_TRY(hipSetDevice(c->device));
     void* ix_stream = nullptr;
@@ -282,12 +292,8 @@ extern "C" int ts_comm_search(ts_comm* c, ts_index* shard, const void* queries, 
         di = tmp.as<int64_t>();
         ds = (float*)(di + (size_t)nq * k);
     }
-    TS_TRY(launch_merge_packed(c->all[b], blk, idx_off, c->world, nq, k, k, ds, di, st));
-    if (!out_on_device) {
-        HIP_TRY(hipMemcpyAsync(out_scores, ds, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out_idx, di, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
+    TS_TRY(merge_launch(merge_args_packed(c->all[b], blk, idx_off, c->world, nq, k, k, ds, di), st));
+    if (!out_on_device) TS_TRY(results_to_host(out_scores, out_idx, ds, di, (size_t)nq * k, st));
     return TS_OK;
 }
 
@@ -442,7 +448,7 @@ extern "C" int ts_shards_create(int32_t ngpu, const int32_t* devices, int64_t n_
         RcclApi* api = rccl_api();
         if (!api) {
             ts_shards_destroy(s);
-            return fail(TS_ERR_UNSUPPORTED, "%s", "RCCL is not available in this process");
+            return no_rccl();
         }
         s->comm.assign(ngpu, nullptr);
         ncclResult_t r = api->CommInitAll(s->comm.data(), ngpu, s->device.data());
@@ -508,7 +514,7 @@ extern "C" int ts_shards_search(ts_shards* s, const void* queries, int q_dtype, 
     if (!s || !queries || !out_scores || !out_idx) return fail(TS_ERR_INVALID, "NULL argument");
     if (q_dtype != TS_F32 && q_dtype != TS_BF16) return fail(TS_ERR_INVALID, "q_dtype %d", q_dtype);
     if (nq < 0 || k < 1 || k > TS_MAX_K) return fail(TS_ERR_INVALID, "bad shape");
-    if ((int64_t)s->ngpu * k > kMergeMax) return fail(TS_ERR_UNSUPPORTED, "ngpu * k exceeds %d", kMergeMax);
+    if ((int64_t)s->ngpu * k > kMergeMax) return fail(TS_ERR_UNSUPPORTED, "ngpu * k exceeds %d", kMergeMax);   // up front, in its own words
     if (nq == 0) return TS_OK;
     std::lock_guard<std::mutex> lock(s->mu);
     const int G = s->ngpu;
@@ -588,10 +594,8 @@ extern "C" int ts_shards_search(ts_shards* s, const void* queries, int q_dtype, 
     TS_TRY(ensure(&s->fin, &s->fin_bytes, (size_t)nq * k * 12));
     int64_t* di = (int64_t*)s->fin;
     float* ds = (float*)(di + (size_t)nq * k);
-    TS_TRY(launch_merge_packed(s->all[0], blk, idx_off, G, nq, k, k, ds, di, st[0]));
-    HIP_TRY(hipMemcpyAsync(out_scores, ds, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st[0]));
-    HIP_TRY(hipMemcpyAsync(out_idx, di, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st[0]));
-    HIP_TRY(hipStreamSynchronize(st[0]));
+    TS_TRY(merge_launch(merge_args_packed(s->all[0], blk, idx_off, G, nq, k, k, ds, di), st[0]));
+    TS_TRY(results_to_host(out_scores, out_idx, ds, di, (size_t)nq * k, st[0]));
     // the other devices' streams hold only their search + their all-gather: both are complete once the root's merge is
     // (the collective ends everywhere together); with the copy exchange their blocks have been read by the root
     if (s->use_rccl)
