@@ -11,6 +11,9 @@ typedef unsigned int u32;
 constexpr int kWave = 64;
 constexpr int kTileRows = 32;      // corpus rows per MFMA tile; index allocations are padded to kRowPad rows
 constexpr int kRowPad = 256;
+constexpr int64_t padded_rows(int64_t n) {     // rows rounded up to kRowPad, at least kRowPad: what an index of n rows allocates
+    return n <= kRowPad ? kRowPad : (n + kRowPad - 1) / kRowPad * kRowPad;
+}
 constexpr int kLdPad = 64;         // row stride is a multiple of 64 elements, zero padded
 
 // ---- ordered keys -------------------------------------------------------------------------

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <type_traits>
@@ -24,6 +25,7 @@
 #include "anyd_plan.h"
 #include "bias_plan.h"
 #include "encoder_plan.h"
+#include "dev_array.h"
 
 using namespace ts;
 
@@ -47,6 +49,9 @@ inline int fail(int code, const char* fmt, ...) {
             return fail(e_ == hipErrorOutOfMemory ? TS_ERR_NOMEM : TS_ERR_HIP, "%s failed: %s (%s:%d)", \
                         #expr, hipGetErrorString(e_), __FILE__, __LINE__);                              \
     } while (0)
+
+// a DevArray call (below): its code is the hipError_t of the allocator
+#define DEV_TRY(expr) HIP_TRY((hipError_t)(expr))
 
 #define TS_TRY(expr)            \
     do {                        \
@@ -140,57 +145,81 @@ struct Knobs {
 constexpr int kCandCap = 8192;        // candidate slots per query (MFMA path); kQBlock, kScanGridPerCU: scan_plan.h
 constexpr size_t kStageBytes = (size_t)256 << 20;
 
-struct ts_index {
+// Device memory has one kind of owner, DevArray (dev_array.h) over hipMalloc: a handle's buffers are members of this type and
+// a temporary is a local of it, so each is freed once, by its destructor, on every path.  No other code of the library
+// allocates, frees or (synchronously) zeroes device scratch.
+struct HipMem {
+    static int alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes ? bytes : 1); }
+    static void free(void* p) { (void)hipFree(p); }
+    static int zero(void* p, size_t bytes) { return (int)hipMemset(p, 0, bytes); }
+};
+template <class T> using DevArray = DevArrayOf<T, HipMem>;
+using DevBuf = DevArray<void>;        // a temporary, freed on every return path
+
+// The stream and the events of an index handle.  A base of ts_index, so destroyed after every member of it: the buffers
+// are freed first, then the events and the stream go.
+struct IndexQueue {
+    hipStream_t stream = nullptr;
+    hipEvent_t order_ev = nullptr;                           // recorded at the end of every call on that call's stream: orders the
+    bool ordered = false;                                    //   next call behind it (`ordered`: recorded at least once)
+    std::vector<hipEvent_t> ev_pool;                         // ts_index_profile_*: pairs, [2i] start, [2i+1] stop
+    IndexQueue() = default;
+    IndexQueue(const IndexQueue&) = delete;
+    IndexQueue& operator=(const IndexQueue&) = delete;
+    ~IndexQueue() {
+        for (hipEvent_t e : ev_pool) hipEventDestroy(e);
+        if (order_ev) hipEventDestroy(order_ev);
+        if (stream) hipStreamDestroy(stream);
+    }
+};
+
+struct ts_index : IndexQueue {
     int device = 0;
     int64_t n = 0, n_pad = 0, ld = 0, row_offset = 0;
     int d = 0, dtype = 0, metric = 0;
     int cu_count = 256;
-    void* rows = nullptr;
-    hipStream_t stream = nullptr;
+    DevArray<void> rows;                                     // owned, or borrowed: a view's (`borrowed`), the caller's (`attached`)
     std::mutex mu;
     // scratch (lazily sized)
-    void* stage = nullptr;      size_t stage_bytes = 0;      // host->device staging
-    void* qstore = nullptr;     float* qf32 = nullptr;       // prepared queries [256 x ld]
-    u64* cand = nullptr;        u32* count = nullptr;        float* thr = nullptr;
-    u64* priv = nullptr;        u32* pcount = nullptr;       int priv_writers = 0;  // MFMA path: lane-private candidate lists
-    float* sample = nullptr;                                 // MFMA path: dense [256 x 8192] score matrix of the threshold sample
+    DevArray<void> stage;                                    // host->device staging
+    DevArray<void> qstore;      DevArray<float> qf32;        // prepared queries [256 x ld]
+    DevArray<u64> cand;         DevArray<u32> count;         DevArray<float> thr;
+    DevArray<u64> priv;         DevArray<u32> pcount;        int priv_writers = 0;  // MFMA path: lane-private candidate lists
+    DevArray<float> sample;                                  // MFMA path: dense [256 x 8192] score matrix of the threshold sample
     bool rebalance_pending = false, rebalance_in_rerun = false; int rebalance_grid = 0;  // the exact re-run's launch also moves the full pass's tile boundaries
-    int* fb_list = nullptr;     int* fb_count = nullptr;     u32* stat = nullptr;   // [kQBlock] candidates per query of the last final select
-    u64* partial = nullptr;     size_t partial_bytes = 0;    // scan partials [256 slots][grid][k] keys, and the buffer the
-    u64* partial2 = nullptr;    size_t partial2_bytes = 0;   //   select rounds ping-pong with (scan_plan.h: scan_scratch)
-    float* res_scores = nullptr; int64_t* res_idx = nullptr; size_t res_cap = 0;  // device result buffers (entries)
-    u32* mask_dev = nullptr;    size_t mask_bytes = 0;       // filtered search: device copy of a host bitmask
-    float* bias_dev = nullptr;  size_t bias_bytes = 0;       // biased search: device copy of a host bias array
-    u32* bias_hist = nullptr;                                // biased matrix search: histogram of w * bias over the call's rows + its range (kernels_sample_biased.h)
+    DevArray<int> fb_list;      DevArray<int> fb_count;      DevArray<u32> stat;    // [kQBlock] candidates per query of the last final select
+    DevArray<u64> partial;                                   // scan partials [256 slots][grid][k] keys, and the buffer the
+    DevArray<u64> partial2;                                  //   select rounds ping-pong with (scan_plan.h: scan_scratch)
+    DevArray<float> res_scores; DevArray<int64_t> res_idx;   size_t res_cap = 0;  // device result buffers (entries)
+    DevArray<u32> mask_dev;                                  // filtered search: device copy of a host bitmask
+    DevArray<float> bias_dev;                                // biased search: device copy of a host bias array
+    DevArray<u32> bias_hist;                                 // biased matrix search: histogram of w * bias over the call's rows + its range (kernels_sample_biased.h)
     const float* active_bias = nullptr; float active_bias_w = 0.f;   // per-row additive term of the search in progress (under `mu`)
     bool active_bias_matrix = false;                         // ... which runs on the matrix path (ts_search_biased_ex): the biased general-width pass
-    int64_t* id_map = nullptr;                               // subset index: local row -> global id
+    DevArray<int64_t> id_map;                                // subset index: local row -> global id (a view of one borrows it)
     bool borrowed = false;                                   // a view: rows / id_map belong to another handle
     bool attached = false;                                   // rows adopted from the caller (ts_index_attach_device): never freed here
     ts_index* parent = nullptr;                              // a view: the handle that owns the rows
     std::atomic<int> nviews{0};                              // live views of this handle (it cannot grow meanwhile)
-    void* rank_buf = nullptr;   size_t rank_bytes = 0;       // ts_rank_of: targets | counts | target scores, one query block
-    void* rank_many_buf = nullptr; size_t rank_many_bytes = 0;  // ts_rank_many: slots | keys | counts of one pass of one query block
+    DevArray<void> rank_buf;                                 // ts_rank_of: targets | counts | target scores, one query block
+    DevArray<void> rank_many_buf;                            // ts_rank_many: slots | keys | counts of one pass of one query block
     const u32* active_mask = nullptr;                        // bitmask of the search in progress (under `mu`)
     int64_t active_allowed = 0;                              // rows that bitmask allows (host masks: counted; else n)
     Knobs knobs;                                             // env at creation, then ts_index_set_option
     hipStream_t last_stream = nullptr;                       // stream the previous call ran on: compared, never used (it may be gone)
-    hipEvent_t order_ev = nullptr;                           // recorded at the end of every call on that call's stream: orders the
-    bool ordered = false;                                    //   next call behind it (`ordered`: recorded at least once)
-    int64_t* part = nullptr;    unsigned* wg_ticks = nullptr;    // full pass of the 16x16 kernel: tile boundaries per workgroup, their times
+    DevArray<int64_t> part;     DevArray<unsigned> wg_ticks;     // full pass of the 16x16 kernel: tile boundaries per workgroup, their times
     int part_g = 0;             int64_t part_ntiles = -1;        // ... the grid and tile count the table was made for
     // int8 screen of the d = 768 (or, opt-in, 1024) bf16 full pass and, opt-in, of the d = 768 / 1024 fp32 one (kernels_screen8.h): the image [scr_pad x d] int8 + [scr_pad / 32] tile scalars,
     // brought up to date before a screened pass for the rows written since (scr_lo .. scr_hi, marked by every upload / append)
-    void* scr_rows = nullptr;   float* scr_tile = nullptr;   int64_t scr_pad = 0;
+    DevArray<void> scr_rows;    DevArray<float> scr_tile;    int64_t scr_pad = 0;
     int64_t scr_lo = 0, scr_hi = 0;
-    void* scr_q = nullptr;      float* scr_qmeta = nullptr;      // the launch's queries in int8 [256 x d] + their scalars
-    u64* scr_cand = nullptr;    u32* scr_count = nullptr;        // the screen's lists [256][kScreenCap] + counts
-    unsigned* pair_pos = nullptr;                            // paired full pass: the tile each workgroup has reached (one word per workgroup of the largest grid)
-    unsigned long long* dbg = nullptr;                       // TS_MFMA_VARIANT=3: per-wave cycle sums / clock probe
+    DevArray<void> scr_q;       DevArray<float> scr_qmeta;       // the launch's queries in int8 [256 x d] + their scalars
+    DevArray<u64> scr_cand;     DevArray<u32> scr_count;         // the screen's lists [256][kScreenCap] + counts
+    DevArray<unsigned> pair_pos;                             // paired full pass: the tile each workgroup has reached (one word per workgroup of the largest grid)
+    DevArray<unsigned long long> dbg;                        // TS_MFMA_VARIANT=3: per-wave cycle sums / clock probe
     double probe_ghz = 0.0, probe_cycles_per_unit = 0.0, probe_units = 0.0;   // last clock probe (16x16 shape, VARIANT 3)
     // optional event brackets around the dominant kernel (ts_index_profile_*)
-    bool profiling = false;
-    std::vector<hipEvent_t> ev_pool;   // pairs: [2i] start, [2i+1] stop
+    bool profiling = false;            // (the events: IndexQueue::ev_pool)
     size_t ev_used = 0;                // events handed out since the last read
     int64_t prof_rows = 0;
     size_t elem() const { return dtype == TS_BF16 ? 2 : 4; }
@@ -206,17 +235,11 @@ inline void screen_touch(ts_index* ix, int64_t lo, int64_t hi) {
 struct ts_timer {
     int device = 0;
     hipEvent_t a = nullptr, b = nullptr;
+    ~ts_timer() {
+        if (a) hipEventDestroy(a);
+        if (b) hipEventDestroy(b);
+    }
 };
-
-inline int ensure(void** p, size_t* have, size_t want) {
-    if (*have >= want && *p) return TS_OK;
-    if (*p) HIP_TRY(hipFree(*p));
-    *p = nullptr;
-    *have = 0;
-    HIP_TRY(hipMalloc(p, want));
-    *have = want;
-    return TS_OK;
-}
 
 // The staging buffer between host and device holds what ONE call moves, up to kStageBytes (larger transfers pass through it in
 // pieces), in steps of 1 MiB; it only grows.  (A fixed 256 MiB per index cost the throw-away index of util.cos_sim -
@@ -225,7 +248,8 @@ inline int ensure(void** p, size_t* have, size_t want) {
 inline int ensure_stage(ts_index* ix, size_t need, size_t floor_bytes) {
     const size_t gran = (size_t)1 << 20;
     const size_t want = std::max(std::min(kStageBytes, need), std::max(floor_bytes, (size_t)1));
-    return ensure(&ix->stage, &ix->stage_bytes, (want + gran - 1) / gran * gran);
+    DEV_TRY(ix->stage.need((want + gran - 1) / gran * gran));
+    return TS_OK;
 }
 
 // Event bracket around one launch: prof_begin records the start event and returns the stop event
@@ -286,14 +310,6 @@ inline int enter_stream(ts_index* ix, void* stream, hipStream_t* out, StreamScop
     *out = st;
     return TS_OK;
 }
-
-// Device buffer freed on every return path.
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-    template <class T> T* as() const { return (T*)p; }
-};
 
 inline int check_device(int device) {
     int c = 0;

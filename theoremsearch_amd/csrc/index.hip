@@ -40,6 +40,12 @@ extern "C" int ts_device_synchronize(int device) {
 // ---------------------------------------------------------------------------------------------
 // index
 // ---------------------------------------------------------------------------------------------
+// A handle under construction: a failure path returns, and what was built so far goes the way every handle goes.
+struct IndexDestroy {
+    void operator()(ts_index* ix) const { ts_index_destroy(ix); }
+};
+using IndexPtr = std::unique_ptr<ts_index, IndexDestroy>;
+
 extern "C" int ts_index_create(int device, int64_t n, int32_t d, int dtype, int metric, ts_index** out) {
     if (!out) return fail(TS_ERR_INVALID, "out is NULL");
     *out = nullptr;
@@ -49,11 +55,11 @@ extern "C" int ts_index_create(int device, int64_t n, int32_t d, int dtype, int 
     if (metric != TS_METRIC_IP && metric != TS_METRIC_COS) return fail(TS_ERR_INVALID, "metric %d", metric);
     TS_TRY(check_device(device));
     HIP_TRY(hipSetDevice(device));
-    ts_index* ix = new (std::nothrow) ts_index();
+    IndexPtr ix(new (std::nothrow) ts_index());
     if (!ix) return fail(TS_ERR_NOMEM, "host allocation failed");
     ix->device = device;
     ix->n = n;
-    ix->n_pad = std::max<int64_t>(kRowPad, (n + kRowPad - 1) / kRowPad * kRowPad);
+    ix->n_pad = padded_rows(n);
     ix->d = d;
     ix->ld = (d + kLdPad - 1) / kLdPad * kLdPad;
     ix->dtype = dtype;
@@ -61,20 +67,13 @@ extern "C" int ts_index_create(int device, int64_t n, int32_t d, int dtype, int 
     hipDeviceProp_t p;
     if (hipGetDeviceProperties(&p, device) == hipSuccess) ix->cu_count = p.multiProcessorCount;
     const size_t bytes = (size_t)ix->n_pad * ix->ld * ix->elem();
-    hipError_t e = hipMalloc(&ix->rows, bytes);
-    if (e != hipSuccess) {
-        delete ix;
-        return fail(TS_ERR_NOMEM, "hipMalloc of %zu bytes for the index failed: %s", bytes, hipGetErrorString(e));
-    }
+    hipError_t e = (hipError_t)ix->rows.need(bytes);
+    if (e != hipSuccess) return fail(TS_ERR_NOMEM, "hipMalloc of %zu bytes for the index failed: %s", bytes, hipGetErrorString(e));
     e = hipStreamCreateWithFlags(&ix->stream, hipStreamDefault);
     if (e == hipSuccess) e = hipMemsetAsync(ix->rows, 0, bytes, ix->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);
-    if (e != hipSuccess) {
-        hipFree(ix->rows);
-        delete ix;
-        return fail(TS_ERR_HIP, "index initialisation failed: %s", hipGetErrorString(e));
-    }
-    *out = ix;
+    if (e != hipSuccess) return fail(TS_ERR_HIP, "index initialisation failed: %s", hipGetErrorString(e));
+    *out = ix.release();
     return TS_OK;
 }
 
@@ -84,7 +83,7 @@ extern "C" int ts_index_view(ts_index* src, ts_index** out) {
     if (!src) return fail(TS_ERR_INVALID, "index is NULL");
     std::lock_guard<std::mutex> lock(src->mu);      // not while the rows are being moved by an append
     HIP_TRY(hipSetDevice(src->device));
-    ts_index* ix = new (std::nothrow) ts_index();
+    IndexPtr ix(new (std::nothrow) ts_index());
     if (!ix) return fail(TS_ERR_NOMEM, "host allocation failed");
     ix->device = src->device;
     ix->n = src->n;
@@ -95,16 +94,13 @@ extern "C" int ts_index_view(ts_index* src, ts_index** out) {
     ix->metric = src->metric;
     ix->row_offset = src->row_offset;
     ix->cu_count = src->cu_count;
-    ix->rows = src->rows;
-    ix->id_map = src->id_map;
+    ix->rows.borrow(src->rows, src->rows.bytes());
+    ix->id_map.borrow(src->id_map, src->id_map.bytes());
     ix->borrowed = true;
-    if (hipStreamCreateWithFlags(&ix->stream, hipStreamDefault) != hipSuccess) {
-        delete ix;
-        return fail(TS_ERR_HIP, "stream creation failed");
-    }
+    if (hipStreamCreateWithFlags(&ix->stream, hipStreamDefault) != hipSuccess) return fail(TS_ERR_HIP, "stream creation failed");
     ix->parent = src;
     src->nviews.fetch_add(1);
-    *out = ix;
+    *out = ix.release();
     return TS_OK;
 }
 
@@ -115,21 +111,8 @@ extern "C" int ts_index_destroy(ts_index* ix) {
     hipSetDevice(ix->device);
     if (ix->ordered && ix->order_ev) hipEventSynchronize(ix->order_ev);   // scratch still in use by a call on a caller's stream
     if (ix->stream) hipStreamSynchronize(ix->stream);
-    if (ix->borrowed) {
-        ix->rows = nullptr;
-        ix->id_map = nullptr;
-        if (ix->parent) ix->parent->nviews.fetch_sub(1);
-    }
-    if (ix->attached) ix->rows = nullptr;
-    void* ptrs[] = {ix->rows,  ix->stage,   ix->qstore,   ix->qf32,     ix->cand,       ix->count,  ix->thr, ix->priv, ix->pcount, ix->sample, ix->mask_dev, ix->bias_dev, ix->bias_hist, ix->rank_buf, ix->rank_many_buf, ix->id_map,
-                    ix->fb_list, ix->fb_count, ix->stat, ix->partial, ix->partial2, ix->res_scores, ix->res_idx, ix->dbg, ix->part, ix->wg_ticks, ix->pair_pos,
-                    ix->scr_rows, ix->scr_tile, ix->scr_q, ix->scr_qmeta, ix->scr_cand, ix->scr_count};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    for (hipEvent_t e : ix->ev_pool) hipEventDestroy(e);
-    if (ix->order_ev) hipEventDestroy(ix->order_ev);
-    if (ix->stream) hipStreamDestroy(ix->stream);
-    delete ix;
+    if (ix->parent) ix->parent->nviews.fetch_sub(1);
+    delete ix;      // every buffer it owns, then the events and the stream (host.h: IndexQueue)
     return TS_OK;
 }
 
@@ -179,34 +162,29 @@ extern "C" int ts_index_subset(ts_index* src, const int64_t* rows, int64_t nrows
         if (r < 0 || r >= src->n) return fail(TS_ERR_INVALID, "rows[%lld] = %lld is not in the index", (long long)i, (long long)rows[i]);
         if (i && rows[i] <= rows[i - 1]) return fail(TS_ERR_INVALID, "rows must be strictly ascending (at %lld)", (long long)i);
     }
-    ts_index* ix = nullptr;
-    TS_TRY(ts_index_create(src->device, nrows, src->d, src->dtype, src->metric, &ix));
+    ts_index* made = nullptr;
+    TS_TRY(ts_index_create(src->device, nrows, src->d, src->dtype, src->metric, &made));
+    IndexPtr ix(made);
     if (nrows == 0) {
-        *out = ix;
+        *out = ix.release();
         return TS_OK;
     }
     std::lock_guard<std::mutex> lock(src->mu);
     hipStream_t src_own;
     StreamScope src_scope;
-    if (enter_stream(src, nullptr, &src_own, &src_scope) != TS_OK) {   // uploads enqueued on the source's own or a caller's stream
-        ts_index_destroy(ix);
-        return TS_ERR_HIP;
-    }
+    if (enter_stream(src, nullptr, &src_own, &src_scope) != TS_OK) return TS_ERR_HIP;   // uploads enqueued on the source's own or a caller's stream
     hipStreamSynchronize(src_own);
-    hipError_t e = hipMalloc((void**)&ix->id_map, (size_t)nrows * 8);
+    hipError_t e = (hipError_t)ix->id_map.need((size_t)nrows * 8);
     if (e == hipSuccess) e = hipMemcpyAsync(ix->id_map, rows, (size_t)nrows * 8, hipMemcpyHostToDevice, ix->stream);
     if (e == hipSuccess) {
         const int grid = (int)std::min<int64_t>((nrows + 3) / 4, 8192);
-        gather_rows_kernel<<<grid, 256, 0, ix->stream>>>((const unsigned char*)src->rows, (unsigned char*)ix->rows, ix->id_map,
+        gather_rows_kernel<<<grid, 256, 0, ix->stream>>>(src->rows.as<const unsigned char>(), ix->rows.as<unsigned char>(), ix->id_map,
                                                          src->row_offset, nrows, (int64_t)src->ld * src->elem());
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);
-    if (e != hipSuccess) {
-        ts_index_destroy(ix);
-        return fail(TS_ERR_HIP, "subset copy failed: %s", hipGetErrorString(e));
-    }
-    *out = ix;
+    if (e != hipSuccess) return fail(TS_ERR_HIP, "subset copy failed: %s", hipGetErrorString(e));
+    *out = ix.release();
     return TS_OK;
 }
 
@@ -305,7 +283,7 @@ static int upload_device_locked(ts_index* ix, const void* dev_rows, int src_dtyp
     hipStream_t st;
     StreamScope scope;
     TS_TRY(enter_stream(ix, stream, &st, &scope));
-    char* dst = (char*)ix->rows + (size_t)row0 * ix->ld * ix->elem();
+    char* dst = ix->rows.as<char>() + (size_t)row0 * ix->ld * ix->elem();
     screen_touch(ix, row0, row0 + nrows);
     return prep_dispatch(src_dtype, ix->dtype, ix->metric == TS_METRIC_COS, dev_rows, src_ld, dst, nullptr, ix->ld, ix->d,
                          nrows, nrows, st);
@@ -323,17 +301,17 @@ static int upload_host_locked(ts_index* ix, const void* host_rows, int src_dtype
     screen_touch(ix, row0, row0 + nrows);
     if (src_dtype == ix->dtype && ix->metric == TS_METRIC_IP && ix->ld == ix->d) {
         // stored as given: straight copy into place
-        HIP_TRY(hipMemcpyAsync((char*)ix->rows + (size_t)row0 * src_row, host_rows, (size_t)nrows * src_row, hipMemcpyHostToDevice, own));
+        HIP_TRY(hipMemcpyAsync(ix->rows.as<char>() + (size_t)row0 * src_row, host_rows, (size_t)nrows * src_row, hipMemcpyHostToDevice, own));
         HIP_TRY(hipStreamSynchronize(own));
         return TS_OK;
     }
     TS_TRY(ensure_stage(ix, (size_t)nrows * src_row, src_row));
-    const int64_t rows_per = std::max<int64_t>(1, (int64_t)(ix->stage_bytes / src_row));
+    const int64_t rows_per = std::max<int64_t>(1, (int64_t)(ix->stage.bytes() / src_row));
     for (int64_t r = 0; r < nrows; r += rows_per) {
         const int64_t cnt = std::min(rows_per, nrows - r);
         HIP_TRY(hipMemcpyAsync(ix->stage, (const char*)host_rows + (size_t)r * src_row, (size_t)cnt * src_row,
                                hipMemcpyHostToDevice, own));
-        char* dst = (char*)ix->rows + (size_t)(row0 + r) * ix->ld * ix->elem();
+        char* dst = ix->rows.as<char>() + (size_t)(row0 + r) * ix->ld * ix->elem();
         TS_TRY(prep_dispatch(src_dtype, ix->dtype, ix->metric == TS_METRIC_COS, ix->stage, ix->d, dst, nullptr, ix->ld,
                              ix->d, cnt, cnt, own));
         HIP_TRY(hipStreamSynchronize(own));  // the stage buffer is reused by the next chunk
@@ -359,7 +337,7 @@ extern "C" int ts_index_upload(ts_index* ix, const void* host_rows, int src_dtyp
 // allocation (1.5x, at least what is asked).  Refused while views of the index exist (they hold the old pointer).
 static int grow_locked(ts_index* ix, int64_t want_rows) {
     if (want_rows > 0xFFFFFFF0ll) return fail(TS_ERR_INVALID, "capacity %lld out of range", (long long)want_rows);
-    const int64_t new_pad = std::max<int64_t>(kRowPad, (want_rows + kRowPad - 1) / kRowPad * kRowPad);
+    const int64_t new_pad = padded_rows(want_rows);
     if (new_pad <= ix->n_pad) return TS_OK;
     if (ix->borrowed || ix->id_map) return fail(TS_ERR_UNSUPPORTED, "a view / subset index cannot grow");
     if (ix->attached) return fail(TS_ERR_UNSUPPORTED, "an index over attached rows cannot grow: the rows belong to the caller");
@@ -367,24 +345,17 @@ static int grow_locked(ts_index* ix, int64_t want_rows) {
     HIP_TRY(hipSetDevice(ix->device));
     const size_t row_bytes = (size_t)ix->ld * ix->elem();
     const size_t old_bytes = (size_t)ix->n_pad * row_bytes, new_bytes = (size_t)new_pad * row_bytes;
-    void* fresh = nullptr;
-    hipError_t e = hipMalloc(&fresh, new_bytes);
+    DevArray<void> fresh;       // old and new rows exist together while the rows move: what a move costs
+    hipError_t e = (hipError_t)fresh.need(new_bytes);
     if (e != hipSuccess) return fail(TS_ERR_NOMEM, "hipMalloc of %zu bytes for the grown index failed: %s", new_bytes, hipGetErrorString(e));
     hipStream_t own;
     StreamScope scope;
-    int rc = enter_stream(ix, nullptr, &own, &scope);
-    if (rc == TS_OK) {
-        e = hipMemcpyAsync(fresh, ix->rows, old_bytes, hipMemcpyDeviceToDevice, own);
-        if (e == hipSuccess) e = hipMemsetAsync((char*)fresh + old_bytes, 0, new_bytes - old_bytes, own);
-        if (e == hipSuccess) e = hipStreamSynchronize(own);
-        if (e != hipSuccess) rc = fail(TS_ERR_HIP, "moving the rows failed: %s", hipGetErrorString(e));
-    }
-    if (rc != TS_OK) {
-        hipFree(fresh);
-        return rc;
-    }
-    hipFree(ix->rows);
-    ix->rows = fresh;
+    TS_TRY(enter_stream(ix, nullptr, &own, &scope));
+    e = hipMemcpyAsync(fresh, ix->rows, old_bytes, hipMemcpyDeviceToDevice, own);
+    if (e == hipSuccess) e = hipMemsetAsync(fresh.as<char>() + old_bytes, 0, new_bytes - old_bytes, own);
+    if (e == hipSuccess) e = hipStreamSynchronize(own);
+    if (e != hipSuccess) return fail(TS_ERR_HIP, "moving the rows failed: %s", hipGetErrorString(e));
+    ix->rows = std::move(fresh);        // frees the old rows
     ix->n_pad = new_pad;
     return TS_OK;
 }
@@ -400,7 +371,7 @@ extern "C" int ts_index_attach_device(ts_index* ix, void* dev_rows, int64_t capa
     std::lock_guard<std::mutex> lock(ix->mu);
     if (ix->id_map || ix->parent) return fail(TS_ERR_UNSUPPORTED, "a view / subset index cannot adopt rows");
     if (ix->nviews.load() > 0) return fail(TS_ERR_UNSUPPORTED, "the index has live views");
-    const int64_t need = std::max<int64_t>(kRowPad, (ix->n + kRowPad - 1) / kRowPad * kRowPad);
+    const int64_t need = padded_rows(ix->n);
     if (capacity_rows < need)
         return fail(TS_ERR_INVALID, "the attached allocation holds %lld rows, %lld are needed (n = %lld rounded up to %d)",
                     (long long)capacity_rows, (long long)need, (long long)ix->n, kRowPad);
@@ -415,10 +386,9 @@ extern "C" int ts_index_attach_device(ts_index* ix, void* dev_rows, int64_t capa
     StreamScope scope;
     TS_TRY(enter_stream(ix, nullptr, &own, &scope));
     HIP_TRY(hipStreamSynchronize(own));
-    if (!ix->attached && ix->rows) HIP_TRY(hipFree(ix->rows));
-    ix->rows = dev_rows;
     ix->n_pad = capacity_rows / kRowPad * kRowPad;
-    ix->attached = true;       // destroy / grow must not free it
+    ix->rows.borrow(dev_rows, (size_t)ix->n_pad * ix->ld * ix->elem());     // the index's own rows are freed, the caller's never
+    ix->attached = true;       // the rows belong to the caller: no growth
     return TS_OK;
 }
 
@@ -470,10 +440,10 @@ extern "C" int ts_index_download(ts_index* ix, void* host_rows, int64_t row0, in
     StreamScope scope;
     TS_TRY(enter_stream(ix, nullptr, &own, &scope));
     TS_TRY(ensure_stage(ix, (size_t)nrows * row_bytes, row_bytes));
-    const int64_t rows_per = std::max<int64_t>(1, (int64_t)(ix->stage_bytes / row_bytes));
+    const int64_t rows_per = std::max<int64_t>(1, (int64_t)(ix->stage.bytes() / row_bytes));
     for (int64_t r = 0; r < nrows; r += rows_per) {
         const int64_t cnt = std::min(rows_per, nrows - r);
-        const char* src = (const char*)ix->rows + (size_t)(row0 + r) * ix->ld * ix->elem();
+        const char* src = ix->rows.as<const char>() + (size_t)(row0 + r) * ix->ld * ix->elem();
         if (ix->dtype == TS_F32)
             unpad_rows_kernel<0><<<1024, 256, 0, ix->stream>>>(src, ix->ld, ix->stage, ix->d, cnt);
         else
@@ -583,12 +553,12 @@ extern "C" int ts_timer_create(int device, ts_timer** out) {
     if (!out) return fail(TS_ERR_INVALID, "out is NULL");
     TS_TRY(check_device(device));
     HIP_TRY(hipSetDevice(device));
-    ts_timer* t = new (std::nothrow) ts_timer();
+    std::unique_ptr<ts_timer> t(new (std::nothrow) ts_timer());
     if (!t) return fail(TS_ERR_NOMEM, "host allocation failed");
     t->device = device;
     HIP_TRY(hipEventCreate(&t->a));
     HIP_TRY(hipEventCreate(&t->b));
-    *out = t;
+    *out = t.release();
     return TS_OK;
 }
 extern "C" int ts_timer_start(ts_timer* t, void* stream) {
@@ -613,8 +583,6 @@ extern "C" int ts_timer_elapsed_ms(ts_timer* t, float* ms) {
 extern "C" int ts_timer_destroy(ts_timer* t) {
     if (!t) return TS_OK;
     hipSetDevice(t->device);
-    if (t->a) hipEventDestroy(t->a);
-    if (t->b) hipEventDestroy(t->b);
     delete t;
     return TS_OK;
 }

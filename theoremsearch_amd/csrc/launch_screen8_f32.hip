@@ -11,11 +11,11 @@ static int screen_prepare_f32_w(ts_index* ix, const void* qmat, int nq_launch, h
     return screen_prepare_with<W>(
         ix, true,
         [&](int64_t tile0, unsigned nblk) {
-            quantize_tiles_f32_kernel<W><<<nblk, 256, 0, st>>>((const float*)ix->rows, (signed char*)ix->scr_rows, (float4*)ix->scr_tile, tile0);
+            quantize_tiles_f32_kernel<W><<<nblk, 256, 0, st>>>(ix->rows.as<const float>(), ix->scr_rows.as<signed char>(), ix->scr_tile.as<float4>(), tile0);
         },
         [&] {
-            quantize_queries_f32_kernel<W><<<kMfmaQ, 64, 0, st>>>((const float*)qmat, std::min(nq_launch, kMfmaQ), (signed char*)ix->scr_q,
-                                                               (float4*)ix->scr_qmeta, ix->scr_count);
+            quantize_queries_f32_kernel<W><<<kMfmaQ, 64, 0, st>>>((const float*)qmat, std::min(nq_launch, kMfmaQ), ix->scr_q.as<signed char>(),
+                                                               ix->scr_qmeta.as<float4>(), ix->scr_count);
         });
 }
 
@@ -28,7 +28,7 @@ int screen_prepare_f32(ts_index* ix, const void* qmat, int nq_launch, hipStream_
 int screen_full_pass_f32(ts_index* ix, int nb, int nq, int grid, int variant, hipStream_t st, const MfmaArgs& a) {
     TS_TRY(screen_tile_pass(ix, nb, grid, variant, st, a));
     ScreenRescoreF32Args r;
-    r.rows = (const float*)ix->rows;
+    r.rows = ix->rows.as<const float>();
     r.q = (const float*)a.q;
     r.thr = a.thr;
     r.scand = ix->scr_cand;

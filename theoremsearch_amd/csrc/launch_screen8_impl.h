@@ -33,11 +33,8 @@ template <int W, class QuantizeTiles, class QuantizeQueries>
 static int screen_prepare_with(ts_index* ix, bool quantize_queries, QuantizeTiles&& quantize_tiles, QuantizeQueries&& quantize_query_rows) {
     const int64_t tiles = ix->n_pad / kTileRows;
     if (ix->scr_pad != ix->n_pad) {
-        if (ix->scr_rows) HIP_TRY(hipFree(ix->scr_rows));
-        if (ix->scr_tile) HIP_TRY(hipFree(ix->scr_tile));
-        ix->scr_rows = nullptr; ix->scr_tile = nullptr; ix->scr_pad = 0;
-        HIP_TRY(hipMalloc(&ix->scr_rows, (size_t)ix->n_pad * W));
-        HIP_TRY(hipMalloc((void**)&ix->scr_tile, (size_t)tiles * 16));
+        ix->scr_pad = 0;
+        DEV_TRY(remake(ix->scr_rows, (size_t)ix->n_pad * W, ix->scr_tile, (size_t)tiles * 16));
         ix->scr_pad = ix->n_pad;
         ix->scr_lo = 0;
         ix->scr_hi = ix->n_pad;
@@ -52,10 +49,10 @@ static int screen_prepare_with(ts_index* ix, bool quantize_queries, QuantizeTile
         }
         ix->scr_lo = ix->scr_hi = 0;
     }
-    if (!ix->scr_q) HIP_TRY(hipMalloc(&ix->scr_q, (size_t)kMfmaQ * W));
-    if (!ix->scr_qmeta) HIP_TRY(hipMalloc((void**)&ix->scr_qmeta, (size_t)kMfmaQ * 16));
-    if (!ix->scr_cand) HIP_TRY(hipMalloc((void**)&ix->scr_cand, (size_t)kMfmaQ * kScreenCap * 8));
-    if (!ix->scr_count) HIP_TRY(hipMalloc((void**)&ix->scr_count, (size_t)kMfmaQ * 4));
+    DEV_TRY(ix->scr_q.need((size_t)kMfmaQ * W));
+    DEV_TRY(ix->scr_qmeta.need((size_t)kMfmaQ * 16));
+    DEV_TRY(ix->scr_cand.need((size_t)kMfmaQ * kScreenCap * 8));
+    DEV_TRY(ix->scr_count.need((size_t)kMfmaQ * 4));
     if (quantize_queries) {
         quantize_query_rows();
         HIP_TRY(hipGetLastError());
@@ -68,11 +65,11 @@ static int screen_prepare_w(ts_index* ix, const void* qmat, int nq_launch, bool 
     return screen_prepare_with<W>(
         ix, quantize_queries,
         [&](int64_t tile0, unsigned nblk) {
-            quantize_tiles_kernel<W><<<nblk, 256, 0, st>>>((const unsigned short*)ix->rows, (signed char*)ix->scr_rows, (float4*)ix->scr_tile, tile0);
+            quantize_tiles_kernel<W><<<nblk, 256, 0, st>>>(ix->rows.as<const unsigned short>(), ix->scr_rows.as<signed char>(), ix->scr_tile.as<float4>(), tile0);
         },
         [&] {
-            quantize_queries_kernel<W><<<kMfmaQ, 64, 0, st>>>((const unsigned short*)qmat, std::min(nq_launch, kMfmaQ), (signed char*)ix->scr_q,
-                                                           (float4*)ix->scr_qmeta, ix->scr_count);
+            quantize_queries_kernel<W><<<kMfmaQ, 64, 0, st>>>((const unsigned short*)qmat, std::min(nq_launch, kMfmaQ), ix->scr_q.as<signed char>(),
+                                                           ix->scr_qmeta.as<float4>(), ix->scr_count);
         });
 }
 
@@ -84,13 +81,13 @@ static int screen_prepare_w(ts_index* ix, const void* qmat, int nq_launch, bool 
 template <int W>
 static int screen_tile_pass_w(ts_index* ix, int nb, int grid, int variant, hipStream_t st, const MfmaArgs& a, bool late = false) {
     MfmaArgs s = a;
-    s.corpus = (const unsigned short*)ix->scr_rows;
-    s.q = (const unsigned short*)ix->scr_q;
+    s.corpus = ix->scr_rows.as<const unsigned short>();
+    s.q = ix->scr_q.as<const unsigned short>();
     s.cand = ix->scr_cand;
     s.count = ix->scr_count;
     s.cap = kScreenCap;
-    s.scr_tile = (const float4*)ix->scr_tile;
-    s.scr_q = (const float4*)ix->scr_qmeta;
+    s.scr_tile = ix->scr_tile.as<const float4>();
+    s.scr_q = ix->scr_qmeta.as<const float4>();
     if constexpr (W == 768)
         if (late && nb == 4 && variant == kVariantProduct && s.row_mask == nullptr) return launch_screen8_late(ix->device, grid, st, s);
     switch (nb) {
@@ -109,7 +106,7 @@ template <int W>
 static int screen_full_pass_w(ts_index* ix, int nb, int nq, int grid, int variant, bool ksplit, hipStream_t st, const MfmaArgs& a) {
     TS_TRY(screen_tile_pass_w<W>(ix, nb, grid, variant, st, a, W == 768 && ix->dtype == TS_BF16 && ix->knobs.get(K_MFMA_SCREEN_LATE, 1) != 0));
     ScreenRescoreArgs r;
-    r.rows = (const unsigned short*)ix->rows;
+    r.rows = ix->rows.as<const unsigned short>();
     r.q = a.q;
     r.thr = a.thr;
     r.scand = ix->scr_cand;

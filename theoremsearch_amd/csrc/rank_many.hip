@@ -77,8 +77,8 @@ extern "C" int ts_rank_many(ts_index* ix, const void* queries, int q_dtype, int 
     QueryFeed feed;
     TS_TRY(query_feed_open(&feed, ix, queries, q_dtype, q_on_device, nq, false, st));
     constexpr int kSlots = kQBlock * kRankT;
-    TS_TRY(ensure(&ix->rank_many_buf, &ix->rank_many_bytes, (size_t)kSlots * (8 + 8 + 4 + 4 + 4) + (size_t)kQBlock * 8));
-    int64_t* d_grow = (int64_t*)ix->rank_many_buf;
+    DEV_TRY(ix->rank_many_buf.need((size_t)kSlots * (8 + 8 + 4 + 4 + 4) + (size_t)kQBlock * 8));
+    int64_t* d_grow = ix->rank_many_buf.as<int64_t>();
     u64* d_tkeys = (u64*)(d_grow + kSlots);
     float* d_gscore = (float*)(d_tkeys + kSlots);
     int* d_gquery = (int*)(d_gscore + kSlots);

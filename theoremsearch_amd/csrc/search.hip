@@ -6,34 +6,29 @@
 
 static_assert(kSelectHistKeys == kHistSelectMax, "scan_plan.h plans the select rounds for the histogram select's capacity");
 
-// one scratch buffer, once: a failed allocation leaves the others as they are and is retried by the next call
+// scratch that starts zeroed: a failed allocation leaves the others as they are and is retried by the next call
 template <class T>
-static int scratch_need(T** slot, size_t bytes, bool zero) {
-    if (*slot) return TS_OK;
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, bytes));
-    if (zero) {
-        const hipError_t e = hipMemset(p, 0, bytes);
-        if (e != hipSuccess) {
-            hipFree(p);
-            return fail(TS_ERR_HIP, "hipMemset of search scratch failed: %s", hipGetErrorString(e));
-        }
-    }
-    *slot = (T*)p;
+static int need_zeroed(DevArray<T>& a, size_t bytes) {
+    bool zeroing = false;
+    const hipError_t e = (hipError_t)a.need_zeroed(bytes, &zeroing);
+    if (zeroing) return fail(TS_ERR_HIP, "hipMemset of search scratch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? TS_ERR_NOMEM : TS_ERR_HIP, "hipMalloc of %zu bytes of search scratch failed: %s", bytes, hipGetErrorString(e));
     return TS_OK;
 }
 
 static int ensure_search_scratch(ts_index* ix, int k) {
-    TS_TRY(scratch_need(&ix->count, (size_t)kQBlock * 4, true));
-    TS_TRY(scratch_need(&ix->thr, (size_t)kQBlock * 4, false));
-    TS_TRY(scratch_need(&ix->fb_list, (size_t)kQBlock * 4, false));
-    TS_TRY(scratch_need(&ix->fb_count, 16, true));
-    TS_TRY(scratch_need(&ix->stat, (size_t)kQBlock * 4, true));
-    if (mfma_index(ix)) TS_TRY(scratch_need(&ix->cand, (size_t)kQBlock * kCandCap * 8, false));
+    TS_TRY(need_zeroed(ix->count, (size_t)kQBlock * 4));
+    DEV_TRY(ix->thr.need((size_t)kQBlock * 4));
+    DEV_TRY(ix->fb_list.need((size_t)kQBlock * 4));
+    TS_TRY(need_zeroed(ix->fb_count, 16));
+    TS_TRY(need_zeroed(ix->stat, (size_t)kQBlock * 4));
+    if (mfma_index(ix)) DEV_TRY(ix->cand.need((size_t)kQBlock * kCandCap * 8));
     // scan partials: [256 slots][grid][k] keys, and what the select rounds write (ping-pong)
     const ScanScratch keys = scan_scratch(ix->cu_count, k);
-    TS_TRY(ensure((void**)&ix->partial, &ix->partial_bytes, keys.partial * 8));
-    return ensure((void**)&ix->partial2, &ix->partial2_bytes, keys.partial2 * 8);
+    DEV_TRY(ix->partial.need(keys.partial * 8));
+    DEV_TRY(ix->partial2.need(keys.partial2 * 8));
+    return TS_OK;
 }
 
 int query_feed_open(QueryFeed* f, ts_index* ix, const void* queries, int q_dtype, int q_on_device, int nq, bool f32copy, hipStream_t st) {
@@ -44,8 +39,8 @@ int query_feed_open(QueryFeed* f, ts_index* ix, const void* queries, int q_dtype
     f->on_device = q_on_device != 0;
     f->f32copy = f32copy;
     f->st = st;
-    TS_TRY(scratch_need(&ix->qstore, (size_t)kQBlock * ix->ld * ix->elem(), false));
-    if (f32copy) TS_TRY(scratch_need(&ix->qf32, (size_t)kQBlock * ix->ld * 4, false));
+    DEV_TRY(ix->qstore.need((size_t)kQBlock * ix->ld * ix->elem()));
+    if (f32copy) DEV_TRY(ix->qf32.need((size_t)kQBlock * ix->ld * 4));
     if (!f->on_device) TS_TRY(ensure_stage(ix, (size_t)std::min(nq, kQBlock) * f->row_bytes, 0));   // one block of queries at a time
     return TS_OK;
 }
@@ -131,7 +126,7 @@ static int run_select_rounds(ts_index* ix, int slots, int m, int k, float* out_s
         const SelectRound& rd = p.round[r];
         a.out = (r & 1) ? ix->partial : ix->partial2;
         a.out_stride = rd.out;
-        if ((size_t)slots * rd.out * 8 > ((r & 1) ? ix->partial_bytes : ix->partial2_bytes))
+        if ((size_t)slots * rd.out * 8 > ((r & 1) ? ix->partial : ix->partial2).bytes())
             return fail(TS_ERR_INTERNAL, "select round %d of %d x %d keys does not fit its scratch", r, slots, rd.out);
         if (rd.seg == 4096) select_kernel<4096><<<dim3(rd.nseg, slots), 256, 0, st>>>(a);
         else select_kernel<1024><<<dim3(rd.nseg, slots), 256, 0, st>>>(a);
@@ -181,7 +176,7 @@ int scan_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
     a.bias = ix->active_bias;
     a.bias_w = ix->active_bias_w;
     if (one_launch) {
-        a.done_ctr = (unsigned*)ix->fb_count + 2;     // zeroed with the block, left zeroed by the kernel
+        a.done_ctr = ix->fb_count.as<unsigned>() + 2;    // zeroed with the block, left zeroed by the kernel
         a.out_scores = out_scores;
         a.out_idx = out_idx;
         a.row_offset = ix->row_offset;
@@ -229,7 +224,7 @@ static int search_validate(const ts_index* ix, const void* queries, int q_dtype,
 static int install_bias(ts_index* ix, const BiasSpec& bias, hipStream_t st) {
     ix->active_bias = bias.bias;
     if (!bias.on_device) {
-        TS_TRY(ensure((void**)&ix->bias_dev, &ix->bias_bytes, std::max<size_t>((size_t)ix->n * 4, 4)));
+        DEV_TRY(ix->bias_dev.need(std::max<size_t>((size_t)ix->n * 4, 4)));
         HIP_TRY(hipMemcpyAsync(ix->bias_dev, bias.bias, (size_t)ix->n * 4, hipMemcpyHostToDevice, st));
         ix->active_bias = ix->bias_dev;
     }
@@ -241,7 +236,7 @@ static int install_mask(ts_index* ix, const uint32_t* row_mask, int mask_on_devi
     ix->active_mask = row_mask;
     if (!mask_on_device) {
         const size_t words = (size_t)((ix->n + 31) / 32);
-        TS_TRY(ensure((void**)&ix->mask_dev, &ix->mask_bytes, std::max<size_t>(words * 4, 4)));
+        DEV_TRY(ix->mask_dev.need(std::max<size_t>(words * 4, 4)));
         HIP_TRY(hipMemcpyAsync(ix->mask_dev, row_mask, words * 4, hipMemcpyHostToDevice, st));
         ix->active_mask = ix->mask_dev;
     }
@@ -292,11 +287,8 @@ static int search_choose(ts_index* ix, int algo, int nq, int k, const BiasSpec* 
 static int result_buffers(ts_index* ix, size_t want, int out_on_device, float** dscores, int64_t** didx) {
     if (out_on_device) return TS_OK;
     if (ix->res_cap < want) {
-        if (ix->res_scores) HIP_TRY(hipFree(ix->res_scores));
-        if (ix->res_idx) HIP_TRY(hipFree(ix->res_idx));
-        ix->res_scores = nullptr; ix->res_idx = nullptr; ix->res_cap = 0;
-        HIP_TRY(hipMalloc((void**)&ix->res_scores, want * 4));
-        HIP_TRY(hipMalloc((void**)&ix->res_idx, want * 8));
+        ix->res_cap = 0;
+        DEV_TRY(remake(ix->res_scores, want * 4, ix->res_idx, want * 8));
         ix->res_cap = want;
     }
     *dscores = ix->res_scores;
@@ -347,7 +339,7 @@ static int search_unbias(ts_index* ix, const BiasSpec& bias, int64_t cnt, const 
                          int out_on_device, DevBuf* tmp, hipStream_t st) {
     float* dsims = bias.out_sims;
     if (!out_on_device) {
-        HIP_TRY(tmp->alloc((size_t)cnt * 4));
+        DEV_TRY(tmp->need((size_t)cnt * 4));
         dsims = tmp->as<float>();
     }
     unbias_kernel<<<(unsigned)((cnt + 255) / 256), 256, 0, st>>>(dscores, didx, ix->active_bias, ix->active_bias_w, ix->row_offset, dsims, cnt);
@@ -507,8 +499,8 @@ static int rank_impl(ts_index* ix, const void* queries, int q_dtype, int q_on_de
     TS_TRY(enter_stream(ix, stream, &st, &scope));
     TS_TRY(ensure_search_scratch(ix, 1));
     constexpr size_t kPer = 8 + 8 + 4;
-    TS_TRY(ensure(&ix->rank_buf, &ix->rank_bytes, (size_t)kQBlock * kPer));
-    int64_t* d_target = (int64_t*)ix->rank_buf;  // rows, or ready-made keys
+    DEV_TRY(ix->rank_buf.need((size_t)kQBlock * kPer));
+    int64_t* d_target = ix->rank_buf.as<int64_t>();  // rows, or ready-made keys
     unsigned long long* d_counts = (unsigned long long*)(d_target + kQBlock);
     float* d_tscore = (float*)(d_counts + kQBlock);
     QueryFeed feed;
@@ -594,7 +586,7 @@ extern "C" int ts_scores(ts_index* ix, const void* queries, int q_dtype, int q_o
         if (want > free_b / 2)
             return fail(TS_ERR_NOMEM, "score matrix of %d x %lld floats (%zu bytes) does not fit: use ts_search / ts_rank_of",
                         nq, (long long)ix->n, want);
-        HIP_TRY(tmp.alloc(want));
+        DEV_TRY(tmp.need(want));
         dout = tmp.as<float>();
     }
     QueryFeed feed;

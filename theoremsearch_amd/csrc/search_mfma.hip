@@ -168,7 +168,7 @@ int mfma_block_queries(const ts_index* ix, int nq) {
 // Once per biased matrix search, before its first block of queries: the histogram of w * bias[row] over every row the call may
 // return (kernels_sample_biased.h) - two short passes over the bias array and the mask, n * 4 bytes each.
 int bias_histogram(ts_index* ix, hipStream_t st) {
-    if (!ix->bias_hist) HIP_TRY(hipMalloc((void**)&ix->bias_hist, (size_t)kBiasHistWords * 4));
+    DEV_TRY(ix->bias_hist.need((size_t)kBiasHistWords * 4));
     HIP_TRY(hipMemsetAsync(ix->bias_hist, 0, (size_t)kBiasHistWords * 4, st));
     BiasHistArgs a;
     a.bias = ix->active_bias;
@@ -278,25 +278,19 @@ static MfmaPlan mfma_plan(const ts_index* ix, int nq, int k) {
 
 // The per-handle scratch this plan needs: made on first use, re-made when the grid outgrows it.
 static int mfma_scratch(ts_index* ix, const MfmaPlan& p, hipStream_t st) {
-    if (p.dense_sample && !ix->sample) HIP_TRY(hipMalloc((void**)&ix->sample, (size_t)kMfmaQ * kLevelSortMax * 4));
+    if (p.dense_sample) DEV_TRY(ix->sample.need((size_t)kMfmaQ * kLevelSortMax * 4));
     if (!p.anyd && ix->priv_writers < 4 * p.grid) {            // (the general-width pass writes the shared lists only)
-        if (ix->priv) HIP_TRY(hipFree(ix->priv));
-        if (ix->pcount) HIP_TRY(hipFree(ix->pcount));
-        ix->priv = nullptr; ix->pcount = nullptr; ix->priv_writers = 0;
+        ix->priv_writers = 0;
         static_assert(4 * kMfma16PrivCap == 2 * kMfmaPrivCap, "both shapes use the same list bytes per workgroup");
-        HIP_TRY(hipMalloc((void**)&ix->priv, (size_t)kMfmaQ * 4 * p.grid * kMfma16PrivCap * 8));
-        HIP_TRY(hipMalloc((void**)&ix->pcount, (size_t)kMfmaQ * 4 * p.grid * 4));
+        DEV_TRY(remake(ix->priv, (size_t)kMfmaQ * 4 * p.grid * kMfma16PrivCap * 8, ix->pcount, (size_t)kMfmaQ * 4 * p.grid * 4));
         ix->priv_writers = 4 * p.grid;
     }
     const int wgs = p.wgs;
     const int64_t full_tiles = p.lv.back().ntiles;
     if (p.balance && (ix->part_g != wgs || ix->part_ntiles != full_tiles)) {
         if (ix->part_g != wgs) {
-            if (ix->part) HIP_TRY(hipFree(ix->part));
-            if (ix->wg_ticks) HIP_TRY(hipFree(ix->wg_ticks));
-            ix->part = nullptr; ix->wg_ticks = nullptr; ix->part_g = 0; ix->part_ntiles = -1;
-            HIP_TRY(hipMalloc((void**)&ix->part, (size_t)(wgs + 1) * 8));
-            HIP_TRY(hipMalloc((void**)&ix->wg_ticks, (size_t)wgs * 4));
+            ix->part_g = 0; ix->part_ntiles = -1;
+            DEV_TRY(remake(ix->part, (size_t)(wgs + 1) * 8, ix->wg_ticks, (size_t)wgs * 4));
             ix->part_g = wgs;
         }
         std::vector<int64_t> equal((size_t)wgs + 1);
@@ -308,11 +302,11 @@ static int mfma_scratch(ts_index* ix, const MfmaPlan& p, hipStream_t st) {
     }
     if (p.pair_lag > 0 && !ix->pair_pos) {
         // one word per workgroup of the pass (index 2 * pair + half < grid): sized for the largest grid the option allows
-        HIP_TRY(hipMalloc((void**)&ix->pair_pos, kMfmaMaxGrid * sizeof(unsigned)));
+        DEV_TRY(ix->pair_pos.need(kMfmaMaxGrid * sizeof(unsigned)));
         HIP_TRY(hipMemsetAsync(ix->pair_pos, 0, kMfmaMaxGrid * sizeof(unsigned), st));
     }
 #ifdef TS_DIAG
-    if (variant_gets_dbg(p.variant) && !ix->dbg) HIP_TRY(hipMalloc((void**)&ix->dbg, 2048 * 4 * 4 * 8));
+    if (variant_gets_dbg(p.variant)) DEV_TRY(ix->dbg.need(2048 * 4 * 4 * 8));
 #endif
     return TS_OK;
 }
@@ -352,8 +346,8 @@ static int mfma_sample(ts_index* ix, const MfmaPlan& p, int nq, const void* qmat
     }
     ix->rebalance_pending = false;
     if (p.screen_rider) {
-        sa.scr_qimg = (signed char*)ix->scr_q;
-        sa.scr_qmeta = (float4*)ix->scr_qmeta;
+        sa.scr_qimg = ix->scr_q.as<signed char>();
+        sa.scr_qmeta = ix->scr_qmeta.as<float4>();
         sa.scr_count = ix->scr_count;
         sa.scr_nrows = std::min(p.nq_launch, kMfmaQ);
     }
@@ -476,7 +470,7 @@ static int mfma_level(ts_index* ix, const MfmaPlan& p, size_t i, int nq, int k, 
     const Level& lv = p.lv[i];
     const bool full_pass = (i + 1 == p.lv.size());
     MfmaArgs a;
-    a.corpus = (const unsigned short*)ix->rows;
+    a.corpus = ix->rows.as<const unsigned short>();
     a.n = ix->n;
     a.ntiles = lv.ntiles;
     a.tile_stride = lv.stride;

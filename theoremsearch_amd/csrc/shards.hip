@@ -64,7 +64,7 @@ extern "C" int ts_merge_topk(int device, const float* scores, const int64_t* idx
     // one temporary block (freed on every return path): ids in | ids out | scores in | scores out
     const size_t nin = (size_t)nparts * nq * k_in, nout = (size_t)nq * k_out;
     DevBuf tmp;
-    HIP_TRY(tmp.alloc(nin * 12 + nout * 12));
+    DEV_TRY(tmp.need(nin * 12 + nout * 12));
     int64_t* di = tmp.as<int64_t>();
     int64_t* doi = di + nin;
     float* ds = (float*)(doi + nout);
@@ -186,9 +186,7 @@ struct ts_comm {
     ncclComm_t comm = nullptr;
     std::mutex mu;
     // exchange buffers of ts_comm_search, two of each (a caller may keep one batch in flight while the next starts)
-    void* mine[2] = {nullptr, nullptr};
-    void* all[2] = {nullptr, nullptr};
-    size_t mine_bytes[2] = {0, 0}, all_bytes[2] = {0, 0};
+    DevArray<void> mine[2], all[2];
     int parity = 0;
 };
 
@@ -234,11 +232,7 @@ extern "C" int ts_comm_destroy(ts_comm* c) {
     hipDeviceSynchronize();
     RcclApi* api = rccl_api();
     if (api && c->comm) api->CommDestroy(c->comm);
-    for (int b = 0; b < 2; ++b) {
-        if (c->mine[b]) hipFree(c->mine[b]);
-        if (c->all[b]) hipFree(c->all[b]);
-    }
-    delete c;
+    delete c;       // and with it the exchange buffers
     return TS_OK;
 }
 
@@ -280,15 +274,15 @@ extern "C" int ts_comm_search(ts_comm* c, ts_index* shard, const void* queries, 
     const int64_t blk = packed_bytes(nq, k), idx_off = packed_idx_off(nq, k);
     const int b = c->parity;
     c->parity ^= 1;
-    TS_TRY(ensure(&c->mine[b], &c->mine_bytes[b], (size_t)blk));
-    TS_TRY(ensure(&c->all[b], &c->all_bytes[b], (size_t)blk * c->world));
-    TS_TRY(ts_search(shard, queries, q_dtype, q_on_device, nq, k, (float*)c->mine[b], (int64_t*)((char*)c->mine[b] + idx_off), 1, st));
+    DEV_TRY(c->mine[b].need((size_t)blk));
+    DEV_TRY(c->all[b].need((size_t)blk * c->world));
+    TS_TRY(ts_search(shard, queries, q_dtype, q_on_device, nq, k, c->mine[b].as<float>(), (int64_t*)(c->mine[b].as<char>() + idx_off), 1, st));
     NCCL_TRY(api, api->AllGather(c->mine[b], c->all[b], (size_t)blk, ncclUint8, c->comm, st));
     float* ds = out_scores;
     int64_t* di = out_idx;
     DevBuf tmp;
     if (!out_on_device) {
-        HIP_TRY(tmp.alloc((size_t)nq * k * 12));
+        DEV_TRY(tmp.need((size_t)nq * k * 12));
         di = tmp.as<int64_t>();
         ds = (float*)(di + (size_t)nq * k);
     }
@@ -365,11 +359,9 @@ struct ts_shards {
     std::vector<int64_t> lo;          // shard g holds global rows [lo[g], lo[g + 1])
     std::vector<ts_index*> shard;
     std::vector<ncclComm_t> comm;
-    std::vector<void*> qdev, mine, all;
-    std::vector<size_t> qdev_bytes, mine_bytes, all_bytes;
+    std::vector<DevArray<void>> qdev, mine, all;        // one of each per shard, on the shard's device
     std::vector<hipEvent_t> done;
-    void* fin = nullptr;
-    size_t fin_bytes = 0;
+    DevArray<void> fin;                                 // the merged answer, on device[0]
     std::vector<std::unique_ptr<ShardWorker>> worker;   // one per shard when ngpu > 1
     void* qpin = nullptr;                               // the query batch in pinned host memory (every device copies from it)
     size_t qpin_bytes = 0;
@@ -385,16 +377,16 @@ extern "C" int ts_shards_destroy(ts_shards* s) {
         hipSetDevice(s->device[g]);
         hipDeviceSynchronize();
         if (api && g < (int)s->comm.size() && s->comm[g]) api->CommDestroy(s->comm[g]);
-        if (g < (int)s->qdev.size() && s->qdev[g]) hipFree(s->qdev[g]);
-        if (g < (int)s->mine.size() && s->mine[g]) hipFree(s->mine[g]);
-        if (g < (int)s->all.size() && s->all[g]) hipFree(s->all[g]);
+        s->qdev[g].reset();      // (sized before the first shard exists: ts_shards_create)
+        s->mine[g].reset();
+        s->all[g].reset();
         ts_index_destroy(s->shard[g]);
     }
     for (hipEvent_t e : s->done)
         if (e) hipEventDestroy(e);
     if (s->fin) {
         hipSetDevice(s->device[0]);
-        hipFree(s->fin);
+        s->fin.reset();
     }
     delete s;
     return TS_OK;
@@ -428,8 +420,7 @@ extern "C" int ts_shards_create(int32_t ngpu, const int32_t* devices, int64_t n_
         s->device.push_back(dev);
     }
     for (int g = 0; g <= ngpu; ++g) s->lo.push_back(n_total * g / ngpu);
-    s->qdev.assign(ngpu, nullptr); s->mine.assign(ngpu, nullptr); s->all.assign(ngpu, nullptr);
-    s->qdev_bytes.assign(ngpu, 0); s->mine_bytes.assign(ngpu, 0); s->all_bytes.assign(ngpu, 0);
+    s->qdev.resize(ngpu); s->mine.resize(ngpu); s->all.resize(ngpu);
     s->done.assign(ngpu, nullptr);
     for (int g = 0; g < ngpu; ++g) {
         ts_index* ix = nullptr;
@@ -542,11 +533,11 @@ extern "C" int ts_shards_search(ts_shards* s, const void* queries, int q_dtype, 
     }
     auto enqueue = [s, qsrc, qbytes, blk, idx_off, G, q_dtype, nq, k, &st](int g) -> int {
         HIP_TRY(hipSetDevice(s->device[g]));
-        TS_TRY(ensure(&s->qdev[g], &s->qdev_bytes[g], qbytes));
-        TS_TRY(ensure(&s->mine[g], &s->mine_bytes[g], (size_t)blk));
-        TS_TRY(ensure(&s->all[g], &s->all_bytes[g], (size_t)blk * G));
+        DEV_TRY(s->qdev[g].need(qbytes));
+        DEV_TRY(s->mine[g].need((size_t)blk));
+        DEV_TRY(s->all[g].need((size_t)blk * G));
         HIP_TRY(hipMemcpyAsync(s->qdev[g], qsrc, qbytes, hipMemcpyHostToDevice, st[g]));
-        TS_TRY(ts_search(s->shard[g], s->qdev[g], q_dtype, 1, nq, k, (float*)s->mine[g], (int64_t*)((char*)s->mine[g] + idx_off), 1, st[g]));
+        TS_TRY(ts_search(s->shard[g], s->qdev[g], q_dtype, 1, nq, k, s->mine[g].as<float>(), (int64_t*)(s->mine[g].as<char>() + idx_off), 1, st[g]));
         if (!s->use_rccl) HIP_TRY(hipEventRecord(s->done[g], st[g]));
         return TS_OK;
     };
@@ -587,12 +578,12 @@ extern "C" int ts_shards_search(ts_shards* s, const void* queries, int q_dtype, 
         HIP_TRY(hipSetDevice(s->device[0]));
         for (int g = 0; g < G; ++g) {
             if (g) HIP_TRY(hipStreamWaitEvent(st[0], s->done[g], 0));
-            HIP_TRY(hipMemcpyPeerAsync((char*)s->all[0] + (size_t)g * blk, s->device[0], s->mine[g], s->device[g], (size_t)blk, st[0]));
+            HIP_TRY(hipMemcpyPeerAsync(s->all[0].as<char>() + (size_t)g * blk, s->device[0], s->mine[g], s->device[g], (size_t)blk, st[0]));
         }
     }
     HIP_TRY(hipSetDevice(s->device[0]));
-    TS_TRY(ensure(&s->fin, &s->fin_bytes, (size_t)nq * k * 12));
-    int64_t* di = (int64_t*)s->fin;
+    DEV_TRY(s->fin.need((size_t)nq * k * 12));
+    int64_t* di = s->fin.as<int64_t>();
     float* ds = (float*)(di + (size_t)nq * k);
     TS_TRY(merge_launch(merge_args_packed(s->all[0], blk, idx_off, G, nq, k, k, ds, di), st[0]));
     TS_TRY(results_to_host(out_scores, out_idx, ds, di, (size_t)nq * k, st[0]));
