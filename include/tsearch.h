@@ -296,9 +296,10 @@ int ts_rank_of(ts_index *ix, const void *queries, int q_dtype, int q_on_device, 
  * out_rank / out_score are aligned with target_rows; -1 / NaN for rows outside this index or with a NaN score.
  * A list may be empty and may repeat a row (repeats share one rank).  Target rows are global ids (row_offset applies);
  * subset indexes are refused.  Queries are prepared as ts_search prepares them.  Host pointers; out_score may be NULL.
- * bf16 and fp32 indexes at d = 384, 512, 768, 1024: one matrix pass over the corpus per block of 256 queries and per 16
- * targets of the longest list (a gather launch computes the targets' scores by the same arithmetic first).  Other widths:
- * one ts_rank_of pass per target column - correct and slow.
+ * bf16 and fp32 indexes at every d that is a multiple of 64 from 128 up to a 4,096-byte row (bf16 up to d = 2048, fp32 up to
+ * d = 1024): one matrix pass over the corpus per block of 256 queries and per 16 targets of the longest list (a gather launch
+ * computes the targets' scores by the same arithmetic first).  Other widths (d = 64, widths that are no multiple of 64): one
+ * ts_rank_of pass per target column - correct and slow.
  * Arithmetic contract: the ranks are consistent with the scores returned here (distinct targets of one query have
  * distinct ranks, ordered by (score, -row)).  Where the fp64 truth cannot separate a target from its neighbours, a rank may
  * differ from ts_rank_of's and from the search paths' positions by the count of those neighbours. */
@@ -312,6 +313,22 @@ int ts_rank_many(ts_index *ix, const void *queries, int q_dtype, int q_on_device
  * document itself never counts).  out_counts[i] = -1 for a NaN score.  Host pointers. */
 int ts_count_above(ts_index *ix, const void *queries, int q_dtype, int q_on_device, int32_t nq, const float *target_scores,
                    const int64_t *target_ids, int64_t *out_counts, void *stream);
+
+/* The many-targets form of ts_count_above, and the sharded form of ts_rank_many: for query i and each of its targets t in
+ * [target_offsets[i], target_offsets[i+1]), out_counts[t] = the number of rows of THIS index that rank before a document with
+ * score target_scores[t] and global id target_ids[t] (score descending, then global id ascending).  The document may be a row
+ * of this index (it never counts itself) or lie before or behind it.  out_counts[t] = -1 for a NaN score.  A list may be
+ * empty, longer than 16 (several passes) and may repeat a document.  Host pointers; subset indexes are refused; the argument
+ * checks are those of ts_rank_many.
+ * At the widths ts_rank_many's matrix pass serves: one counting pass per block of 256 queries and per 16 targets of the
+ * longest list, no gather launch (the keys are made on the host).  Other widths: one ts_count_above per target column.
+ * Contract: summed over the shards of a corpus, the counts are the document's rank in the whole corpus, given that the score
+ * handed in is the one ts_rank_many returned for the document on the shard that owns it, and that all shards share storage
+ * type and width - every shard then scores its rows by the same arithmetic (matrix pass or scan) as the owner scored the
+ * document. */
+int ts_count_above_many(ts_index *ix, const void *queries, int q_dtype, int q_on_device, int32_t nq,
+                        const int64_t *target_offsets, const float *target_scores, const int64_t *target_ids,
+                        int64_t *out_counts, void *stream);
 
 /* Full [nq x n] fp32 score matrix (small N only): util.cos_sim(q_emb, s_emb) of
  * compare_embeddings.py:24,61.  out row stride is n. */

@@ -26,25 +26,20 @@
 //     atomic per (workgroup, query, target) at the end.  NaN scores and padding rows never count.
 #pragma once
 #include "kernels_mfma16_ops.h"
+#include "rank_plan.h"
 
 namespace ts {
 
-constexpr int kRankT = 16;           // targets per query per pass (the host splits longer lists into passes)
+// kRankT, kRankRowPad, the served widths, RB and the LDS bytes of a launch: rank_plan.h
 constexpr int kRankThreads = 512;    // 8 waves
 constexpr int kRankWaves = kRankThreads / 64;
-constexpr int kRankNBW = 256 / 16 / kRankWaves;   // query blocks per wave (2)
+constexpr int kRankNBW = kRankQueries / 16 / kRankWaves;   // query blocks per wave (2)
 constexpr int kRankSeg = 16;         // k-steps whose query fragments are in flight together
-constexpr int kRankRowPad = 16;      // bytes between LDS rows: 16-row fragment reads spread over the banks
-
-// RB = row blocks of 16 per tile: 4 while a 64-row tile fits the LDS (row <= 2048 bytes: bf16 at every served width, fp32
-// at d <= 512), else 2
-constexpr int rank_rb(int row_bytes) { return row_bytes <= 2048 ? 4 : 2; }
-constexpr int rank_lds_bytes(int rb, int row_bytes) { return 16 * rb * (row_bytes + kRankRowPad); }
 
 struct RankManyArgs {
     const void* corpus;       // [n_pad x ld] storage dtype
     int64_t n;                // real rows
-    int ld;                   // elements per row = d (384, 512, 768 or 1024)
+    int ld;                   // elements per row = d (rank_many_served: a multiple of 64)
     const void* q;            // prepared queries in the storage dtype, [256 x ld]
     int nq;                   // queries of this block (<= 256)
     // counting pass
@@ -60,8 +55,12 @@ struct RankManyArgs {
     float* gscore;            // [nslots]
 };
 
-template <bool F32, int RB, bool GATHER>
+// TAIL: a bf16 width with d % 128 == 64, whose k-steps end in a group of two (rank_tail, rank_plan.h).  A template flag and
+// not a test of `steps` alone: the test in every group costs the widths without a tail 57 VGPRs and 8 % of the pass
+// (3M x 768 bf16, 256 queries: 3.37 against 3.13 ms); with TAIL = false their kernels are the ones they always had.
+template <bool F32, int RB, bool GATHER, bool TAIL = false>
 __global__ void __launch_bounds__(kRankThreads) rank_many_kernel(RankManyArgs a) {
+    static_assert(!(F32 && TAIL), "fp32: d / 16 steps, a multiple of 4");
     extern __shared__ __attribute__((aligned(16))) unsigned char srows[];
     constexpr int kRows = 16 * RB;
     constexpr int kElem = F32 ? 4 : 2;
@@ -70,8 +69,7 @@ __global__ void __launch_bounds__(kRankThreads) rank_many_kernel(RankManyArgs a)
     const int r16 = lane & 15, kq = lane >> 4;
     const int row_bytes = a.ld * kElem;
     const int pitch = row_bytes + kRankRowPad;
-    const int steps = a.ld / kStepElems;                          // a multiple of 4 at every served width (rank_many.hip admits 384 / 512 / 768 / 1024 only;
-                                                                  // a width with steps % 4 == 2 needs the tail group of kernels_mfma_anyd.h)
+    const int steps = a.ld / kStepElems;                          // even; fp32: a multiple of 4
     const int nblocks = (a.nq + 15) / 16;
 
     // this workgroup's tiles
@@ -143,11 +141,15 @@ __global__ void __launch_bounds__(kRankThreads) rank_many_kernel(RankManyArgs a)
 #pragma unroll
                 for (int g4 = 0; g4 < kRankSeg; g4 += 4) {
                     if (s0 + g4 < steps) {
+                        // TAIL (bf16, d % 128 == 64): the last group has two steps (as kernels_mfma_anyd_pass.inc).  Nothing past the
+                        // row end is read - behind the tile's last row lies the end of the LDS allocation - or multiplied
+                        const bool full = !TAIL || s0 + g4 + 4 <= steps;
                         uint4 av[4][RB];
 #pragma unroll
                         for (int s = 0; s < 4; ++s)
 #pragma unroll
-                            for (int rb = 0; rb < RB; ++rb) av[s][rb] = *(const uint4*)(arow[rb] + (s0 + g4 + s) * 64);
+                            for (int rb = 0; rb < RB; ++rb)
+                                if (s < 2 || full) av[s][rb] = *(const uint4*)(arow[rb] + (s0 + g4 + s) * 64);
 #pragma unroll
                         for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -159,9 +161,10 @@ __global__ void __launch_bounds__(kRankThreads) rank_many_kernel(RankManyArgs a)
                                     for (int i = 0; i < 4; ++i)
                                         acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i], bf[i], acc[rb], 0, 0, 0);
                                 } else {
-                                    acc[rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(reinterpret_cast<const bf16x8&>(av[s][rb]),
-                                                                                      reinterpret_cast<const bf16x8&>(bv[g4 + s]),
-                                                                                      acc[rb], 0, 0, 0);
+                                    if (s < 2 || full)
+                                        acc[rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(reinterpret_cast<const bf16x8&>(av[s][rb]),
+                                                                                          reinterpret_cast<const bf16x8&>(bv[g4 + s]),
+                                                                                          acc[rb], 0, 0, 0);
                                 }
                             }
                     }

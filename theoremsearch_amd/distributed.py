@@ -413,6 +413,49 @@ class ShardedSearcher:
         out[~known] = -1
         return out
 
+    def rank_many(self, queries: np.ndarray, targets, local_rank_many=None, local_count_above_many=None):
+        """Ranks of several global rows per query over the WHOLE sharded corpus: ``(ranks, scores)`` as
+        `TheoremIndex.rank_many` returns them (lists of per-query arrays aligned with ``targets``; -1 / NaN = no such row).
+        `rank_of`'s protocol on the flattened target list: this shard ranks the targets it owns (`TheoremIndex.rank_many`),
+        one all-reduce (max) makes the scores known to every rank, this shard counts its rows that rank before each known
+        target it does not own (`count_above_many`), one all-reduce (sum) adds the counts.  The shards share storage type
+        and width, so each scores its rows by the owner's arithmetic.  The two callables default to this rank's index;
+        they can be injected for CPU tests."""
+        import torch
+        ix = getattr(self, "index", None)
+        local_rank_many = local_rank_many or (lambda q, t: ix.rank_many(q, t))
+        local_count_above_many = local_count_above_many or (lambda q, s, t: ix.count_above_many(q, s, t))
+        lists = [np.asarray(t, dtype=np.int64).reshape(-1) for t in targets]
+        ranks, scores = local_rank_many(queries, lists)
+        if self.world == 1:
+            return ranks, scores
+        offsets = np.zeros(len(lists) + 1, dtype=np.int64)
+        np.cumsum([t.shape[0] for t in lists], out=offsets[1:])
+        split = lambda flat: [flat[offsets[i]:offsets[i + 1]] for i in range(len(lists))]
+        if offsets[-1] == 0:                    # every rank holds the same lists: none of them has anything to exchange
+            return split(np.zeros(0, np.int64)), split(np.zeros(0, np.float32))
+        rows = np.concatenate(lists)
+        local_r = np.concatenate([np.asarray(r, dtype=np.int64).reshape(-1) for r in ranks])
+        local_s = np.concatenate([np.asarray(s, dtype=np.float32).reshape(-1) for s in scores])
+        dev = "cuda" if self.dist.get_backend(self.group) == "nccl" else "cpu"
+        mine = local_r >= 0
+        sc = torch.from_numpy(np.where(mine, local_s, -np.inf).astype(np.float32)).to(dev)
+        self.dist.all_reduce(sc, op=self.dist.ReduceOp.MAX, group=self.group)  # exactly one shard owns each row
+        sc_host = sc.cpu().numpy()
+        known = np.isfinite(sc_host)
+        counts = np.where(mine, local_r, 0).astype(np.int64)
+        others = known & ~mine
+        if others.any():
+            pick = split(others)
+            c = local_count_above_many(queries, [s[p] for s, p in zip(split(sc_host), pick)],
+                                       [r[p] for r, p in zip(split(rows), pick)])
+            counts[others] = np.concatenate([np.asarray(x, dtype=np.int64).reshape(-1) for x in c])
+        total = torch.from_numpy(counts).to(dev)
+        self.dist.all_reduce(total, op=self.dist.ReduceOp.SUM, group=self.group)
+        out = total.cpu().numpy()
+        out[~known] = -1
+        return split(out), split(np.where(known, sc_host, np.nan).astype(np.float32))
+
 
 class Shards:
     """One process, all GPUs of the node: ``ts_shards_*`` (``ncclCommInitAll``, one stream per device, the exchange

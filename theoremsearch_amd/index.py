@@ -331,8 +331,19 @@ class TheoremIndex:
                                         _ffi.as_ptr(ranks), _ffi.as_ptr(scores), None))
         return ranks, scores
 
+    @staticmethod
+    def _ragged(lists, dtype, nq):
+        """Per-query sequences -> (offsets int64 [nq + 1], their concatenation as one contiguous array of ``dtype``)."""
+        lists = [np.asarray(t, dtype=dtype).reshape(-1) for t in lists]
+        if len(lists) != nq:
+            raise ValueError(f"{len(lists)} target lists for {nq} queries")
+        offsets = np.zeros(nq + 1, dtype=np.int64)
+        np.cumsum([t.shape[0] for t in lists], out=offsets[1:])
+        return offsets, np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, dtype=dtype))
+
     def rank_many(self, queries, targets):
-        """Ranks of several rows per query in one matrix pass per block of 256 queries: ``targets`` holds one integer
+        """Ranks of several rows per query in one matrix pass per block of 256 queries (every width that is a multiple of 64
+        from 128 up to a 4,096-byte row; other widths: one `rank_of` pass per target column): ``targets`` holds one integer
         sequence per query (ragged, possibly empty, repeats allowed).  Returns ``(ranks, scores)``, lists of per-query
         int64 / float32 arrays aligned with ``targets``; ``-1`` / NaN for rows not in the index or with a NaN score.
         The ranks are consistent with the returned scores (score descending, row ascending); where the fp64 truth cannot
@@ -340,18 +351,30 @@ class TheoremIndex:
         q = _host_rows(queries)
         if q.shape[1] != self.d:
             raise ValueError(f"queries have d={q.shape[1]}, index has d={self.d}")
-        lists = [np.asarray(t, dtype=np.int64).reshape(-1) for t in targets]
-        if len(lists) != q.shape[0]:
-            raise ValueError(f"{len(lists)} target lists for {q.shape[0]} queries")
-        offsets = np.zeros(q.shape[0] + 1, dtype=np.int64)
-        np.cumsum([t.shape[0] for t in lists], out=offsets[1:])
-        rows = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, dtype=np.int64))
+        offsets, rows = self._ragged(targets, np.int64, q.shape[0])
         ranks = np.empty(max(1, rows.shape[0]), dtype=np.int64)
         scores = np.empty(max(1, rows.shape[0]), dtype=np.float32)
         _ffi.check(self._lib.ts_rank_many(self._h, _ffi.as_ptr(q), _ffi.np_dtype_code(q), 0, q.shape[0], _ffi.as_ptr(offsets),
                                           _ffi.as_ptr(rows), _ffi.as_ptr(ranks), _ffi.as_ptr(scores), None))
         return ([ranks[offsets[i]:offsets[i + 1]] for i in range(q.shape[0])],
                 [scores[offsets[i]:offsets[i + 1]] for i in range(q.shape[0])])
+
+    def count_above_many(self, queries, target_scores, target_ids):
+        """The many-targets form of `count_above`: ``target_scores`` / ``target_ids`` hold one sequence per query (ragged,
+        possibly empty, repeats allowed) of documents given by score and GLOBAL id, wherever they live.  Returns a list of
+        per-query int64 arrays: the rows of this index that rank before each document (``-1`` for a NaN score).  Summed
+        over the shards of a corpus this is the document's rank, given the score `rank_many` returned on its own shard."""
+        q = _host_rows(queries)
+        if q.shape[1] != self.d:
+            raise ValueError(f"queries have d={q.shape[1]}, index has d={self.d}")
+        offsets, sc = self._ragged(target_scores, np.float32, q.shape[0])
+        id_offsets, ids = self._ragged(target_ids, np.int64, q.shape[0])
+        if not np.array_equal(offsets, id_offsets):
+            raise ValueError("one id per target score")
+        out = np.empty(max(1, ids.shape[0]), dtype=np.int64)
+        _ffi.check(self._lib.ts_count_above_many(self._h, _ffi.as_ptr(q), _ffi.np_dtype_code(q), 0, q.shape[0], _ffi.as_ptr(offsets),
+                                                 _ffi.as_ptr(sc), _ffi.as_ptr(ids), _ffi.as_ptr(out), None))
+        return [out[offsets[i]:offsets[i + 1]] for i in range(q.shape[0])]
 
     def count_above(self, queries, target_scores, target_ids) -> np.ndarray:
         """Rows of this index that rank before a document with the given score and GLOBAL id (it may live on another
