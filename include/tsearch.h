@@ -282,6 +282,82 @@ int ts_search_biased_ex(ts_index *ix, const void *queries, int q_dtype, int q_on
                         float *out_scores, float *out_sims, int64_t *out_idx, int out_on_device, void *stream, int algo,
                         ts_search_stats *stats);
 
+/* ---- metadata filters evaluated on the device -----------------------------------------------------
+ * The WHERE clause in front of ORDER BY <#> LIMIT k (streamlit_app.py:175-283) and the sidebar predicates of the showcase app
+ * (app_showcase_model.py:102-121), evaluated to the row bitmask of ts_search_filtered by one kernel over the rows' metadata
+ * held as columns in HBM, instead of by a host predicate per row.
+ *
+ * ts_meta: up to 32 columns over n rows of one device.  A scalar column is int32 per row (a dictionary code, a year, a count,
+ * a 0 / 1 flag); TS_META_NULL is SQL NULL.  ts_meta_set_column uploads rows [row0, row0 + nrows) from host memory and may be
+ * called again for any range (the upsert by slogan_id); rows of a scalar column that were never uploaded are NULL.  A list
+ * column (the authors) is set whole, as CSR: offsets[n + 1] ascending from 0, codes[offsets[n]] all >= 0; a NULL list is
+ * stored as an empty one.  A column keeps the kind of its first upload.  n is fixed: a table does not grow with
+ * ts_index_append, and a search whose index has another n is refused.
+ *
+ * A program is a list of at most 32 atoms in at most 16 groups (distinct values of `group`, any integers):
+ *   - a row passes when every group holds; a group holds when at least one of its atoms is true; the empty program
+ *     (natoms = 0) allows every row;
+ *   - TS_ATOM_RANGE: lo <= v <= hi;  TS_ATOM_IN: bit v of `set` (v < 0 or v >= set_bits: not in the set);  `negate` inverts
+ *     either - but an atom whose value is TS_META_NULL is not true, negated or not.  That is SQL's three-valued logic as a
+ *     WHERE clause sees it (a comparison with NULL is not true, and neither is its NOT);
+ *   - TS_ATOM_IS_NULL: v == TS_META_NULL; with `negate`, v != TS_META_NULL;
+ *   - TS_ATOM_ANY_IN (list columns only): some code of the row's list has its bit in `set`; false on an empty list; `negate`
+ *     is refused.
+ * TS_ERR_INVALID with a message for every malformed program: more than 32 atoms or 16 groups, a kind out of range, a column
+ * out of range, never set or of the other kind (scalar atoms on a list column, ANY_IN on a scalar one), lo > hi, negate
+ * outside 0 / 1, a missing set (NULL with set_bits > 0) or set_bits outside [0, INT32_MAX].  Sets are host bitsets (uint32 words, bit c & 31 of word
+ * c >> 5 = code c, ceil(set_bits / 32) words), copied by the call.
+ *
+ * ts_meta_eval runs the program over all n rows on `stream` (hipStream_t as void*; NULL = the legacy null stream) and waits
+ * for the count: *out owns a device bitmask in the layout of ts_search_filtered - n bits, allocated in whole 256-row blocks,
+ * every bit past n zero - and knows how many rows it allows.  A row set is immutable (later ts_meta_set_column calls do not
+ * change it) and belongs to the device of its ts_meta.  There is no host evaluator. */
+typedef struct ts_meta ts_meta;
+typedef struct ts_rowset ts_rowset;
+
+#define TS_META_NULL INT32_MIN
+#define TS_META_MAX_COLS 32
+#define TS_META_MAX_ATOMS 32
+#define TS_META_MAX_GROUPS 16
+
+int ts_meta_create(int device, int64_t n, int32_t ncols, ts_meta **out);
+int ts_meta_destroy(ts_meta *m);
+int ts_meta_set_column(ts_meta *m, int32_t col, const int32_t *values, int64_t row0, int64_t nrows);
+int ts_meta_set_lists(ts_meta *m, int32_t col, const int64_t *offsets, const int32_t *codes);
+
+#define TS_ATOM_RANGE 0
+#define TS_ATOM_IN 1
+#define TS_ATOM_ANY_IN 2
+#define TS_ATOM_IS_NULL 3
+typedef struct ts_atom {
+    int32_t kind, col, lo, hi;
+    int32_t negate;      /* 0 / 1 */
+    int32_t group;       /* atoms of one group are OR-ed, the groups are AND-ed */
+    const uint32_t *set; /* host bitset over the column's codes (IN, ANY_IN) */
+    int64_t set_bits;
+} ts_atom;
+
+int ts_meta_eval(ts_meta *m, const ts_atom *atoms, int32_t natoms, ts_rowset **out, void *stream);
+/* n, the rows allowed and the device address of the mask (each may be NULL) */
+int ts_rowset_info(const ts_rowset *r, int64_t *n, int64_t *allowed, void **device_mask);
+/* the mask to host memory: ceil(n / 32) words */
+int ts_rowset_download(ts_rowset *r, uint32_t *host_words);
+int ts_rowset_destroy(ts_rowset *r);
+
+/* ts_search_filtered_ex / ts_search_biased_ex with the mask and its count taken from a row set.  Because the count is known,
+ * a device mask is decided as a counted host mask is: a batch the matrix path takes runs there when the row set allows at
+ * least a tenth of the rows (TS_ALGO_MFMA is refused with TS_ERR_UNSUPPORTED when it is sparser), everything else on the
+ * scan.  (A bare device mask handed to ts_search_filtered_ex keeps its rule: the scan.)  TS_ERR_INVALID when the row set has
+ * another n than the index or lives on another device; on a subset index the mask is over the subset's own rows, as for
+ * ts_search_filtered.  The row set must stay alive until the enqueued work has run. */
+int ts_search_rowset(ts_index *ix, const void *queries, int q_dtype, int q_on_device, int32_t nq, int32_t k,
+                     const ts_rowset *rows, float *out_scores, int64_t *out_idx, int out_on_device, void *stream,
+                     int algo, ts_search_stats *stats);
+int ts_search_biased_rowset(ts_index *ix, const void *queries, int q_dtype, int q_on_device, int32_t nq, int32_t k,
+                            const float *bias, int bias_on_device, float weight, const ts_rowset *rows,
+                            float *out_scores, float *out_sims, int64_t *out_idx, int out_on_device, void *stream,
+                            int algo, ts_search_stats *stats);
+
 /* Rank of one given row per query in the canonical order of that query's scores over the whole index (0 = best):
  * the number of rows whose (score, -row) beats the target's.  One streaming pass that counts; replaces ranking the
  * full [nq x N] matrix and looking the relevant document up - np.argsort(-sim_matrix) followed by the position of

@@ -36,6 +36,12 @@ class SearchStats(C.Structure):
                 ("screened", C.c_int32), ("candidates", C.c_int64)]
 
 
+class Atom(C.Structure):
+    """ts_atom: one atom of a metadata filter program (``set``: host uint32 words, copied by ts_meta_eval)."""
+    _fields_ = [("kind", C.c_int32), ("col", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32), ("negate", C.c_int32),
+                ("group", C.c_int32), ("set", C.c_void_p), ("set_bits", C.c_int64)]
+
+
 # name -> (restype, argtypes); kept in one table so tests can check it against the header
 _SIGNATURES = {
     "ts_version": (C.c_int, []),
@@ -82,6 +88,19 @@ _SIGNATURES = {
     "ts_search_biased_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_int, C.c_float,
                                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                       C.POINTER(SearchStats)]),
+    "ts_meta_create": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]),
+    "ts_meta_destroy": (C.c_int, [C.c_void_p]),
+    "ts_meta_set_column": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64]),
+    "ts_meta_set_lists": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ts_meta_eval": (C.c_int, [C.c_void_p, C.POINTER(Atom), C.c_int32, C.POINTER(C.c_void_p), C.c_void_p]),
+    "ts_rowset_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_void_p)]),
+    "ts_rowset_download": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ts_rowset_destroy": (C.c_int, [C.c_void_p]),
+    "ts_search_rowset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(SearchStats)]),
+    "ts_search_biased_rowset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_int,
+                                          C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                          C.POINTER(SearchStats)]),
     "ts_rank_of": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                              C.c_void_p]),
     "ts_count_above": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

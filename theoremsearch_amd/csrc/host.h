@@ -25,6 +25,7 @@
 #include "anyd_plan.h"
 #include "bias_plan.h"
 #include "encoder_plan.h"
+#include "meta_plan.h"
 #include "dev_array.h"
 
 using namespace ts;
@@ -204,7 +205,7 @@ struct ts_index : IndexQueue {
     DevArray<void> rank_buf;                                 // ts_rank_of: targets | counts | target scores, one query block
     DevArray<void> rank_many_buf;                            // ts_rank_many: slots | keys | counts of one pass of one query block
     const u32* active_mask = nullptr;                        // bitmask of the search in progress (under `mu`)
-    int64_t active_allowed = 0;                              // rows that bitmask allows (host masks: counted; else n)
+    int64_t active_allowed = 0;                              // rows that bitmask allows (host masks: counted; a row set's: known; else n)
     Knobs knobs;                                             // env at creation, then ts_index_set_option
     hipStream_t last_stream = nullptr;                       // stream the previous call ran on: compared, never used (it may be gone)
     DevArray<int64_t> part;     DevArray<unsigned> wg_ticks;     // full pass of the 16x16 kernel: tile boundaries per workgroup, their times
@@ -231,6 +232,30 @@ inline void screen_touch(ts_index* ix, int64_t lo, int64_t hi) {
     if (ix->scr_hi <= ix->scr_lo) { ix->scr_lo = lo; ix->scr_hi = hi; }
     else { ix->scr_lo = std::min(ix->scr_lo, lo); ix->scr_hi = std::max(ix->scr_hi, hi); }
 }
+
+// The rows' metadata as columns (meta.hip).  A scalar column: `values` [n]; a list column: `offsets` [n + 1] and `values`
+// [offsets[n]], its codes.  `sets` and `allowed` are the scratch of one ts_meta_eval (under `mu`; the call waits for its
+// count, so nothing of it is in flight when the next one starts).
+struct ts_meta {
+    int device = 0;
+    int64_t n = 0;
+    int ncols = 0;
+    int cu_count = 256;
+    std::mutex mu;
+    int kind[TS_META_MAX_COLS] = {};                         // MetaColKind
+    DevArray<int32_t> values[TS_META_MAX_COLS];
+    DevArray<int64_t> offsets[TS_META_MAX_COLS];
+    DevArray<u32> sets;
+    DevArray<u64> allowed;
+};
+
+// A device row bitmask in the layout of ts_search_filtered, allocated in whole 256-row blocks (bits past n are zero), and
+// the number of rows it allows
+struct ts_rowset {
+    int device = 0;
+    int64_t n = 0, allowed = 0;
+    DevArray<u32> mask;
+};
 
 struct ts_timer {
     int device = 0;

@@ -167,7 +167,9 @@ struct AlgoInputs {
     int scan_max_queries;       // TS_SCAN_MAX_QUERIES
     bool bias, subset;          // a biased search; a subset index
     bool mask, mask_on_device;
-    int64_t allowed;            // rows a host mask allows (count_allowed_rows), read only where mask_wants_count()
+    int64_t allowed;            // rows the mask allows: a host mask's (count_allowed_rows), read only where mask_wants_count(),
+                                //   or a device mask's where allowed_known
+    bool allowed_known;         // a device mask that comes with its count (a row set, meta_plan.h); false: every decision as before
 };
 struct AlgoChoice {
     int algo;                   // TS_ALGO_SCAN or TS_ALGO_MFMA
@@ -180,6 +182,11 @@ inline bool mfma_batch(const AlgoInputs& in) {
 // a host mask in front of a batch the matrix path would take: its density decides, so its bits are counted
 inline bool mask_wants_count(const AlgoInputs& in) {
     return in.mask && !in.mask_on_device && !in.bias && in.algo != TS_ALGO_SCAN && mfma_batch(in);
+}
+// ... or a device mask whose count came with it (a row set): the same batches, nothing to count
+inline bool mask_count_decides(const AlgoInputs& in) {
+    return mask_wants_count(in) ||
+           (in.mask && in.mask_on_device && in.allowed_known && !in.bias && in.algo != TS_ALGO_SCAN && mfma_batch(in));
 }
 
 inline AlgoChoice choose_algo(const AlgoInputs& in) {
@@ -198,8 +205,9 @@ inline AlgoChoice choose_algo(const AlgoInputs& in) {
         // Batches behind a host mask that keeps at least a tenth of the rows run the MFMA path: the bit is tested in its
         // append path and the threshold estimates are made for the allowed rows (the sample sees only those).  Sparser
         // masks leave the sample too few allowed rows to estimate from; device masks would need a count + sync first:
-        // both go through the scan kernel, 4 queries per pass (or through a subset index).
-        const bool dense_host_mask = mask_wants_count(in) && in.allowed * 10 >= in.n;
+        // both go through the scan kernel, 4 queries per pass (or through a subset index).  A device mask that comes with
+        // its count (allowed_known: a row set) is decided as a counted host mask is.
+        const bool dense_host_mask = mask_count_decides(in) && in.allowed * 10 >= in.n;
         if (algo == TS_ALGO_MFMA && !dense_host_mask)
             return {0, "the MFMA path serves host masks that keep at least a tenth of the rows, for more than 4 queries"};
         algo = dense_host_mask ? TS_ALGO_MFMA : TS_ALGO_SCAN;

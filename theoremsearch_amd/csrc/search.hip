@@ -243,9 +243,10 @@ static int install_mask(ts_index* ix, const uint32_t* row_mask, int mask_on_devi
     return TS_OK;
 }
 
-// scan or matrix path (scan_plan.h: choose_algo); a host mask whose density decides is counted here
+// scan or matrix path (scan_plan.h: choose_algo); a host mask whose density decides is counted here.  known_allowed >= 0: the
+// rows a device mask allows (a row set's count)
 static int search_choose(ts_index* ix, int algo, int nq, int k, const BiasSpec* bias, const uint32_t* row_mask, int mask_on_device,
-                         int* use) {
+                         int64_t known_allowed, int* use) {
     AlgoInputs in;
     in.algo = algo;
     in.mfma_ok = mfma_index(ix) && ix->n >= 1;
@@ -264,6 +265,8 @@ static int search_choose(ts_index* ix, int algo, int nq, int k, const BiasSpec* 
     in.mask = row_mask != nullptr;
     in.mask_on_device = mask_on_device != 0;
     in.allowed = 0;
+    in.allowed_known = row_mask && mask_on_device && known_allowed >= 0;
+    if (in.allowed_known) ix->active_allowed = in.allowed = known_allowed;
     if (bias && bias->ex) {
         // ts_search_biased_ex decides with its own rule (bias_plan.h): the biased general-width pass serves the hand-laid
         // widths too, and its AUTO limit is its own
@@ -377,7 +380,7 @@ static int search_read_back(ts_index* ix, int use, int block, int nq, int k, con
 static int search_impl(ts_index* ix, const void* queries, int q_dtype, int q_on_device, int32_t nq, int32_t k,
                        float* out_scores, int64_t* out_idx, int out_on_device, void* stream, int algo,
                        ts_search_stats* stats, const uint32_t* row_mask = nullptr, int mask_on_device = 0,
-                       const BiasSpec* bias = nullptr) {
+                       const BiasSpec* bias = nullptr, int64_t known_allowed = -1) {
     if (stats) memset(stats, 0, sizeof(*stats));
     TS_TRY(search_validate(ix, queries, q_dtype, nq, k, out_scores, out_idx, algo));
     if (nq == 0) return TS_OK;
@@ -394,7 +397,7 @@ static int search_impl(ts_index* ix, const void* queries, int q_dtype, int q_on_
     if (bias) TS_TRY(install_bias(ix, *bias, st));
     if (row_mask) TS_TRY(install_mask(ix, row_mask, mask_on_device, st));
     int use = TS_ALGO_SCAN;
-    TS_TRY(search_choose(ix, algo, nq, k, bias, row_mask, mask_on_device, &use));
+    TS_TRY(search_choose(ix, algo, nq, k, bias, row_mask, mask_on_device, known_allowed, &use));
     if (stats) stats->algo = use;
 
     float* dscores = out_scores;
@@ -466,6 +469,39 @@ extern "C" int ts_search_biased_ex(ts_index* ix, const void* queries, int q_dtyp
     b.ex = true;
     return search_impl(ix, queries, q_dtype, q_on_device, nq, k, out_scores, out_idx, out_on_device, stream, algo, stats, row_mask,
                        mask_on_device, &b);
+}
+
+// the mask and its count from a row set (meta.hip): one of this index's shape, on its device
+static int rowset_check(const ts_index* ix, const ts_rowset* rows) {
+    if (!ix || !rows) return fail(TS_ERR_INVALID, "NULL argument");
+    if (rows->n != ix->n) return fail(TS_ERR_INVALID, "the row set has %lld rows, the index %lld", (long long)rows->n, (long long)ix->n);
+    if (rows->device != ix->device) return fail(TS_ERR_INVALID, "the row set lives on device %d, the index on device %d", rows->device, ix->device);
+    return TS_OK;
+}
+
+extern "C" int ts_search_rowset(ts_index* ix, const void* queries, int q_dtype, int q_on_device, int32_t nq, int32_t k,
+                                const ts_rowset* rows, float* out_scores, int64_t* out_idx, int out_on_device, void* stream, int algo,
+                                ts_search_stats* stats) {
+    TS_TRY(rowset_check(ix, rows));
+    return search_impl(ix, queries, q_dtype, q_on_device, nq, k, out_scores, out_idx, out_on_device, stream, algo, stats, rows->mask, 1,
+                       nullptr, rows->allowed);
+}
+
+extern "C" int ts_search_biased_rowset(ts_index* ix, const void* queries, int q_dtype, int q_on_device, int32_t nq, int32_t k,
+                                       const float* bias, int bias_on_device, float weight, const ts_rowset* rows, float* out_scores,
+                                       float* out_sims, int64_t* out_idx, int out_on_device, void* stream, int algo,
+                                       ts_search_stats* stats) {
+    if (!bias) return fail(TS_ERR_INVALID, "bias is NULL");
+    if (!(weight == weight) || std::isinf(weight)) return fail(TS_ERR_INVALID, "weight must be finite");
+    TS_TRY(rowset_check(ix, rows));
+    BiasSpec b;
+    b.bias = bias;
+    b.on_device = bias_on_device;
+    b.weight = weight;
+    b.out_sims = out_sims;
+    b.ex = true;
+    return search_impl(ix, queries, q_dtype, q_on_device, nq, k, out_scores, out_idx, out_on_device, stream, algo, stats, rows->mask, 1,
+                       &b, rows->allowed);
 }
 
 template <int DT, int CH, int G>

@@ -7,6 +7,10 @@ to one bit per row (`filter_mask`), and `TheoremIndex.search(..., mask=)` return
 that pass - identical to the reference's answer whenever its pool held ``top_k`` matches, and complete
 when it did not.  The SQL form (streamlit_app.py:175-243 builds the same predicates as a WHERE clause in
 front of ``ORDER BY <#> LIMIT k``) maps to the same mask.
+
+`filter_mask` and `sql_filter_mask` call a Python predicate per row: the definition, and fine for a few thousand rows.
+For a real table, `metadata.MetaTable` holds the same metadata as columns on the device and evaluates the same filter
+states there (``table.eval(filters)``); its `RowSet` goes wherever ``mask=`` takes a bool array.
 """
 from __future__ import annotations
 
@@ -57,9 +61,10 @@ def filtered_index(index, theorems_data: Sequence[Mapping], filters: Mapping):
     return index.subset(filter_mask(theorems_data, filters))
 
 
-def search_filtered(index, query_emb, theorems_data: Sequence[Mapping], filters: Mapping, mask: np.ndarray | None = None):
+def search_filtered(index, query_emb, theorems_data: Sequence[Mapping], filters: Mapping, mask=None):
     """The filtered result list of the showcase app: ``[{"info": item, "similarity": cos}]``, best first,
-    at most ``filters["top_k"]`` entries, exact over ALL rows that pass (not only a top-200 pool)."""
+    at most ``filters["top_k"]`` entries, exact over ALL rows that pass (not only a top-200 pool).  ``mask``: a ready-made
+    bool array or a `metadata.RowSet` for this filter state."""
     if mask is None:
         mask = filter_mask(theorems_data, filters)
     k = max(1, min(int(filters["top_k"]), 256, len(theorems_data)))

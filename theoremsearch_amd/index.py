@@ -18,6 +18,7 @@ import numpy as np
 
 from . import _ffi
 from ._ffi import TS_ALGO_AUTO, TS_ALGO_MFMA, TS_ALGO_SCAN, TS_BF16, TS_F32, TS_METRIC_COS, TS_METRIC_IP
+from .metadata import RowSet
 
 _DTYPES = {"f32": TS_F32, "fp32": TS_F32, "float32": TS_F32, "bf16": TS_BF16, "bfloat16": TS_BF16}
 _METRICS = {"ip": TS_METRIC_IP, "dot": TS_METRIC_IP, "cos": TS_METRIC_COS, "cosine": TS_METRIC_COS}
@@ -201,7 +202,9 @@ class TheoremIndex:
     def search(self, queries, k: int, algo: str = "auto", return_stats: bool = False, mask=None):
         """Exact top-k.  Returns ``(scores [nq x k] float32, indices [nq x k] int64)`` ordered by
         score descending then index ascending; padding is ``(-inf, -1)``.  ``mask`` (bool per row)
-        restricts the search to the rows where it is true (metadata filters): the k best allowed rows."""
+        restricts the search to the rows where it is true (metadata filters): the k best allowed rows.
+        ``mask`` may also be a `metadata.RowSet` (a mask evaluated on the device, with its count): the same
+        answer, and a query batch behind it runs on the matrix path when it allows a tenth of the rows."""
         q = _host_rows(queries)
         if q.shape[1] != self.d:
             raise ValueError(f"queries have d={q.shape[1]}, index has d={self.d}")
@@ -218,17 +221,22 @@ class TheoremIndex:
                 idx[idx >= 0] += self.row_offset
             return (scores, idx, {"algo": 0, "levels": 0, "fallback_queries": 0, "candidates": 0, "screened": 0}) if return_stats else (scores, idx)
         if mask is not None:
-            m = np.asarray(mask, dtype=bool).reshape(-1)
-            if m.shape[0] != self.n:
-                raise ValueError(f"mask has {m.shape[0]} entries, index has {self.n} rows")
-            bits = np.packbits(m, bitorder="little")
-            words = np.zeros((self.n + 31) // 32 * 4, dtype=np.uint8)
-            words[: bits.shape[0]] = bits
-            words = words.view(np.uint32)
             stats = _ffi.SearchStats()
-            _ffi.check(self._lib.ts_search_filtered_ex(self._h, _ffi.as_ptr(q), _ffi.np_dtype_code(q), 0, nq, k,
-                                                       _ffi.as_ptr(words), 0, _ffi.as_ptr(scores), _ffi.as_ptr(idx), 0, None,
-                                                       _ALGOS[algo], C.byref(stats)))
+            if isinstance(mask, RowSet):
+                _ffi.check(self._lib.ts_search_rowset(self._h, _ffi.as_ptr(q), _ffi.np_dtype_code(q), 0, nq, k, mask.handle,
+                                                      _ffi.as_ptr(scores), _ffi.as_ptr(idx), 0, None, _ALGOS[algo],
+                                                      C.byref(stats)))
+            else:
+                m = np.asarray(mask, dtype=bool).reshape(-1)
+                if m.shape[0] != self.n:
+                    raise ValueError(f"mask has {m.shape[0]} entries, index has {self.n} rows")
+                bits = np.packbits(m, bitorder="little")
+                words = np.zeros((self.n + 31) // 32 * 4, dtype=np.uint8)
+                words[: bits.shape[0]] = bits
+                words = words.view(np.uint32)
+                _ffi.check(self._lib.ts_search_filtered_ex(self._h, _ffi.as_ptr(q), _ffi.np_dtype_code(q), 0, nq, k,
+                                                           _ffi.as_ptr(words), 0, _ffi.as_ptr(scores), _ffi.as_ptr(idx), 0, None,
+                                                           _ALGOS[algo], C.byref(stats)))
             if return_stats:
                 return scores, idx, {"algo": stats.algo, "levels": stats.levels,
                                      "fallback_queries": stats.fallback_queries, "candidates": stats.candidates,
@@ -245,13 +253,20 @@ class TheoremIndex:
         return scores, idx
 
     def search_device(self, q_ptr: int, q_dtype: str, nq: int, k: int, out_scores_ptr: int, out_idx_ptr: int,
-                      stream: int = 0, algo: str = "auto", mask_ptr: int = 0) -> None:
+                      stream: int = 0, algo: str = "auto", mask_ptr: int = 0, rowset: Optional[RowSet] = None) -> None:
         """Asynchronous search on device buffers (queries [nq x d] dense; outputs [nq x k] f32 / i64),
         enqueued on ``stream`` (0 = the index's own stream).  ``mask_ptr``: device uint32 bitmask
-        (ceil(n / 32) words) restricting the rows, see `search`.
+        (ceil(n / 32) words) restricting the rows, see `search` - a bare device mask runs on the scan;
+        ``rowset``: a `metadata.RowSet` instead, whose known count lets ``algo`` decide as for a host mask (keep it
+        open until the enqueued work has run).
         Queries that already have the form the matrix kernels multiply (the index's dtype, an inner-product index, a
         whole launch's worth: 64 / 128 / 192 / 256 of them) are read in place - keep them unchanged until the enqueued work
         has run (work enqueued later on the same stream is ordered behind it anyway)."""
+        if rowset is not None:
+            _ffi.check(self._lib.ts_search_rowset(self._h, C.c_void_p(q_ptr), _DTYPES[q_dtype], 1, int(nq), int(k), rowset.handle,
+                                                  C.c_void_p(out_scores_ptr), C.c_void_p(out_idx_ptr), 1, C.c_void_p(stream),
+                                                  _ALGOS[algo], None))
+            return
         if mask_ptr:
             _ffi.check(self._lib.ts_search_filtered(self._h, C.c_void_p(q_ptr), _DTYPES[q_dtype], 1, int(nq), int(k),
                                                     C.c_void_p(mask_ptr), 1, C.c_void_p(out_scores_ptr),
@@ -268,7 +283,8 @@ class TheoremIndex:
         Returns ``(weighted scores, raw similarities, indices)``, each ``[nq x k]``.
         ``algo=None`` is ``ts_search_biased`` (the scan); ``"scan" | "mfma" | "auto"`` go through ``ts_search_biased_ex``:
         ``"mfma"`` is the batched matrix search (one corpus pass per 256 queries; refused where it is not served),
-        ``"auto"`` takes it for a batch of more than 4 queries (an fp32 index: more than 8).  ``return_stats`` appends the call's counters."""
+        ``"auto"`` takes it for a batch of more than 4 queries (an fp32 index: more than 8).  ``return_stats`` appends the call's counters.
+        ``mask`` may be a `metadata.RowSet`: always ``ts_search_biased_rowset`` (``algo=None``: the scan, the same kernel)."""
         q = _host_rows(queries)
         if q.shape[1] != self.d:
             raise ValueError(f"queries have d={q.shape[1]}, index has d={self.d}")
@@ -280,6 +296,15 @@ class TheoremIndex:
         sims = np.empty((nq, k), dtype=np.float32)
         idx = np.empty((nq, k), dtype=np.int64)
         words = None
+        if isinstance(mask, RowSet):
+            stats = _ffi.SearchStats()
+            _ffi.check(self._lib.ts_search_biased_rowset(self._h, _ffi.as_ptr(q), _ffi.np_dtype_code(q), 0, nq, k, _ffi.as_ptr(b), 0,
+                                                         float(weight), mask.handle, _ffi.as_ptr(scores), _ffi.as_ptr(sims),
+                                                         _ffi.as_ptr(idx), 0, None, _ALGOS[algo or "scan"], C.byref(stats)))
+            if return_stats:
+                return scores, sims, idx, {"algo": stats.algo, "levels": stats.levels, "fallback_queries": stats.fallback_queries,
+                                           "candidates": stats.candidates, "screened": stats.screened}
+            return scores, sims, idx
         if mask is not None:
             m = np.asarray(mask, dtype=bool).reshape(-1)
             if m.shape[0] != self.n:

@@ -88,7 +88,8 @@ def citation_bias(citations: Sequence[Optional[int]]) -> np.ndarray:
 def search(index: TheoremIndex, query_vec, top_k: int, citation_weight: float = 0.0,
            citations: Optional[Sequence[Optional[int]]] = None, mask=None, exact: bool = False, bias=None):
     """Returns a list of dicts ``{"row", "similarity", "score"}`` ordered like the SQL result.  ``mask`` (bool per row,
-    e.g. `filters.sql_filter_mask`) plays the WHERE clause: only those rows are ranked.
+    e.g. `filters.sql_filter_mask`, or a `metadata.RowSet` evaluated on the device: ``MetaTable.from_sql_rows(rows).eval(f)``)
+    plays the WHERE clause: only those rows are ranked.
     ``exact=False`` (default) is the reference's form: the ``max(50, 10 k)`` nearest rows re-ranked by the weighted score.
     ``exact=True`` ranks EVERY (allowed) row by the weighted score on the device (``ts_search_biased``): the same answer
     whenever the pool holds it, and the right one when a heavily cited theorem sits outside the pool; ``bias`` may carry
@@ -135,7 +136,8 @@ def search_batch(index: TheoremIndex, query_vecs, top_k: int, citation_weight: f
                  citations: Optional[Sequence[Optional[int]]] = None, bias=None, mask=None):
     """`search` with ``exact=True`` for many queries at once: every (allowed) row ranked by the weighted score, one corpus
     pass per 256 queries where the index has the biased matrix search (``ts_search_biased_ex`` on ``auto``), the scan
-    otherwise.  Returns one list per query, each shaped like the result of ``search(..., exact=True)``."""
+    otherwise.  Returns one list per query, each shaped like the result of ``search(..., exact=True)``.  ``mask``: bool per
+    row, or a `metadata.RowSet` - whose batch stays on the matrix pass (a row set knows its count)."""
     q = np.asarray(query_vecs, dtype=np.float32)
     q = q.reshape(1, -1) if q.ndim == 1 else q
     if citations is None and bias is None:
