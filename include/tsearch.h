@@ -519,6 +519,15 @@ int ts_attention_short(int device, const void *qkv, const int64_t *attention_mas
  * a causal sequence, a sequence whose mask is all zeros) comes back as zeros, in out and in pieces. */
 int ts_attention_float(int device, const void *qkv, const void *qkv_bias, const int64_t *attention_mask, int32_t batch, int32_t seq,
                        int32_t q_heads, int32_t kv_heads, int32_t head_dim, int causal, float scale, void *out, void *pieces, void *stream);
+/* The same operation as ts_attention_float - arguments, layouts, masks, bias, pieces - without its V^T-fits-LDS limit: V^T passes
+ * through two LDS buffers in chunks of 128 / 64 / 32 keys (head size 64 / 128 / 256) under a workgroup per (sequence, query head,
+ * 64 queries), and every (query tile, key tile) step is ts_attention_float's arithmetic in the same order: wherever both serve a
+ * shape, out and pieces are the same bits.  Serves head sizes 64 / 128 / 256 at any seq from 1 to 32,768 with
+ * batch * q_heads * ceil(seq / 64) <= 2^31 - 1 (TS_ERR_UNSUPPORTED otherwise).  A query row without a single allowed key (a
+ * padding token on the left of a causal sequence, a sequence whose mask is all zeros, a whole chunk of padding in front of it)
+ * comes back as zeros, in out and in pieces. */
+int ts_attention_tiled(int device, const void *qkv, const void *qkv_bias, const int64_t *attention_mask, int32_t batch, int32_t seq,
+                       int32_t q_heads, int32_t kv_heads, int32_t head_dim, int causal, float scale, void *out, void *pieces, void *stream);
 /* The same for the decoder-style encoder the production app embeds with (Qwen/Qwen3-Embedding-0.6B, streamlit_app.py:55;
  * Qwen3Attention: grouped-query, causal, head size 128): out = softmax(Q K^T / sqrt(128) + causal + key mask) V per (sequence,
  * query head); query head h reads key / value head h / (q_heads / kv_heads).  qkv: device bf16 [batch * seq][(q_heads + 2 kv_heads)

@@ -6,6 +6,7 @@
 
 #include "host.h"
 #include "kernels_attention.h"
+#include "kernels_attention_tiled.h"
 #include "kernels_encoder.h"
 
 // ---- validators: TS_OK, or the refusal (code and text set) ---------------------------------------------------------------------
@@ -195,6 +196,35 @@ extern "C" int ts_attention_float(int device, const void* qkv, const void* qkv_b
         return dispatch_value<0, 1>(causal != 0, [&](auto c) {
             // the limit: what the longest sequence of the head size needs
             return launch_lds<attention_f32_kernel<hd, c != 0>, attn_f32_lds_limit(hd)>(
+                device, p.grid, p.block, p.lds, st, (const float*)qkv, attention_mask, batch, seq, q_heads, kv_heads, scale_log2e,
+                (float*)out, (unsigned short*)pieces, (const float*)qkv_bias);
+        });
+    });
+}
+
+extern "C" int ts_attention_tiled(int device, const void* qkv, const void* qkv_bias, const int64_t* attention_mask, int32_t batch, int32_t seq,
+                                  int32_t q_heads, int32_t kv_heads, int32_t head_dim, int causal, float scale, void* out, void* pieces,
+                                  void* stream) {
+    // ts_attention_float's checks, in its order, with its texts
+    if (!qkv || (!out && !pieces)) return fail(TS_ERR_INVALID, "NULL argument");
+    TS_TRY(aligned16({qkv_bias}, "qkv_bias must be 16-byte aligned"));
+    if (batch < 0 || seq < 1 || q_heads < 1 || kv_heads < 1 || q_heads % kv_heads != 0)
+        return fail(TS_ERR_INVALID, "batch = %d, seq = %d, heads = %d over %d", batch, seq, q_heads, kv_heads);
+    const AttnTiledPlan p = attn_tiled_plan(batch, seq, q_heads, head_dim);
+    if (!p.ok)
+        return fail(TS_ERR_UNSUPPORTED,
+                    "head size %d / %d tokens: this kernel serves head sizes 64 / 128 / 256 up to %d tokens (and 2^31 - 1 query blocks of %d)",
+                    head_dim, seq, kAttnTiledMaxSeq, kAttnTiledQueries);
+    if ((((uintptr_t)qkv | (uintptr_t)out) & 15) != 0 || (((uintptr_t)pieces) & 7) != 0)
+        return fail(TS_ERR_INVALID, "qkv and out must be 16-byte aligned, pieces 8-byte");
+    if (!(scale > 0.0f)) return fail(TS_ERR_INVALID, "scale must be positive");
+    if (batch == 0) return TS_OK;
+    hipStream_t st;
+    TS_TRY(enter_device(device, stream, &st));
+    const float scale_log2e = scale * 1.4426950408889634f;
+    return dispatch_value<64, 128, 256>(head_dim, [&](auto hd) {
+        return dispatch_value<0, 1>(causal != 0, [&](auto c) {
+            return launch_lds<attention_f32_tiled_kernel<hd, c != 0>, attn_tiled_lds(hd)>(
                 device, p.grid, p.block, p.lds, st, (const float*)qkv, attention_mask, batch, seq, q_heads, kv_heads, scale_log2e,
                 (float*)out, (unsigned short*)pieces, (const float*)qkv_bias);
         });

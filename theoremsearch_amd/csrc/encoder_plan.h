@@ -133,6 +133,37 @@ inline AttnPlan attn_float_plan(int batch, int seq, int q_heads, int head_dim) {
     return p;
 }
 
+// ts_attention_tiled (kernels_attention_tiled.h): the same heads at any length up to kAttnTiledMaxSeq.  One workgroup of four
+// waves per (sequence, query head, block of kAttnTiledQueries queries); V^T goes through two LDS buffers of attn_tiled_chunk keys
+// each (pitch chunk + 4 floats), about 68 - 74 KB together: two workgroups share a CU's 160 KiB
+constexpr int kAttnTiledMaxSeq = 32768;                             // Qwen3's max_position_embeddings
+constexpr int kAttnTiledQueries = 64;                               // four query tiles of 16, one per wave
+constexpr int attn_tiled_chunk(int HD) { return HD == 64 ? 128 : HD == 128 ? 64 : HD == 256 ? 32 : 0; }
+constexpr int attn_tiled_lds(int HD) { return 2 * HD * (attn_tiled_chunk(HD) + 4) * 4; }
+static_assert(attn_tiled_lds(64) <= 80 * 1024 && attn_tiled_lds(128) <= 80 * 1024 && attn_tiled_lds(256) <= 80 * 1024,
+              "two workgroups per CU");
+
+struct AttnTiledPlan {
+    bool ok;            // the head size and the sequence are served and the grid fits 31 bits (the caller has refused seq < 1 and heads < 1)
+    int tiles;          // T = ceil(seq / 16)
+    int qblocks;        // ceil(T / 4): blocks of kAttnTiledQueries queries
+    unsigned grid, block;
+    int lds;
+};
+inline AttnTiledPlan attn_tiled_plan(int batch, int seq, int q_heads, int head_dim) {
+    AttnTiledPlan p = {};
+    if (!(head_dim == 64 || head_dim == 128 || head_dim == 256) || seq > kAttnTiledMaxSeq) return p;
+    p.tiles = (seq + 15) / 16;
+    p.qblocks = (p.tiles + 3) / 4;
+    const int64_t grid = (int64_t)batch * q_heads * p.qblocks;
+    if (grid > INT32_MAX) return p;
+    p.ok = true;
+    p.grid = (unsigned)grid;
+    p.block = 256;
+    p.lds = attn_tiled_lds(head_dim);
+    return p;
+}
+
 // ---------------------------------------------------------------------------------------------
 // the other grids
 // ---------------------------------------------------------------------------------------------

@@ -75,8 +75,27 @@ def attention_float(qkv: torch.Tensor, key_mask: Optional[torch.Tensor], B: int,
     return ctx, pieces
 
 
+def attention_tiled(qkv: torch.Tensor, key_mask: Optional[torch.Tensor], B: int, S: int, hq: int, hkv: int, hd: int, causal: bool,
+                    scale: float, want_pieces: bool = False, bias: Optional[torch.Tensor] = None, want_context: bool = True):
+    """`attention_float` at any length from 1 to 32,768 tokens (``ts_attention_tiled``: V^T through LDS in chunks of keys, a
+    workgroup per 64 queries): the same arguments, the same return value, the same bits where both serve a shape."""
+    qkv = qkv.contiguous()
+    ctx = torch.empty((B, S, hq * hd), dtype=torch.float32, device=qkv.device) if (want_context or not want_pieces) else None
+    pieces = torch.empty((B * S, 3 * hq * hd), dtype=torch.bfloat16, device=qkv.device) if want_pieces else None
+    _ffi.encoder_op("ts_attention_tiled", qkv, qkv, bias, key_mask, B, S, hq, hkv, hd, 1 if causal else 0, float(scale), ctx, pieces)
+    return ctx, pieces
+
+
 # The limits of the library's kernels (csrc/encoder_plan.h; tests/test_encoder_ref_cpu.py holds each against the library's refusals)
 _FLOAT_ATTENTION_MAX_SEQ = {64: 512, 128: 256, 256: 128}      # what fits the CU's LDS as V^T (attn_f32_max_seq)
+_TILED_MAX_SEQ = 32768                                        # ts_attention_tiled: tokens (kAttnTiledMaxSeq)
+_TILED_CHUNK = {64: 128, 128: 64, 256: 32}                    # keys per staged chunk of V^T by head size (attn_tiled_chunk)
+# Where the forwards take ts_attention_tiled: only where it was at least as fast as torch's attention with its layout copies
+# (tools/attention_tiled_timing.py, profiles/attention_tiled_timing.jsonl, 256 sequences, us per call, tiled against torch):
+# heads of 128 (Qwen3, causal) 2,229 / 8,184 at 384 tokens, 5,685 / 12,900 at 512, 5,523 / 11,552 at 64 x 1,024: every length;
+# heads of 256 (Gemma3) 628 / 768 at 192 tokens, 1,085 / 1,114 at 256, but 2,373 / 2,105 at 384: up to 256 tokens, torch's beyond;
+# heads of 64 (BERT) have no length past ts_attention_float's 512 (the position table ends there): not measured, every length.
+_TILED_ROUTED_MAX_SEQ = {64: _TILED_MAX_SEQ, 128: _TILED_MAX_SEQ, 256: 256}
 _SHORT_HEAD, _SHORT_MAX_SEQ = 64, 128                         # ts_attention_short (bf16): head size, tokens (kAttnRowsMaxSeq)
 _GQA_HEAD, _GQA_MAX_SEQ = 128, 128                            # ts_attention_gqa (bf16): head size, tokens (kAttnGqaRowsMaxSeq)
 _NORM_MAX_VECS = 256                                          # the norm kernels: 16-byte accesses per row (64 lanes x kLnMax)
@@ -86,6 +105,22 @@ def float_attention_applies(x: torch.Tensor, S: int, hd: int) -> bool:
     """fp32 hidden states, a head size the kernel serves and a sequence whose V^T fits the LDS (512 / 256 / 128 tokens for heads
     of 64 / 128 / 256); TS_ENCODER_ATTENTION=0 keeps torch's attention."""
     return (x.dtype == torch.float32 and S <= _FLOAT_ATTENTION_MAX_SEQ.get(hd, 0) and os.environ.get("TS_ENCODER_ATTENTION", "1") != "0")
+
+
+def fp32_attention_kind(x: torch.Tensor, S: int, hd: int) -> Optional[str]:
+    """Which of the library's fp32 attentions serves fp32 hidden states ``x`` at ``S`` tokens and head size ``hd``: ``"float"``
+    where `float_attention_applies` (ts_attention_float, routing unchanged), ``"tiled"`` beyond that up to 32,768 tokens
+    (ts_attention_tiled) - for heads of 256 up to 256 tokens only: at 384 it measured slower than torch's attention, see
+    `_TILED_ROUTED_MAX_SEQ` -, ``None`` - torch's attention - otherwise, for another head size, for bf16 or with
+    TS_ENCODER_ATTENTION=0."""
+    if float_attention_applies(x, S, hd):
+        return "float"
+    if x.dtype == torch.float32 and S <= _TILED_ROUTED_MAX_SEQ.get(hd, 0) and os.environ.get("TS_ENCODER_ATTENTION", "1") != "0":
+        return "tiled"
+    return None
+
+
+_FP32_ATTENTION = {"float": attention_float, "tiled": attention_tiled}
 
 
 class FusedBertForward:
@@ -210,19 +245,20 @@ class FusedBertForward:
         # ONE wave per (sequence, head), straight from the fused projection to the context layout (``ts_attention_short``)
         short = x.dtype == torch.bfloat16 and hd == _SHORT_HEAD and S <= _SHORT_MAX_SEQ and os.environ.get("TS_ENCODER_ATTENTION", "1") != "0"
         # (the most negative finite value, not -inf: a sequence without a single token would otherwise soften to NaN)
-        short32 = float_attention_applies(x, S, hd)          # fp32: the library's fp32 attention (ts_attention_float)
+        kind32 = fp32_attention_kind(x, S, hd)               # fp32: the library's fp32 attention (ts_attention_float / _tiled)
+        short32 = kind32 is not None
         mask = None if (no_padding or short or short32) else torch.zeros((B, 1, 1, S), dtype=x.dtype, device=x.device).masked_fill_(
             ~attention_mask[:, None, None, :].to(torch.bool), torch.finfo(x.dtype).min)
         key_mask = None if (no_padding or not (short or short32)) else attention_mask.to(torch.int64).contiguous()
         pieces = self.pieces and x.dtype == torch.float32 and "wo_p" in self.layers[0]
         if pieces:
-            return self._forward_pieces(x, mask, key_mask, short32, B, S, H, hd)
+            return self._forward_pieces(x, mask, key_mask, kind32, B, S, H, hd)
         for L in self.layers:
             qkv = F.linear(x, L["wqkv"], L["bqkv"])
             if short:
                 ctx = self._attention(qkv, key_mask, B, S)
             elif short32:
-                ctx = attention_float(qkv, key_mask, B, S, self.heads, self.heads, hd, False, hd ** -0.5)[0]
+                ctx = _FP32_ATTENTION[kind32](qkv, key_mask, B, S, self.heads, self.heads, hd, False, hd ** -0.5)[0]
             else:
                 qkv = qkv.view(B, S, 3, self.heads, hd).permute(2, 0, 3, 1, 4)
                 ctx = F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2], attn_mask=mask)
@@ -232,11 +268,11 @@ class FusedBertForward:
             x = self._add_ln(F.linear(h, L["w2"], L["b2"]), x, L["ln2"])
         return x
 
-    def _forward_pieces(self, x: torch.Tensor, mask: Optional[torch.Tensor], key_mask: Optional[torch.Tensor], short32: bool, B: int,
-                        S: int, H: int, hd: int) -> torch.Tensor:
+    def _forward_pieces(self, x: torch.Tensor, mask: Optional[torch.Tensor], key_mask: Optional[torch.Tensor], kind32: Optional[str],
+                        B: int, S: int, H: int, hd: int) -> torch.Tensor:
         """The layers of an fp32 model with every GEMM on the bf16 matrix pipe (``fp32_gemm="bf16x3"``): weights are pieces
         (``_refresh``), every activation reaches its GEMM as pieces written by the kernel that produced it (LayerNorm, GELU, the
-        fp32 attention up to 128 tokens; beyond, torch's attention output passes through ``ts_split_pieces``)."""
+        library's fp32 attention ``kind32``; without one, torch's attention output passes through ``ts_split_pieces``)."""
         F = torch.nn.functional
         exact_gelu = self.cfg.hidden_act == "gelu"
         xp = split_pieces(x.view(B * S, H), 0)
@@ -244,8 +280,8 @@ class FusedBertForward:
             # every GEMM runs WITHOUT its bias: the kernel that reads its output adds it on the way in (torch.addmm with an output
             # type first copies the broadcast bias into the result: one more pass over every GEMM's output)
             qkv = pieces_mm(xp, L["wqkv_p"])
-            if short32:                # the attention writes the pieces of its output itself
-                cp = attention_float(qkv, key_mask, B, S, self.heads, self.heads, hd, False, hd ** -0.5, want_pieces=True, bias=L["bqkv"], want_context=False)[1]
+            if kind32:                 # the attention writes the pieces of its output itself
+                cp = _FP32_ATTENTION[kind32](qkv, key_mask, B, S, self.heads, self.heads, hd, False, hd ** -0.5, want_pieces=True, bias=L["bqkv"], want_context=False)[1]
             else:
                 qkv = (qkv + L["bqkv"]).view(B, S, 3, self.heads, hd).permute(2, 0, 3, 1, 4)
                 ctx = F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2], attn_mask=mask)
@@ -270,7 +306,9 @@ class FusedQwen3Forward:
 
     * causal grouped-query attention of short sequences (bf16, up to 128 tokens) as ONE kernel straight from the stacked
       projection (``ts_attention_gqa``: one wave per (sequence, query head); torch's flash-attention launch took 202 us per
-      layer at 256 sequences x 32 tokens, 504 us at 128); longer sequences and fp32 keep ``scaled_dot_product_attention``.
+      layer at 256 sequences x 32 tokens, 504 us at 128); longer bf16 sequences keep ``scaled_dot_product_attention``;
+    * in fp32 the library's fp32 attention at every length: ``ts_attention_float`` up to 256 tokens, ``ts_attention_tiled`` beyond
+      (`fp32_attention_kind`) - no additive mask, no layout copies, and in the pieces path the pieces straight from the kernel.
 
     Same weights, same order of operations, the roundings of the modules replaced."""
 
@@ -376,7 +414,8 @@ class FusedQwen3Forward:
         # short sequences in bf16: the library's own causal grouped-query attention (TS_ENCODER_ATTENTION=0 keeps torch's)
         short = (x.dtype == torch.bfloat16 and self.hd == _GQA_HEAD and S <= _GQA_MAX_SEQ and x.is_contiguous() and
                  os.environ.get("TS_ENCODER_ATTENTION", "1") != "0")
-        short32 = float_attention_applies(x, S, self.hd)      # fp32: the library's fp32 attention (causal, grouped-query)
+        kind32 = fp32_attention_kind(x, S, self.hd)           # fp32: the library's fp32 attention (causal, grouped-query)
+        short32 = kind32 is not None
         key_mask = None if (no_padding or not (short or short32)) else attention_mask.to(torch.int64).contiguous()
         if not no_padding and not short and not short32:
             # causal, and padding keys are never attended to (the most negative finite value: rows of padding stay finite)
@@ -394,7 +433,7 @@ class FusedQwen3Forward:
                 qkv = pieces_mm(hp, L["wqkv_p"]).view(B, S, -1)
                 _ffi.encoder_op("ts_qk_norm_rope", x, qkv, L["qn"], L["kn"], cos, sin, self.eps, B * S, S, self.hq, self.hkv, hd, dt)
                 if short32:
-                    cp = attention_float(qkv, key_mask, B, S, self.hq, self.hkv, hd, True, hd ** -0.5, want_pieces=True, want_context=False)[1]
+                    cp = _FP32_ATTENTION[kind32](qkv, key_mask, B, S, self.hq, self.hkv, hd, True, hd ** -0.5, want_pieces=True, want_context=False)[1]
                 else:
                     cp = split_pieces(self._sdpa(qkv, mask, B, S, nq, nkv, hd).reshape(B * S, nq), 0)
                 x, h, hp = self._add_rmsnorm_pieces(x, pieces_mm(cp, L["wo_p"]).view(B, S, H), L["ln2"], True)
@@ -412,7 +451,7 @@ class FusedQwen3Forward:
                 ctx = torch.empty((B, S, nq), dtype=x.dtype, device=x.device)
                 _ffi.encoder_op("ts_attention_gqa", x, qkv, key_mask, B, S, self.hq, self.hkv, hd, 1, ctx)
             elif short32:
-                ctx = attention_float(qkv, key_mask, B, S, self.hq, self.hkv, hd, True, hd ** -0.5)[0]
+                ctx = _FP32_ATTENTION[kind32](qkv, key_mask, B, S, self.hq, self.hkv, hd, True, hd ** -0.5)[0]
             else:
                 ctx = self._sdpa(qkv, mask, B, S, nq, nkv, hd)
             x, h = self._add_rmsnorm(x, F.linear(ctx, L["wo"]), L["ln2"], True)
@@ -438,8 +477,9 @@ class FusedGemma3Forward:
       sliding and full attention layers have their own cos / sin tables);
     * ``gelu_tanh(gate) * up`` as ONE kernel (``ts_geglu``).
 
-    The attention is ``scaled_dot_product_attention`` (heads of 256, grouped-query, every key visible: sequences shorter than
-    the sliding window).  Same weights, same order of operations, the roundings of the modules replaced.  Longer sequences
+    The attention (heads of 256, grouped-query, every key visible: sequences shorter than the sliding window) is the library's in
+    fp32 - ``ts_attention_float`` up to 128 tokens, ``ts_attention_tiled`` up to 256 (`fp32_attention_kind`) - and
+    ``scaled_dot_product_attention`` otherwise.  Same weights, same order of operations, the roundings of the modules replaced.  Longer sequences
     than the sliding window take the model's own forward."""
 
     def __init__(self, model):
@@ -542,7 +582,8 @@ class FusedGemma3Forward:
             cos, sin = m.rotary_emb(x, pos, lt)                       # [1 x S x 256] of the model's type
             tables[lt] = (cos[0].contiguous(), sin[0].contiguous())
         mask = None
-        short32 = float_attention_applies(x, S, self.hd)      # fp32: the library's fp32 attention (every key visible, heads of 256)
+        kind32 = fp32_attention_kind(x, S, self.hd)           # fp32: the library's fp32 attention (every key visible, heads of 256)
+        short32 = kind32 is not None
         key_mask = attention_mask.to(torch.int64).contiguous() if (short32 and not no_padding) else None
         if not no_padding and not short32:
             neg = torch.finfo(x.dtype).min
@@ -561,7 +602,7 @@ class FusedGemma3Forward:
             _ffi.encoder_op("ts_gemma_qk_norm_rope", x, qkv, L["qn"], L["kn"], cos, sin, self.eps, B * S, S, self.hq, self.hkv, hd, dt)
             cp = None
             if short32:
-                ctx, cp = attention_float(qkv, key_mask, B, S, self.hq, self.hkv, hd, False, self.scaling, want_pieces=pieces, want_context=not pieces)
+                ctx, cp = _FP32_ATTENTION[kind32](qkv, key_mask, B, S, self.hq, self.hkv, hd, False, self.scaling, want_pieces=pieces, want_context=not pieces)
             else:
                 q = qkv[..., :nq].view(B, S, self.hq, hd).transpose(1, 2)
                 k = qkv[..., nq:nq + nkv].view(B, S, self.hkv, hd).transpose(1, 2)
