@@ -264,10 +264,14 @@ __device__ __forceinline__ void mfma16_write_probe(unsigned long long* dbg, unsi
 // tile's last MFMA, where one wave per SIMD has nothing to hide them behind.  Two accumulator sets, accL[tile parity] (the loop runs
 // two tiles per trip, as for the k-split), and the integer thresholds per parity: tile t multiplies into its own set while twelve
 // two-instruction pieces (TS16_LATE) in the gaps behind the MFMAs of query block 3 of its k-steps 0 .. 5 test the other set - tile
-// t - 1, last written a tile ago - and leave four lane masks in SGPRs.  The end of tile t is the ring's drain, one OR of the masks
-// and a branch; the rare path stages the pairs of tile t - 1 from the other set with that tile's row base (the checked form from
-// the first tile with padding rows on).  The last tile is tested behind the loop as the other form tests every tile.  The same
-// pairs in another order within a wave's list.  Registers: 24 query fragments in VGPRs, 24 in AGPRs, as the k-split.
+// t - 1, last written a tile ago - and leave four lane masks in SGPRs; their union and the scalar bookkeeping of the next tile
+// (ring offsets, the stream's tile base, the fragment read addresses, the address of the scalars two tiles ahead) stand in the same
+// gaps of the later k-steps.  The steady trips run in a loop of their own, one hand-over to the general units follows.  The end
+// of a steady tile t is the ring's drain, the test of the union with the rare-path branch, the load of tile t + 2's scalars into
+// the registers tile t read them from (two sets by parity, nothing rotated) and the loop branch; the rare path stages the pairs
+// of tile t - 1 from the other set with that tile's row base (the checked form from the first tile with padding rows on).  The
+// last tile is tested behind the loop as the other form tests every tile.  The same pairs in another order within a wave's list.
+// Registers: 24 query fragments in VGPRs, 24 in AGPRs, as the k-split.
 template <int D, int NB, int VARIANT, bool SPARSE, bool F32 = false, bool PAIR = false, bool KSPLIT = false>
 __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a) {
     static_assert(!PAIR || (!SPARSE && !F32), "pairs exist for the bf16 full pass");
@@ -478,6 +482,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     int lthr[kLate ? 2 : 1][kLate ? NB : 1];
     int lbest = 0;
     u64 lhit[kLate ? NB : 1];
+    u64 lany = 0, lany2 = 0;                             // the union of lhit[], made among the MFMAs too (TS16_LATE)
     if constexpr (kLate) {
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
@@ -590,7 +595,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
             constexpr int g_ = NB == 1 ? (G_) + 2 : (G_);                                                  \
             constexpr int P_ = ((KS_) / 2) * gpk_ + g_;                                                    \
             if constexpr ((KS_) % 2 == 0 && g_ >= 0 && g_ < gpk_ && (NB == 1) == ((G_) < 0) && P_ < 4 * NB) { \
-                if constexpr (kLate) screen_thr_piece<P_ & 3>(lthr[par_][P_ >> 2], tmc, fq1[P_ >> 2], fq2[P_ >> 2], fq3[P_ >> 2]); \
+                if constexpr (kLate) screen_thr_piece<P_ & 3>(lthr[par_][P_ >> 2], tml[par_], fq1[P_ >> 2], fq2[P_ >> 2], fq3[P_ >> 2]); \
                 else screen_thr_piece<P_ & 3>(ithr[P_ >> 2], tmc, fq1[P_ >> 2], fq2[P_ >> 2], fq3[P_ >> 2]);   \
             }                                                                                              \
         }                                                                                                  \
@@ -598,6 +603,11 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     // late-test screen: piece 3 b + p of the block tests of the PREVIOUS tile (late_test_a / b / c, kernels_screen8_tile.h) in gap G_
     // (0, 1) behind the two MFMAs of query block 3 of k-step KS_ - gaps that hold nothing else in any k-step: k-steps 0 .. 5.  The
     // pieces read the other parity's accumulators and thresholds; the four lane masks stay in SGPRs to the end of the tile.
+    // The same gaps of the later k-steps take the scalar bookkeeping that used to stand behind the tile's last MFMA, where one
+    // wave per SIMD has nothing to overlap it with (scalar instructions do not take the vector issue): the union of the four
+    // masks (k-steps 6, 7: lany), and in a steady tile, behind the DMA piece of the last k-step, the ring offsets and the stream's
+    // tile base of the NEXT tile (soff / poff / noff_l, s_tile) and the address of the scalars two tiles ahead (sp_l).  The empty
+    // statements pin the values: computed here, not where the next tile first reads them.
 #define TS16_LATE(KS_, G_)                                                                                 \
     do {                                                                                                   \
         if constexpr (kLate) {                                                                             \
@@ -607,6 +617,27 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
                 if constexpr (p_ % 3 == 0) late_test_a(lbest, accL[par_ ^ 1][0][b_], accL[par_ ^ 1][1][b_]); \
                 if constexpr (p_ % 3 == 1) late_test_b(lbest, accL[par_ ^ 1][1][b_]);                      \
                 if constexpr (p_ % 3 == 2) late_test_c(lhit[b_], lbest, lthr[par_ ^ 1][b_]);               \
+            }                                                                                              \
+            if constexpr (p_ == 3 * NB) late_or(lany, lhit[0], lhit[1]);                                   \
+            if constexpr (p_ == 3 * NB + 1) late_or(lany2, lhit[2], lhit[3]);                              \
+            if constexpr (p_ == 3 * NB + 2) late_or(lany, lany, lany2);                                    \
+            if constexpr (steady_ && p_ == 2 * (kSteps - kA)) {   /* k-step kSteps - kA has fetched the unit's last k-step */ \
+                asm volatile("" : "+s"(noff_l));                  /* (the two additions here, not behind the DMA piece) */ \
+                la_l[0] = lds_base + noff_l + xo[0] + koff;                                                \
+                la_l[1] = lds_base + noff_l + xo[1] + koff;                                                \
+                asm volatile("" : "+v"(la_l[0]), "+v"(la_l[1]));                                           \
+                na[0] = la_l[0]; na[1] = la_l[1];                                                          \
+            }                                                                                              \
+            if constexpr (steady_ && p_ == 2 * kSteps - 2) {                                               \
+                poff = soff;                                                                               \
+                soff = noff_l;                                                                             \
+                noff_l = (soff + kUnitBytes == (unsigned)dims::kLds) ? 0u : soff + kUnitBytes;             \
+                s_tile += steady_jump;                                                                     \
+                asm volatile("" : "+s"(poff), "+s"(soff), "+s"(noff_l), "+s"(s_tile));                     \
+            }                                                                                              \
+            if constexpr (steady_ && p_ == 2 * kSteps - 1) {                                               \
+                sp_l += 1;                                                                                 \
+                asm volatile("" : "+s"(sp_l));                                                             \
             }                                                                                              \
         }                                                                                                  \
     } while (0)
@@ -699,10 +730,15 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
 #define TS16_UNIT_S(UI)                                                                                    \
     do {                                                                                                   \
         constexpr int cui_ = ((UI) + kSlots - 1) % kUnits;                                                 \
-        const unsigned noff = (soff + kUnitBytes == (unsigned)dims::kLds) ? 0u : soff + kUnitBytes;        \
+        /* (late-test screen: the next slot's offset is carried, rotated among the MFMAs of the unit before - TS16_LATE) */ \
+        const unsigned noff = kLate ? noff_l : (soff + kUnitBytes == (unsigned)dims::kLds) ? 0u : soff + kUnitBytes; \
         unsigned ua[2], na[2];                                                                             \
-        ua[0] = lds_base + soff + xo[0] + koff; ua[1] = lds_base + soff + xo[1] + koff;                    \
-        na[0] = lds_base + noff + xo[0] + koff; na[1] = lds_base + noff + xo[1] + koff;                    \
+        if constexpr (!kLate) {                                                                            \
+            ua[0] = lds_base + soff + xo[0] + koff; ua[1] = lds_base + soff + xo[1] + koff;                \
+            na[0] = lds_base + noff + xo[0] + koff; na[1] = lds_base + noff + xo[1] + koff;                \
+        } else {   /* one carried pair of read addresses: this unit's image, from TS16_LATE's piece on the next one's */ \
+            ua[0] = la_l[0]; ua[1] = la_l[1];                                                              \
+        }                                                                                                  \
         if constexpr (!kNoDma) wait_vmcnt<(kSlots - 3) * kPieces>();   /* own pieces of unit u + 1 */       \
         if constexpr (PAIR && (UI) == (2 % kUnits)) {                   /* ahead of the partner: give way */ \
             /* (the read and its use are unconditional: a value defined under a branch would reach this point through a */ \
@@ -729,9 +765,11 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
         TS16_STEP(UI, 0); TS16_STEP(UI, 1); TS16_STEP(UI, 2); TS16_STEP(UI, 3);                            \
         if constexpr (kUnitSteps > 4) { TS16_STEP(UI, 4 % kUnitSteps); TS16_STEP(UI, 5 % kUnitSteps); TS16_STEP(UI, 6 % kUnitSteps); TS16_STEP(UI, 7 % kUnitSteps); } \
         if constexpr (kUnitSteps > 8) { TS16_STEP(UI, 8 % kUnitSteps); TS16_STEP(UI, 9 % kUnitSteps); TS16_STEP(UI, 10 % kUnitSteps); TS16_STEP(UI, 11 % kUnitSteps); } \
-        if constexpr (cui_ == kUnits - 1 && !kNoDma) s_tile += steady_jump;                                \
-        poff = soff;                                                                                       \
-        soff = noff;                                                                                       \
+        if constexpr (!kLate) {                                                                            \
+            if constexpr (cui_ == kUnits - 1 && !kNoDma) s_tile += steady_jump;                            \
+            poff = soff;                                                                                   \
+            soff = noff;                                                                                   \
+        }                                                                                                  \
     } while (0)
 
 #define TS16_UNIT(UI)                                                                                      \
@@ -786,6 +824,9 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     const int nt_steady = (a.run == 1 && ahead == kSlots - 1 && !kStamps && nu > ahead) ? (nu - ahead) / kUnits : 0;
     const int64_t steady_jump = tile_bytes * a.tile_stride;
     unsigned soff = 0, poff = (unsigned)(kSlots - 1) * kUnitBytes;
+    unsigned noff_l = (unsigned)kUnitBytes;              // late-test screen: the slot behind soff (TS16_UNIT_S, TS16_LATE)
+    unsigned la_l[2] = {lds_base + xo[0] + koff, lds_base + xo[1] + koff};   // ... and its steady tiles' fragment read addresses
+    static_assert(!kLate || kUnits == 1, "the late-test screen advances the stream's tile base once per unit");
     // the steady part addresses the stream as (uniform tile base in SGPRs) + (this lane's offset inside a tile); the
     // prologue has issued `ahead` units: the next one lies in visited tile t0 + ahead / kUnits
     const unsigned dma_voff = (unsigned)(drow * (Deq * 2) + dchunk * 16);
@@ -802,6 +843,12 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     // (tile_scalars_ptr / screen_tile_scalars, kernels_screen8_tile.h: why a constant-address-space pointer and one 16-byte load)
     const tile_scalars_ptr scr_tile = (tile_scalars_ptr)a.scr_tile;
     f32x4 tmc = {0.0f, 0.0f, 0.0f, 0.0f}, tmn = {0.0f, 0.0f, 0.0f, 0.0f};
+    // late-test screen: the two sets by tile parity instead (the loop runs two tiles per trip): tile t reads tml[t & 1] and its
+    // tail loads tile t + 2 into the same registers - nothing is rotated.  A steady tile has at least kSlots - 1 tiles behind it,
+    // so its load needs no clamp to the workgroup's last tile: sp_l runs one entry per tile, advanced among the MFMAs (TS16_LATE),
+    // and points at tile t + 2 when the tail of tile t loads.  The general units keep the clamp and make no use of sp_l.
+    f32x4 tml[2] = {{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
+    tile_scalars_ptr sp_l = scr_tile + (t0 + 1);
     // I8: this tile's integer thresholds, computed among its MFMAs (piece 0 writes them; no initialisation: a loop of one
     // trip here changes the code hipcc makes for the other instantiations)
     int ithr[I8 ? NB : 1];
@@ -814,9 +861,15 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     screen_u64_gptr s_cand = nullptr;
     screen_mask_cptr s_mask = nullptr;
     if constexpr (I8) {
-        screen_tile_scalars(tmc, scr_tile, t0);
-        screen_tile_scalars(tmn, scr_tile, t0 + (nt > 1 ? 1 : 0));
-        asm volatile("" : "+s"(tmc), "+s"(tmn));
+        if constexpr (kLate) {
+            screen_tile_scalars(tml[0], scr_tile, t0);
+            screen_tile_scalars(tml[1], scr_tile, t0 + (nt > 1 ? 1 : 0));
+            asm volatile("" : "+s"(tml[0]), "+s"(tml[1]), "+s"(sp_l));
+        } else {
+            screen_tile_scalars(tmc, scr_tile, t0);
+            screen_tile_scalars(tmn, scr_tile, t0 + (nt > 1 ? 1 : 0));
+            asm volatile("" : "+s"(tmc), "+s"(tmn));
+        }
         const int64_t whole = a.n / kTileRows - t0;      // this workgroup's tiles in front of the first one with padding rows
         t_chk = whole < (int64_t)nt ? (whole > 0 ? (int)whole : 0) : nt;
         s_n = (u32)a.n;
@@ -829,11 +882,16 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
             asm volatile("" : "+s"(s_mask));
         }
     }
-    auto tile = [&](auto par_c, const int t) __attribute__((always_inline)) {
+    // FORM: kTilePick = steady or general by t, and the hand-over behind the last steady tile; the late-test screen runs its steady
+    // tiles in a loop of their own (kTileSteady: no general-unit code in that loop, nothing to copy where the two forms would
+    // meet, no dispatch per tile), hands over once behind it and runs the rest as kTileGeneral.
+    constexpr int kTilePick = 0, kTileSteady = 1, kTileGeneral = 2;
+    auto tile = [&](auto par_c, auto form_c, const int t) __attribute__((always_inline)) {
         constexpr int par_ = decltype(par_c)::value;
+        constexpr int form_ = decltype(form_c)::value;
         (void)par_;
         unsigned long long tail0 = 0;
-        if (t < nt_steady) {
+        if (form_ == kTileSteady || (form_ == kTilePick && t < nt_steady)) {
             TS16_UNIT_S(0);
             if constexpr (kUnits >= 2) TS16_UNIT_S(1 % kUnits);
             if constexpr (kUnits >= 4) {
@@ -847,7 +905,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
                 TS16_UNIT_S(7 % kUnits);
             }
             if constexpr (!kNoMma) lds_ring_landed(af);      // before any branch: see lds_ring_landed
-            if (t + 1 == nt_steady) {
+            if (form_ == kTilePick && t + 1 == nt_steady) {
                 // hand over to the general units: the same ring, counted in units
                 u = kUnits * nt_steady;
                 slot = u % kSlots;
@@ -898,10 +956,14 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
             return;
         }
         if constexpr (kLate) {
-            // what is left of the tail: the masks the fillers left, one branch, the scalars' rotation.  The pairs of tile t - 1 come
-            // out of the other parity's set, which nobody writes before the next tile's first MFMAs.
-            asm volatile("" : "+s"(tmn));
-            const u64 lany = (lhit[0] | lhit[1]) | (lhit[2] | lhit[3]);
+            // what is left of the tail: the test of the masks' union (made among the MFMAs), one branch and the load of the scalars two
+            // tiles ahead.  The pairs of tile t - 1 come out of the other parity's set, which nobody writes before the next tile's
+            // first MFMAs.  (tile t + 1's scalars: landed behind the drain above)
+            asm volatile("" : "+s"(tml[par_ ^ 1]));
+            // (steady: the load in front of the branch - the rare path reads no tile scalars - and volatile, so that it keeps its
+            // place among the asm statements: a plain one sinks through the next tile, which is the same basic block, to the wait
+            // in front of its first use)
+            if constexpr (form_ == kTileSteady) tml[par_] = *(const volatile __attribute__((address_space(4))) f32x4*)sp_l;
             if (__builtin_expect(lany != 0, 0)) {
                 const u32 tp = (u32)t0 + (u32)t - 1u;    // (tile 0 tests the "nothing passes" start of the odd set: never here)
                 const u32 row_base = tp * kTileRows + 4 * kq;
@@ -918,8 +980,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
                             mfma8_append_block<false>(accL[par_ ^ 1][0][b], accL[par_ ^ 1][1][b], lthr[par_ ^ 1][b], qid[b], row_base, scnt, stage8, 0u, s_nq, s_count, s_cand);
                 }
             }
-            tmc = tmn;
-            screen_tile_scalars(tmn, scr_tile, t0 + (t + 2 < nt ? t + 2 : nt - 1));
+            if constexpr (form_ != kTileSteady) screen_tile_scalars(tml[par_], scr_tile, t0 + (t + 2 < nt ? t + 2 : nt - 1));
             return;
         }
         if constexpr (I8) {
@@ -954,13 +1015,46 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
         }
         mfma16_tile_tail<NB, VARIANT, kStaged>(acc, thr, qid, cnt, t0, t, kq, writer, nwriters, a, stage, stage_cnt);
     };
-    if constexpr (KSPLIT || kLate) {
+    using tile_pick = std::integral_constant<int, kTilePick>;
+    if constexpr (kLate) {
+        // the steady trips (two tiles, one per accumulator set) in a loop that holds nothing else ...
+        int t = 0;
+        const int t_trips = __builtin_amdgcn_readfirstlane(nt_steady & ~1);      // (a scalar compare at the loop's end)
+        if (t_trips > 0) {
+            do {
+                tile(std::integral_constant<int, 0>{}, std::integral_constant<int, kTileSteady>{}, t);
+                tile(std::integral_constant<int, 1>{}, std::integral_constant<int, kTileSteady>{}, t + 1);
+                t += 2;
+            } while (t < t_trips);
+        }
+        if (t > 0) {
+            // ... one hand-over to the general units: the same ring, counted in units ...
+            u = kUnits * t;
+            slot = u % kSlots;
+            issue_u = u + ahead;
+            issue_ui = issue_u % kUnits;
+            issue_slot = issue_u % kSlots;
+            issue_run_pos = 0;
+            tile_src = s_tile + dma_voff;
+        }
+        // (the last steady tile's load of tile scalars lands here, on every path into the loop below: else hipcc puts a wait of its
+        // own among the MFMAs of that loop's first tile)
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(tml[0]), "+s"(tml[1]));
+        // ... and those for the rest (a left-over odd steady tile among them): t is even here, the parities go on as they were
+        // (the break: with "if (t + 1 < nt)" around the odd tile the loop has a path from the even tile's tail straight to the next
+        // even tile, on which hipcc sees that tail's scalar load in flight and waits for it among the MFMAs)
+        for (; t < nt; t += 2) {
+            tile(std::integral_constant<int, 0>{}, std::integral_constant<int, kTileGeneral>{}, t);
+            if (t + 1 >= nt) break;
+            tile(std::integral_constant<int, 1>{}, std::integral_constant<int, kTileGeneral>{}, t + 1);
+        }
+    } else if constexpr (KSPLIT) {
         for (int t = 0; t < nt; t += 2) {
-            tile(std::integral_constant<int, 0>{}, t);
-            if (t + 1 < nt) tile(std::integral_constant<int, 1>{}, t + 1);
+            tile(std::integral_constant<int, 0>{}, tile_pick{}, t);
+            if (t + 1 < nt) tile(std::integral_constant<int, 1>{}, tile_pick{}, t + 1);
         }
     } else {
-        for (int t = 0; t < nt; ++t) tile(std::integral_constant<int, 0>{}, t);
+        for (int t = 0; t < nt; ++t) tile(std::integral_constant<int, 0>{}, tile_pick{}, t);
     }
     if constexpr (KSPLIT && !kNoEpi && !kNoMma) {
         // the last tile's halves: one more barrier (every wave has written), then the same test

@@ -38,6 +38,10 @@ __device__ __forceinline__ void late_test_b(int& m, const f32x4& a1) {
 __device__ __forceinline__ void late_test_c(u64& mask, int m, int thr) {
     asm volatile("v_cmp_ge_i32 %0, %1, %2" : "=s"(mask) : "v"(m), "v"(thr));
 }
+// ... and the union of two of the lane masks, placed the same way (a scalar instruction: it writes SCC)
+__device__ __forceinline__ void late_or(u64& dst, u64 x, u64 y) {
+    asm volatile("s_or_b64 %0, %1, %2" : "=s"(dst) : "s"(x), "s"(y) : "scc");
+}
 
 // Integer thresholds of the int8 screen (kernels_screen8.h has the derivation and the rounding argument): every row of a tile
 // whose exact fp32 score can reach the query's `thr` has an int8 dot product >= the (tile, query) threshold.  The query's side
