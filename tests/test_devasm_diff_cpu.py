@@ -78,6 +78,44 @@ def test_changed_descriptor_value_is_reported(tmp_path):
     assert "u.s: descriptor kern_a: .amdhsa_next_free_vgpr 12 -> 13" in report
 
 
+def _summary(tmp_path, a_units, b_units):
+    for side, units in (("a", a_units), ("b", b_units)):
+        (tmp_path / side).mkdir()
+        for name, text in units.items():
+            (tmp_path / side / name).write_text(text)
+    out = io.StringIO()
+    n = devasm_diff.compare_dirs(tmp_path / "a", tmp_path / "b", out=out, summary=True)
+    return n, out.getvalue()
+
+
+MEM_BODY = "\tds_read_b128 v[4:7], v2\n\tv_mfma_f32_16x16x4_f32 v[8:11], v4, v5, v[8:11]\n\tglobal_store_dwordx4 v3, v[8:11], s[0:1]\n\ts_barrier"
+
+
+def test_summary_accepts_a_moved_kernel_that_keeps_its_static_figures(tmp_path):
+    a = _kernel("kern_a", 0, MEM_BODY, vgprs=60) + _kernel("kern_b", 1, BODY)
+    b = _kernel("kern_a", 0, MEM_BODY.replace("v[4:7], v2", "v[12:15], v1"), vgprs=64) + _kernel("kern_b", 1, BODY)
+    n, report = _summary(tmp_path, {"u.s": a}, {"u.s": b})
+    assert n == 0, report
+    assert "u.s: kern_a: moved, static gate holds" in report and "kern_b" not in report
+    assert "1 kernels moved, 0 one-sided or failing" in report
+    row = {ln.split()[0]: ln.split()[1:3] for ln in report.splitlines() if ln.startswith("    ") and len(ln.split()) >= 3}
+    assert row["next_free_vgpr"] == ["60", "64"] and row["waves_per_simd"] == ["8", "8"]
+    assert row["v_mfma"] == ["1", "1"] and row["ds_read"] == ["1", "1"] and row["global_store"] == ["1", "1"] and row["s_barrier"] == ["1", "1"]
+    assert row["group_segment_fixed_size"] == ["0", "0"]
+
+
+def test_summary_fails_on_a_count_lds_or_occupancy_change(tmp_path):
+    a = _kernel("kern_a", 0, MEM_BODY, vgprs=64) + _kernel("kern_b", 1, MEM_BODY, vgprs=64) + _kernel("kern_c", 2, MEM_BODY)
+    b = (_kernel("kern_a", 0, MEM_BODY + "\n\tds_read_b128 v[4:7], v2", vgprs=64) + _kernel("kern_b", 1, MEM_BODY, vgprs=72)
+         + _kernel("kern_c", 2, MEM_BODY).replace("group_segment_fixed_size 0", "group_segment_fixed_size 1024"))
+    n, report = _summary(tmp_path, {"u.s": a}, {"u.s": b})
+    assert n == 3, report
+    assert "u.s: kern_a: STATIC GATE FAILS: ds_read" in report
+    assert "u.s: kern_b: STATIC GATE FAILS: waves_per_simd" in report                 # 512 // 64 = 8 -> 512 // 72 = 7
+    assert "u.s: kern_c: STATIC GATE FAILS: group_segment_fixed_size" in report
+    assert devasm_diff.waves_per_simd(128) == 4 and devasm_diff.waves_per_simd(129) == 3 and devasm_diff.waves_per_simd(512) == 1
+
+
 def test_symbol_or_unit_on_one_side_only_is_reported(tmp_path):
     a = {"u.s": _kernel("kern_a", 0, BODY) + _kernel("kern_b", 1, BODY), "only_a.s": _kernel("kern_c", 0, BODY)}
     b = {"u.s": _kernel("kern_a", 0, BODY)}

@@ -6,6 +6,7 @@
 
 #include "host.h"
 #include "kernels_attention.h"
+#include "kernels_attention_f32.h"
 #include "kernels_attention_tiled.h"
 #include "kernels_encoder.h"
 

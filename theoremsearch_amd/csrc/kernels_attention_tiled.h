@@ -1,4 +1,4 @@
-// fp32 attention without the V^T-fits-LDS limit (ts_attention_tiled): attention_f32_kernel (kernels_attention.h) with the V^T image
+// fp32 attention without the V^T-fits-LDS limit (ts_attention_tiled): attention_f32_kernel (kernels_attention_f32.h) with the V^T image
 // fed in chunks of keys, for heads of 64 / 128 / 256 at any sequence length up to kAttnTiledMaxSeq.  The corpus texts are global
 // context + statement, up to 512 tokens and more for a checkpoint with a longer max_seq_length; attention_f32_kernel stops at
 // 512 / 256 / 128 tokens because it holds the whole V^T of a (sequence, head) in LDS.
@@ -23,7 +23,10 @@
 // order: the same two score chains over the same permutation of the head dimension, the same masking to -inf, exp2 with
 // scale * log2 e, the same rescale of o, m, l, the same KC output chains, the same 1 / l.  Chunking changes where a V^T fragment is
 // read from and nothing else, so wherever both kernels serve a shape the outputs are the same bits
-// (tests/test_attention_tiled_gpu.py).
+// (tests/test_attention_tiled_gpu.py).  The step is each kernel's own text, not a function the two share, on purpose: with the step (or
+// the K fragment load alone) as a __forceinline__ function called here, every instantiation's register assignment moves and
+// ts_attention_tiled at head 64 measures 0.4-1.5 % slower than before at 384 / 512 tokens (profiles/HISTORY.md, Round 21).
+// Whoever changes the step changes both texts; the test above holds them together.
 //
 // Staging.  A thread moves 16 bytes of a V row per item: lane -> (key = lane / 4 of 16, columns 4 (lane & 3) ..): a wave's load
 // covers 64 contiguous bytes of 16 rows, and its four 4-byte stores (column d, pitch C + 4 = 4 mod 32 banks) fall 2-way on a

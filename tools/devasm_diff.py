@@ -11,6 +11,14 @@ of the same name on both sides) and per function symbol it compares
   * the values of the `.amdhsa_*` kernel descriptor.
 It prints the units, functions and descriptors compared, every difference with its unit and symbol, and the symbols (or
 units) present on one side only.  Exit status 0 = the same symbols on both sides and no difference.
+
+    python tools/devasm_diff.py --summary DIR_A DIR_B
+
+The gate of a change that may move a kernel's instructions but not what it costs: for every kernel whose instructions or
+descriptor differ it prints a table of both sides - scratch and LDS bytes, .amdhsa_next_free_vgpr and the waves per SIMD it
+allows, and the counts of v_mfma*, ds_read*, ds_write*, global_load*, global_store*, buffer_* and s_barrier lines - and whether
+the static gate holds: scratch, LDS and every count unchanged, waves per SIMD not below side A's.  Exit status 0 = the same
+symbols on both sides and no moved kernel fails it.
 """
 import difflib
 import re
@@ -64,11 +72,42 @@ def parse(text):
     return funcs, descs
 
 
-def compare_dirs(dir_a, dir_b, out=sys.stdout):
-    """Prints the report; returns the number of differences (one-sided units and symbols count)."""
+_STATIC_FIELDS = (".amdhsa_private_segment_fixed_size", ".amdhsa_group_segment_fixed_size")
+_COUNTED = (("v_mfma", ("v_mfma",)), ("ds_read", ("ds_read", "ds_load")), ("ds_write", ("ds_write", "ds_store")),
+            ("global_load", ("global_load",)), ("global_store", ("global_store",)), ("buffer", ("buffer_",)), ("s_barrier", ("s_barrier",)))
+
+
+def waves_per_simd(next_free_vgpr):
+    """gfx90a and later: 512 unified registers per lane of a SIMD, allocated in blocks of 8, at most 8 waves."""
+    return min(8, 512 // max(8, -(-int(next_free_vgpr) // 8) * 8))
+
+
+def static_row(lines, desc):
+    """The figures a moved kernel must keep: scratch and LDS bytes, registers and the waves per SIMD they allow, and how many
+    matrix, LDS, global, buffer and barrier instructions it holds."""
+    row = {f[len(".amdhsa_"):]: desc.get(f) for f in _STATIC_FIELDS}
+    row["next_free_vgpr"] = desc.get(".amdhsa_next_free_vgpr")
+    row["waves_per_simd"] = waves_per_simd(row["next_free_vgpr"]) if row["next_free_vgpr"] is not None else None
+    for name, prefixes in _COUNTED:
+        row[name] = sum(1 for ln in lines if ln.startswith(prefixes))
+    row["lines"] = len(lines)
+    return row
+
+
+def static_verdict(a, b):
+    """'' when b keeps a's scratch, LDS and instruction counts and allows no fewer waves per SIMD, else what it broke."""
+    bad = [k for k in a if k not in ("next_free_vgpr", "waves_per_simd", "lines") and a[k] != b[k]]
+    if a["waves_per_simd"] is not None and b["waves_per_simd"] is not None and b["waves_per_simd"] < a["waves_per_simd"]:
+        bad.append("waves_per_simd")
+    return ", ".join(bad)
+
+
+def compare_dirs(dir_a, dir_b, out=sys.stdout, summary=False):
+    """Prints the report; returns the number of differences (one-sided units and symbols count).  summary: instead of the
+    first differing lines, one static table row pair (static_row) per differing kernel and whether it holds (static_verdict)."""
     a_units = {p.name: p for p in sorted(Path(dir_a).glob("*.s"))}
     b_units = {p.name: p for p in sorted(Path(dir_b).glob("*.s"))}
-    ndiff = nfunc = ndesc = nunits = 0
+    ndiff = nfunc = ndesc = nunits = nmoved = 0
     for name in sorted(set(a_units) ^ set(b_units)):
         print("unit %s: only in %s" % (name, dir_a if name in a_units else dir_b), file=out)
         ndiff += 1
@@ -80,6 +119,21 @@ def compare_dirs(dir_a, dir_b, out=sys.stdout):
             for sym in sorted(set(xa) ^ set(xb)):
                 print("%s: %s %s: only in %s" % (name, kind, sym, dir_a if sym in xa else dir_b), file=out)
                 ndiff += 1
+        if summary:
+            nfunc += len(set(fa) & set(fb))
+            ndesc += len(set(da) & set(db))
+            for sym in sorted(set(fa) & set(fb) & set(da) & set(db)):
+                if fa[sym] == fb[sym] and da[sym] == db[sym]:
+                    continue
+                nmoved += 1
+                ra, rb = static_row(fa[sym], da[sym]), static_row(fb[sym], db[sym])
+                bad = static_verdict(ra, rb)
+                ndiff += 1 if bad else 0
+                print("%s: %s: %s" % (name, sym, "STATIC GATE FAILS: " + bad if bad else "moved, static gate holds"), file=out)
+                print("    %-28s %10s %10s" % ("", "a", "b"), file=out)
+                for k in ra:
+                    print("    %-28s %10s %10s%s" % (k, ra[k], rb[k], "" if ra[k] == rb[k] else "   *"), file=out)
+            continue
         for sym in sorted(set(fa) & set(fb)):
             nfunc += 1
             if fa[sym] != fb[sym]:
@@ -93,11 +147,16 @@ def compare_dirs(dir_a, dir_b, out=sys.stdout):
                 if da[sym].get(field) != db[sym].get(field):
                     ndiff += 1
                     print("%s: descriptor %s: %s %s -> %s" % (name, sym, field, da[sym].get(field), db[sym].get(field)), file=out)
-    print("devasm_diff: %d units, %d functions, %d descriptors compared: %d differences" % (nunits, nfunc, ndesc, ndiff), file=out)
+    if summary:
+        print("devasm_diff: %d units, %d functions, %d descriptors compared: %d kernels moved, %d one-sided or failing the static gate"
+              % (nunits, nfunc, ndesc, nmoved, ndiff), file=out)
+    else:
+        print("devasm_diff: %d units, %d functions, %d descriptors compared: %d differences" % (nunits, nfunc, ndesc, ndiff), file=out)
     return ndiff
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 3:
+    args = [a for a in sys.argv[1:] if a != "--summary"]
+    if len(args) != 2:
         sys.exit(__doc__)
-    sys.exit(1 if compare_dirs(sys.argv[1], sys.argv[2]) else 0)
+    sys.exit(1 if compare_dirs(args[0], args[1], summary="--summary" in sys.argv[1:]) else 0)
