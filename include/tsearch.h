@@ -505,7 +505,8 @@ int ts_embed_layernorm(int device, const int64_t *ids, const int64_t *type_ids, 
  * [batch][seq], 0 = padding key, or NULL; out: device bf16 [batch][seq][heads * 64].  head_dim must be 64 and seq at most 128
  * (TS_ERR_UNSUPPORTED otherwise: the caller keeps its library attention); up to 64 tokens every score tile of a (sequence, head)
  * is held at once, 65 .. 128 tokens walk the query tiles against K / V fragments held in registers.  Scores and softmax in fp32, probabilities rounded to
- * bf16 for the second product (as flash attention does). */
+ * bf16 for the second product (as flash attention does).  A query row without a single allowed key (a sequence whose mask is
+ * all zeros) comes back as zeros (torch's softmax gives NaN there). */
 int ts_attention_short(int device, const void *qkv, const int64_t *attention_mask, int32_t batch, int32_t seq, int32_t heads,
                       int32_t head_dim, void *out, void *stream);
 
