@@ -263,10 +263,12 @@ __device__ __forceinline__ void mfma16_write_probe(unsigned long long* dbg, unsi
 // kVariantScreenLate (kLate; D = 384, NB = 4, launch_screen8_late.hip): the same screen with the block tests off the path behind a
 // tile's last MFMA, where one wave per SIMD has nothing to hide them behind.  Two accumulator sets, accL[tile parity] (the loop runs
 // two tiles per trip, as for the k-split), and the integer thresholds per parity: tile t multiplies into its own set while twelve
-// two-instruction pieces (TS16_LATE) in the gaps behind the MFMAs of query block 3 of its k-steps 0 .. 5 test the other set - tile
-// t - 1, last written a tile ago - and leave four lane masks in SGPRs; their union and the scalar bookkeeping of the next tile
-// (ring offsets, the stream's tile base, the fragment read addresses, the address of the scalars two tiles ahead) stand in the same
-// gaps of the later k-steps.  The steady trips run in a loop of their own, one hand-over to the general units follows.  The end
+// pieces of at most two instructions (TS16_LATE) in MFMA gaps of its k-steps 0 .. 6 test the other set - tile t - 1, last written
+// a tile ago - and leave four lane masks in SGPRs; their union and the scalar bookkeeping of the next tile (ring offsets, the
+// stream's tile base, the fragment read addresses, the address of the scalars two tiles ahead) stand in gaps of the later k-steps.
+// In a steady tile no piece reads what another piece of the same k-step wrote, the k-step's wait is the one instruction hipcc
+// sees (so it pads nothing), M0 is written a gap ahead of its DMA piece, and no gap holds more than three instructions, two of
+// them vector instructions.  The steady trips run in a loop of their own, one hand-over to the general units follows.  The end
 // of a steady tile t is the ring's drain, the test of the union with the rare-path branch, the load of tile t + 2's scalars into
 // the registers tile t read them from (two sets by parity, nothing rotated) and the loop branch; the rare path stages the pairs
 // of tile t - 1 from the other set with that tile's row base (the checked form from the first tile with padding rows on).  The
@@ -480,7 +482,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     // tile 0 tests it.
     f32x4 accL[kLate ? 2 : 1][2][kLate ? NB : 1];
     int lthr[kLate ? 2 : 1][kLate ? NB : 1];
-    int lbest = 0;
+    int lbest[2] = {0, 0};
     u64 lhit[kLate ? NB : 1];
     u64 lany = 0, lany2 = 0;                             // the union of lhit[], made among the MFMAs too (TS16_LATE)
     if constexpr (kLate) {
@@ -558,10 +560,17 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
                 constexpr int j_ = (S_) / kPieceEvery;                                                     \
                 unsigned long long d0_ = 0;                                                                \
                 if (VARIANT == kVariantStamps) d0_ = cycle_stamp();                                        \
-                if constexpr (steady_) lds_dma16s<j_ * 128, kStreamNT>(dma_voff, ssrc, idst + j_ * (4096 - 128 * TS16_DMA_IMM_LDS)); \
+                if constexpr (steady_ && kLate) lds_dma16s_go<j_ * 128, kStreamNT>(dma_voff, ssrc);        \
+                else if constexpr (steady_) lds_dma16s<j_ * 128, kStreamNT>(dma_voff, ssrc, idst + j_ * (4096 - 128 * TS16_DMA_IMM_LDS)); \
                 else lds_dma16<kStreamNT>(isrc + j_ * 128, idst + j_ * 4096);                                         \
                 if (VARIANT == kVariantStamps) t_dma += cycle_stamp() - d0_;                               \
             }                                                                                              \
+    } while (0)
+    // late-test screen, steady tiles: M0 of the piece one MFMA ahead of it (lds_dma16s_m0) - no pad inside the piece
+#define TS16_PIECE_M0(S_)                                                                                  \
+    do {                                                                                                   \
+        if constexpr (kLate && steady_ && !kNoDma && (S_) % kPieceEvery == kPieceEvery - 1)                \
+            lds_dma16s_m0<((S_) / kPieceEvery) * (4096 - 128 * TS16_DMA_IMM_LDS)>(idst);                   \
     } while (0)
     // k-split: the blocks that go to the partner (2, 3) first - at the end of a tile their sums are four MFMAs old when they are
     // stored, no wait states to add - and one filler behind each MFMA of the kept blocks: in the tile's last unit the sum and the
@@ -595,49 +604,74 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
             constexpr int g_ = NB == 1 ? (G_) + 2 : (G_);                                                  \
             constexpr int P_ = ((KS_) / 2) * gpk_ + g_;                                                    \
             if constexpr ((KS_) % 2 == 0 && g_ >= 0 && g_ < gpk_ && (NB == 1) == ((G_) < 0) && P_ < 4 * NB) { \
-                if constexpr (kLate) screen_thr_piece<P_ & 3>(lthr[par_][P_ >> 2], tml[par_], fq1[P_ >> 2], fq2[P_ >> 2], fq3[P_ >> 2]); \
+                /* (late-test screen: piece KS_ / 2 of block g_ - the four pieces of a block in four k-steps, a k-step head */ \
+                /* between a piece and the next, see TS16_STEP; nobody reads lthr before the next tile's late_test_c) */ \
+                if constexpr (kLate) screen_thr_piece<(P_ >> 2)>(lthr[par_][P_ & 3], tml[par_], fq1[P_ & 3], fq2[P_ & 3], fq3[P_ & 3]); \
                 else screen_thr_piece<P_ & 3>(ithr[P_ >> 2], tmc, fq1[P_ >> 2], fq2[P_ >> 2], fq3[P_ >> 2]);   \
             }                                                                                              \
         }                                                                                                  \
     } while (0)
-    // late-test screen: piece 3 b + p of the block tests of the PREVIOUS tile (late_test_a / b / c, kernels_screen8_tile.h) in gap G_
-    // (0, 1) behind the two MFMAs of query block 3 of k-step KS_ - gaps that hold nothing else in any k-step: k-steps 0 .. 5.  The
+    // late-test screen: the pieces of the block tests of the PREVIOUS tile (late_test_a / b / c, kernels_screen8_tile.h) in gap G_
+    // of k-step KS_, k-steps 0 .. 6: the three pieces of a block in three k-steps, two blocks abreast (lbest[0], lbest[1]).  The
     // pieces read the other parity's accumulators and thresholds; the four lane masks stay in SGPRs to the end of the tile.
     // The same gaps of the later k-steps take the scalar bookkeeping that used to stand behind the tile's last MFMA, where one
     // wave per SIMD has nothing to overlap it with (scalar instructions do not take the vector issue): the union of the four
-    // masks (k-steps 6, 7: lany), and in a steady tile, behind the DMA piece of the last k-step, the ring offsets and the stream's
-    // tile base of the NEXT tile (soff / poff / noff_l, s_tile) and the address of the scalars two tiles ahead (sp_l).  The empty
-    // statements pin the values: computed here, not where the next tile first reads them.
+    // masks (k-steps 6, 8, 10: lany), and in a steady tile the ring offsets (nring, idst), the fragment read addresses of the next
+    // tile (la_l), the address of the scalars two tiles ahead (sp_l) and, behind the DMA piece of the last k-step, the stream's
+    // tile base of the NEXT tile (s_tile).  The empty statements on both sides pin the values: computed in this gap, neither
+    // where the next tile first reads them nor right behind the last reader of their inputs, where hipcc gathers them.
+    // Placement (G_: 0, 1 = behind the MFMAs of block 3; 2, 3 = behind those of block 2, free in the odd k-steps and from
+    // k-step 8 on): hipcc puts a wait state in front of an asm statement that reads a register an earlier asm statement wrote
+    // when nothing but asm statements lies between the two.  The one instruction of a k-step that is not asm text is its head's
+    // s_waitcnt (TS16_STEP), so every producer -> consumer pair of pieces has a k-step head between its two statements, and no
+    // gap holds more than two vector instructions or three in all (tests/test_screen8_gaps_isa_cpu.py).
 #define TS16_LATE(KS_, G_)                                                                                 \
     do {                                                                                                   \
         if constexpr (kLate) {                                                                             \
-            constexpr int p_ = (KS_) * 2 + (G_);                                                           \
-            if constexpr (p_ < 3 * NB) {                                                                   \
-                constexpr int b_ = p_ / 3;                                                                 \
-                if constexpr (p_ % 3 == 0) late_test_a(lbest, accL[par_ ^ 1][0][b_], accL[par_ ^ 1][1][b_]); \
-                if constexpr (p_ % 3 == 1) late_test_b(lbest, accL[par_ ^ 1][1][b_]);                      \
-                if constexpr (p_ % 3 == 2) late_test_c(lhit[b_], lbest, lthr[par_ ^ 1][b_]);               \
+            constexpr int at_ = (KS_) * 4 + (G_);                                                          \
+            constexpr int o_ = par_ ^ 1;                                                                   \
+            /* blocks 0, 2 through lbest[0], blocks 1, 3 through lbest[1]: a, b, c of a block in three k-steps */ \
+            if constexpr (at_ == 0 * 4 + 0) late_test_a(lbest[0], accL[o_][0][0], accL[o_][1][0]);         \
+            if constexpr (at_ == 1 * 4 + 2) late_test_a(lbest[1], accL[o_][0][1], accL[o_][1][1]);         \
+            if constexpr (at_ == 1 * 4 + 0) late_test_b(lbest[0], accL[o_][1][0]);                         \
+            if constexpr (at_ == 2 * 4 + 0) late_test_b(lbest[1], accL[o_][1][1]);                         \
+            if constexpr (at_ == 2 * 4 + 1) late_test_c(lhit[0], lbest[0], lthr[o_][0]);                   \
+            if constexpr (at_ == 3 * 4 + 2) late_test_a(lbest[0], accL[o_][0][2], accL[o_][1][2]);         \
+            if constexpr (at_ == 3 * 4 + 3) late_test_c(lhit[1], lbest[1], lthr[o_][1]);                   \
+            if constexpr (at_ == 3 * 4 + 0) late_test_a(lbest[1], accL[o_][0][3], accL[o_][1][3]);         \
+            if constexpr (at_ == 4 * 4 + 0) late_test_b(lbest[0], accL[o_][1][2]);                         \
+            if constexpr (at_ == 5 * 4 + 2) late_test_b(lbest[1], accL[o_][1][3]);                         \
+            if constexpr (at_ == 5 * 4 + 3) late_test_c(lhit[2], lbest[0], lthr[o_][2]);                   \
+            if constexpr (at_ == 6 * 4 + 0) late_test_c(lhit[3], lbest[1], lthr[o_][3]);                   \
+            if constexpr (at_ == 6 * 4 + 1) late_or(lany, lhit[0], lhit[1]);                               \
+            if constexpr (at_ == 8 * 4 + 0) late_or(lany2, lhit[2], lhit[3]);                              \
+            if constexpr (at_ == 10 * 4 + 0) late_or(lany, lany, lany2);                                   \
+            if constexpr (steady_ && at_ == 0 * 4 + 1) {          /* the ring slot this tile's DMA pieces fill (TS16_PIECE_M0) */ \
+                asm volatile("" : "+s"(nring[par_]));                                                      \
+                idst = lds0 + nring[par_];                                                                 \
+                asm volatile("" : "+s"(idst));                                                             \
             }                                                                                              \
-            if constexpr (p_ == 3 * NB) late_or(lany, lhit[0], lhit[1]);                                   \
-            if constexpr (p_ == 3 * NB + 1) late_or(lany2, lhit[2], lhit[3]);                              \
-            if constexpr (p_ == 3 * NB + 2) late_or(lany, lany, lany2);                                    \
-            if constexpr (steady_ && p_ == 2 * (kSteps - kA)) {   /* k-step kSteps - kA has fetched the unit's last k-step */ \
-                asm volatile("" : "+s"(noff_l));                  /* (the two additions here, not behind the DMA piece) */ \
-                la_l[0] = lds_base + noff_l + xo[0] + koff;                                                \
-                la_l[1] = lds_base + noff_l + xo[1] + koff;                                                \
+            if constexpr (steady_ && at_ == 4 * (kSteps - kA - 1) + 2) {   /* ... and the slot of the next tile's image */ \
+                asm volatile("" : "+s"(nring[o_]));                                                        \
+                nring[par_] = (nring[o_] + kUnitBytes == (unsigned)dims::kLds) ? 0u : nring[o_] + kUnitBytes; \
+                asm volatile("" : "+s"(nring[par_]));                                                      \
+            }                                                                                              \
+            if constexpr (steady_ && at_ == 4 * (kSteps - kA) + 0) {   /* k-step kSteps - kA has fetched the unit's last k-step */ \
+                asm volatile("" : "+s"(nring[par_]));             /* (the two additions here, not behind the DMA piece) */ \
+                la_l[0] = lds_base + nring[par_] + xo[0] + koff;                                           \
+                la_l[1] = lds_base + nring[par_] + xo[1] + koff;                                           \
                 asm volatile("" : "+v"(la_l[0]), "+v"(la_l[1]));                                           \
                 na[0] = la_l[0]; na[1] = la_l[1];                                                          \
             }                                                                                              \
-            if constexpr (steady_ && p_ == 2 * kSteps - 2) {                                               \
-                poff = soff;                                                                               \
-                soff = noff_l;                                                                             \
-                noff_l = (soff + kUnitBytes == (unsigned)dims::kLds) ? 0u : soff + kUnitBytes;             \
-                s_tile += steady_jump;                                                                     \
-                asm volatile("" : "+s"(poff), "+s"(soff), "+s"(noff_l), "+s"(s_tile));                     \
-            }                                                                                              \
-            if constexpr (steady_ && p_ == 2 * kSteps - 1) {                                               \
+            if constexpr (steady_ && at_ == 4 * (kSteps - 2) + 2) {                                        \
+                asm volatile("" : "+s"(sp_l));                                                             \
                 sp_l += 1;                                                                                 \
                 asm volatile("" : "+s"(sp_l));                                                             \
+            }                                                                                              \
+            if constexpr (steady_ && at_ == 4 * (kSteps - 1) + 2) {   /* behind the tile's last DMA piece */ \
+                asm volatile("" : "+s"(s_tile));                                                           \
+                s_tile += steady_jump;                                                                     \
+                asm volatile("" : "+s"(s_tile));                                                           \
             }                                                                                              \
         }                                                                                                  \
     } while (0)
@@ -658,13 +692,13 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
         TS16_MMA(0, 0, KS_, af[R0_]); TS16_LOAD(0, N_); TS16_THR8(KS_, -2);                                \
         TS16_MMA(1, 0, KS_, af[R0_ + 1]); TS16_LOAD(1, N_); TS16_THR8(KS_, -1);                            \
         if constexpr (NB > 1) {                                                                            \
-            TS16_MMA(0, 1, KS_, af[R0_]); TS16_THR8(KS_, 0);                                               \
+            TS16_MMA(0, 1, KS_, af[R0_]); TS16_THR8(KS_, 0); TS16_PIECE_M0(S_);                            \
             TS16_MMA(1, 1, KS_, af[R0_ + 1]); TS16_THR8(KS_, 1);                                           \
         }                                                                                                  \
         TS16_PIECE(S_);                                                                                    \
         if constexpr (NB > 2) {                                                                            \
-            TS16_MMA(0, 2, KS_, af[R0_]); TS16_THR8(KS_, 2);                                               \
-            TS16_MMA(1, 2, KS_, af[R0_ + 1]); TS16_THR8(KS_, 3);                                           \
+            TS16_MMA(0, 2, KS_, af[R0_]); TS16_THR8(KS_, 2); TS16_LATE(KS_, 2);                            \
+            TS16_MMA(1, 2, KS_, af[R0_ + 1]); TS16_THR8(KS_, 3); TS16_LATE(KS_, 3);                        \
         }                                                                                                  \
         if constexpr (NB > 3) { TS16_MMA(0, 3, KS_, af[R0_]); TS16_LATE(KS_, 0); TS16_MMA(1, 3, KS_, af[R0_ + 1]); TS16_LATE(KS_, 1); } \
     } while (0)
@@ -694,7 +728,14 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
         if constexpr (!kNoMma) {                                                                           \
             /* all but the reads of the kA - 2 k-steps after this one have landed (LDS returns in order); the wait */ \
             /* names this k-step's fragments, so that no consumer of them is placed above it */             \
-            if constexpr (kA == 3) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(af[r0_]), "+v"(af[r0_ + 1])); \
+            /* (late-test screen, steady tiles: the wait as an instruction hipcc sees, behind the statement that names the */ \
+            /* fragments - hipcc pads an asm statement that reads what an earlier one wrote when nothing but asm statements */ \
+            /* lies between the two, and this is the one instruction of a k-step that need not be asm text) */ \
+            if constexpr (kLate && steady_) {                                                              \
+                static_assert(!kLate || kA == 3, "lgkmcnt(2)");                                            \
+                asm volatile("" : "+v"(af[r0_]), "+v"(af[r0_ + 1]));                                       \
+                __builtin_amdgcn_s_waitcnt(0xC27F);                     /* s_waitcnt lgkmcnt(2) */         \
+            } else if constexpr (kA == 3) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(af[r0_]), "+v"(af[r0_ + 1])); \
             else asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(af[r0_]), "+v"(af[r0_ + 1]));                  \
         }                                                                                                  \
         if constexpr (!kNoMma && F32) {                                                                    \
@@ -730,8 +771,8 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
 #define TS16_UNIT_S(UI)                                                                                    \
     do {                                                                                                   \
         constexpr int cui_ = ((UI) + kSlots - 1) % kUnits;                                                 \
-        /* (late-test screen: the next slot's offset is carried, rotated among the MFMAs of the unit before - TS16_LATE) */ \
-        const unsigned noff = kLate ? noff_l : (soff + kUnitBytes == (unsigned)dims::kLds) ? 0u : soff + kUnitBytes; \
+        /* (late-test screen: the slots' offsets are carried by tile parity and advanced among the MFMAs - nring, TS16_LATE) */ \
+        const unsigned noff = kLate ? 0u : (soff + kUnitBytes == (unsigned)dims::kLds) ? 0u : soff + kUnitBytes; \
         unsigned ua[2], na[2];                                                                             \
         if constexpr (!kLate) {                                                                            \
             ua[0] = lds_base + soff + xo[0] + koff; ua[1] = lds_base + soff + xo[1] + koff;                \
@@ -761,7 +802,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
         constexpr bool steady_ = true;                                                                     \
         const unsigned char* isrc = nullptr;                                                               \
         const unsigned char* ssrc = s_tile + cui_ * (kUnitK * 2);       /* wave-uniform: SGPRs */           \
-        const unsigned idst = lds0 + poff;                                                                 \
+        unsigned idst = lds0 + poff;                 /* (late-test screen: set among the MFMAs, TS16_LATE) */ \
         TS16_STEP(UI, 0); TS16_STEP(UI, 1); TS16_STEP(UI, 2); TS16_STEP(UI, 3);                            \
         if constexpr (kUnitSteps > 4) { TS16_STEP(UI, 4 % kUnitSteps); TS16_STEP(UI, 5 % kUnitSteps); TS16_STEP(UI, 6 % kUnitSteps); TS16_STEP(UI, 7 % kUnitSteps); } \
         if constexpr (kUnitSteps > 8) { TS16_STEP(UI, 8 % kUnitSteps); TS16_STEP(UI, 9 % kUnitSteps); TS16_STEP(UI, 10 % kUnitSteps); TS16_STEP(UI, 11 % kUnitSteps); } \
@@ -793,7 +834,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
         const unsigned char* isrc = tile_src + issue_ui * (kUnitK * 2);                                    \
         const unsigned char* ssrc = nullptr;                                                               \
         /* (wave-uniform by construction; with one unit per tile hipcc loses track of that and would hand M0 a VGPR) */ \
-        const unsigned idst = __builtin_amdgcn_readfirstlane(lds0 + issue_slot * kUnitBytes);              \
+        unsigned idst = __builtin_amdgcn_readfirstlane(lds0 + issue_slot * kUnitBytes);                    \
         TS16_STEP(UI, 0); TS16_STEP(UI, 1); TS16_STEP(UI, 2); TS16_STEP(UI, 3);                            \
         if constexpr (kUnitSteps > 4) { TS16_STEP(UI, 4 % kUnitSteps); TS16_STEP(UI, 5 % kUnitSteps); TS16_STEP(UI, 6 % kUnitSteps); TS16_STEP(UI, 7 % kUnitSteps); } \
         if constexpr (kUnitSteps > 8) { TS16_STEP(UI, 8 % kUnitSteps); TS16_STEP(UI, 9 % kUnitSteps); TS16_STEP(UI, 10 % kUnitSteps); TS16_STEP(UI, 11 % kUnitSteps); } \
@@ -824,7 +865,10 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
     const int nt_steady = (a.run == 1 && ahead == kSlots - 1 && !kStamps && nu > ahead) ? (nu - ahead) / kUnits : 0;
     const int64_t steady_jump = tile_bytes * a.tile_stride;
     unsigned soff = 0, poff = (unsigned)(kSlots - 1) * kUnitBytes;
-    unsigned noff_l = (unsigned)kUnitBytes;              // late-test screen: the slot behind soff (TS16_UNIT_S, TS16_LATE)
+    // late-test screen: the ring's slot offsets of its steady tiles, one register per tile parity and nothing rotated (the loop
+    // runs two tiles per trip): entering tile t, nring[t & 1] is the slot unit t - 1 has left - where tile t's DMA pieces go - and
+    // nring[(t & 1) ^ 1] the slot of unit t; tile t makes nring[t & 1] the slot of unit t + 1 among its MFMAs (TS16_LATE)
+    unsigned nring[2] = {(unsigned)(kSlots - 1) * kUnitBytes, 0u};
     unsigned la_l[2] = {lds_base + xo[0] + koff, lds_base + xo[1] + koff};   // ... and its steady tiles' fragment read addresses
     static_assert(!kLate || kUnits == 1, "the late-test screen advances the stream's tile base once per unit");
     // the steady part addresses the stream as (uniform tile base in SGPRs) + (this lane's offset inside a tile); the
@@ -1123,6 +1167,7 @@ __global__ void __launch_bounds__(kMfmaThreads, 1) mfma16_topk_kernel(MfmaArgs a
 #undef TS16_FILL
 #undef TS16_THR8
 #undef TS16_PIECE
+#undef TS16_PIECE_M0
 #undef TS16_ISSUED
     if (I8 && !variant_test_only(VARIANT)) {
         screen_flush_stage(stage8, scnt, lane, s_count, s_cand);

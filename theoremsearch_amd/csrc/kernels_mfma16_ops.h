@@ -86,6 +86,20 @@ __device__ __forceinline__ void lds_dma16s(unsigned voff, const void* sbase, uns
             : "v"(voff), "s"(sbase), "s"(lds_dst), "n"(IMM)
             : "memory");
 }
+// The same piece as two statements with an MFMA between them (the late-test screen's steady tiles): M0 = lds_dst + OFF a gap
+// ahead - the MFMA is the wait state the write of M0 needs in front of the load, and the sum needs no register of its own - then
+// the load alone.  Nothing the compiler makes between the two may write M0 (tests/test_screen8_gaps_isa_cpu.py reads the ISA).
+template <int OFF>
+__device__ __forceinline__ void lds_dma16s_m0(unsigned lds_dst) {
+    if constexpr (OFF == 0) asm volatile("s_mov_b32 m0, %0" : : "s"(lds_dst));
+    else asm volatile("s_add_i32 m0, %0, %1" : : "s"(lds_dst), "n"(OFF) : "scc");
+}
+template <int IMM, bool NT = true>
+__device__ __forceinline__ void lds_dma16s_go(unsigned voff, const void* sbase) {
+    static_assert(IMM >= 0 && IMM < 4096, "13-bit signed immediate");
+    if constexpr (NT) asm volatile("global_load_lds_dwordx4 %0, %1 offset:%2" TS_DMA_POLICY : : "v"(voff), "s"(sbase), "n"(IMM) : "memory");
+    else asm volatile("global_load_lds_dwordx4 %0, %1 offset:%2" : : "v"(voff), "s"(sbase), "n"(IMM) : "memory");
+}
 // Every outstanding fragment read has landed; names the whole ring, so that no copy of a ring register the compiler may
 // need where control flow merges (end of a tile, steady / general branch) is placed above it.
 template <int N>
