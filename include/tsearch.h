@@ -540,6 +540,20 @@ int ts_attention_tiled(int device, const void *qkv, const void *qkv_bias, const 
  * without a single allowed key (a padding token on the left of a causal sequence) comes back as zeros. */
 int ts_attention_gqa(int device, const void *qkv, const int64_t *attention_mask, int32_t batch, int32_t seq, int32_t q_heads,
                     int32_t kv_heads, int32_t head_dim, int causal, void *out, void *stream);
+/* bf16 attention at any length: out = softmax(Q K^T * scale + key mask [+ causal]) V for head sizes 64 / 128 / 256, grouped-query when
+ * kv_heads < q_heads (query head h reads key / value head h / (q_heads / kv_heads)), at any seq from 1 to 32,768 with
+ * batch * q_heads * ceil(seq / 64) <= 2^31 - 1 (TS_ERR_UNSUPPORTED otherwise).  qkv: device bf16 [batch][seq][(q_heads + 2 kv_heads)
+ * * head_dim] - query heads, key heads, value heads of each token, the stacked projection's output (ts_attention_short's
+ * [batch][seq][3][heads][64] is the same memory with q_heads = kv_heads = heads); attention_mask: device int64 [batch][seq], 0 =
+ * padding key, or NULL; out: device bf16 [batch][seq][q_heads * head_dim]; both 16-byte aligned; scale > 0.  Flash-style: a workgroup
+ * per (sequence, query head, 64 queries) walks K and V in chunks of 128 / 64 / 32 keys through LDS; per chunk fp32 scores on the bf16
+ * matrix instructions, a running maximum and sum in fp32 (rescaled at every chunk), the unnormalised probabilities rounded to bf16
+ * (to nearest even) for the second product, fp32 accumulation, one division at the end.  ts_attention_short / ts_attention_gqa
+ * round the normalised probabilities: the entries agree within their rounding bounds, not bit for bit.  A query row without a
+ * single allowed key (a padding token on the left of a causal sequence, a sequence whose mask is all zeros, a whole chunk of
+ * padding in front of it) comes back as zeros. */
+int ts_attention_flash(int device, const void *qkv, const int64_t *attention_mask, int32_t batch, int32_t seq, int32_t q_heads,
+                      int32_t kv_heads, int32_t head_dim, int causal, float scale, void *out, void *stream);
 
 /* The decoder-style encoder the production app embeds with (Qwen/Qwen3-Embedding-0.6B, streamlit_app.py:55;
  * ec2/generate_embeddings/embedders.py:1-4): RMSNorm, rotary positions, grouped-query attention, gated MLP.  Three kernels for

@@ -6,6 +6,7 @@
 
 #include "host.h"
 #include "kernels_attention.h"
+#include "kernels_attention_bf16_tiled.h"
 #include "kernels_attention_f32.h"
 #include "kernels_attention_tiled.h"
 #include "kernels_encoder.h"
@@ -228,6 +229,32 @@ extern "C" int ts_attention_tiled(int device, const void* qkv, const void* qkv_b
             return launch_lds<attention_f32_tiled_kernel<hd, c != 0>, attn_tiled_lds(hd)>(
                 device, p.grid, p.block, p.lds, st, (const float*)qkv, attention_mask, batch, seq, q_heads, kv_heads, scale_log2e,
                 (float*)out, (unsigned short*)pieces, (const float*)qkv_bias);
+        });
+    });
+}
+
+extern "C" int ts_attention_flash(int device, const void* qkv, const int64_t* attention_mask, int32_t batch, int32_t seq, int32_t q_heads,
+                                 int32_t kv_heads, int32_t head_dim, int causal, float scale, void* out, void* stream) {
+    // ts_attention_tiled's checks, in its order, with its texts where they apply (no bias, no pieces)
+    TS_TRY(require({qkv, out}));
+    if (batch < 0 || seq < 1 || q_heads < 1 || kv_heads < 1 || q_heads % kv_heads != 0)
+        return fail(TS_ERR_INVALID, "batch = %d, seq = %d, heads = %d over %d", batch, seq, q_heads, kv_heads);
+    const AttnTiledPlan p = attn_bf16_tiled_plan(batch, seq, q_heads, head_dim);
+    if (!p.ok)
+        return fail(TS_ERR_UNSUPPORTED,
+                    "head size %d / %d tokens: this kernel serves head sizes 64 / 128 / 256 up to %d tokens (and 2^31 - 1 query blocks of %d)",
+                    head_dim, seq, kAttnBf16TiledMaxSeq, kAttnBf16TiledQueries);
+    TS_TRY(aligned16({qkv, out}, "qkv and out must be 16-byte aligned"));
+    if (!(scale > 0.0f)) return fail(TS_ERR_INVALID, "scale must be positive");
+    if (batch == 0) return TS_OK;
+    hipStream_t st;
+    TS_TRY(enter_device(device, stream, &st));
+    const float scale_log2e = scale * 1.4426950408889634f;
+    return dispatch_value<64, 128, 256>(head_dim, [&](auto hd) {
+        return dispatch_value<0, 1>(causal != 0, [&](auto c) {
+            return launch_lds<attention_bf16_tiled_kernel<hd, c != 0>, attn_bf16_tiled_lds(hd)>(
+                device, p.grid, p.block, p.lds, st, (const unsigned short*)qkv, attention_mask, batch, seq, q_heads, kv_heads, scale_log2e,
+                (unsigned short*)out);
         });
     });
 }

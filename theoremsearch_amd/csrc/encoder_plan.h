@@ -164,6 +164,38 @@ inline AttnTiledPlan attn_tiled_plan(int batch, int seq, int q_heads, int head_d
     return p;
 }
 
+// ts_attention_flash (kernels_attention_bf16_tiled.h): bf16 in / out at the same heads and lengths, the same workgroup shape.  The K
+// rows (pitch HD + 8 elements) and the V rows (pitch HD + 16: the transposed reads' conflict-free pitch) of a chunk go through two
+// LDS buffers, 16 KiB of K and 16 KiB of V each before the pads: 68 - 76 KB together, two workgroups share a CU's 160 KiB
+constexpr int kAttnBf16TiledMaxSeq = 32768;
+constexpr int kAttnBf16TiledQueries = 64;
+constexpr int attn_bf16_tiled_chunk(int HD) { return attn_tiled_chunk(HD); }
+constexpr int attn_bf16_tiled_k_pitch(int HD) { return HD + 8; }
+constexpr int attn_bf16_tiled_v_pitch(int HD) { return HD + 16; }
+constexpr int attn_bf16_tiled_lds(int HD) {
+    return 2 * attn_bf16_tiled_chunk(HD) * (attn_bf16_tiled_k_pitch(HD) + attn_bf16_tiled_v_pitch(HD)) * 2;
+}
+static_assert(attn_bf16_tiled_lds(64) <= 80 * 1024 && attn_bf16_tiled_lds(128) <= 80 * 1024 && attn_bf16_tiled_lds(256) <= 80 * 1024,
+              "two workgroups per CU");
+static_assert(attn_bf16_tiled_chunk(64) * 64 * 2 == 16 * 1024 && attn_bf16_tiled_chunk(128) * 128 * 2 == 16 * 1024 &&
+                  attn_bf16_tiled_chunk(256) * 256 * 2 == 16 * 1024,
+              "16 KiB of K and of V per buffer at every head size");
+
+// the launch shape is attn_tiled_plan's: one workgroup per (sequence, query head, block of 64 queries)
+inline AttnTiledPlan attn_bf16_tiled_plan(int batch, int seq, int q_heads, int head_dim) {
+    AttnTiledPlan p = {};
+    if (!(head_dim == 64 || head_dim == 128 || head_dim == 256) || seq < 1 || seq > kAttnBf16TiledMaxSeq || batch < 0 || q_heads < 1) return p;
+    p.tiles = (seq + 15) / 16;
+    p.qblocks = (p.tiles + 3) / 4;
+    const int64_t grid = (int64_t)batch * q_heads * p.qblocks;
+    if (grid > INT32_MAX) return p;
+    p.ok = true;
+    p.grid = (unsigned)grid;
+    p.block = 256;
+    p.lds = attn_bf16_tiled_lds(head_dim);
+    return p;
+}
+
 // ---------------------------------------------------------------------------------------------
 // the other grids
 // ---------------------------------------------------------------------------------------------

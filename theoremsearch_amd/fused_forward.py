@@ -86,6 +86,17 @@ def attention_tiled(qkv: torch.Tensor, key_mask: Optional[torch.Tensor], B: int,
     return ctx, pieces
 
 
+def attention_bf16(qkv: torch.Tensor, key_mask: Optional[torch.Tensor], B: int, S: int, hq: int, hkv: int, hd: int, causal: bool,
+                   scale: float) -> torch.Tensor:
+    """bf16 attention at any length from 1 to 32,768 tokens for heads of 64 / 128 / 256 (``ts_attention_flash``: K and V through LDS in
+    chunks of keys, a workgroup per 64 queries, online softmax), straight from the stacked projection's output ``qkv [B x S x (hq + 2
+    hkv) hd]``: the context, bf16 ``[B x S x hq hd]``."""
+    qkv = qkv.contiguous()
+    ctx = torch.empty((B, S, hq * hd), dtype=torch.bfloat16, device=qkv.device)
+    _ffi.encoder_op("ts_attention_flash", qkv, qkv, key_mask, B, S, hq, hkv, hd, 1 if causal else 0, float(scale), ctx)
+    return ctx
+
+
 # The limits of the library's kernels (csrc/encoder_plan.h; tests/test_encoder_ref_cpu.py holds each against the library's refusals)
 _FLOAT_ATTENTION_MAX_SEQ = {64: 512, 128: 256, 256: 128}      # what fits the CU's LDS as V^T (attn_f32_max_seq)
 _TILED_MAX_SEQ = 32768                                        # ts_attention_tiled: tokens (kAttnTiledMaxSeq)
@@ -98,6 +109,24 @@ _TILED_CHUNK = {64: 128, 128: 64, 256: 32}                    # keys per staged 
 _TILED_ROUTED_MAX_SEQ = {64: _TILED_MAX_SEQ, 128: _TILED_MAX_SEQ, 256: 256}
 _SHORT_HEAD, _SHORT_MAX_SEQ = 64, 128                         # ts_attention_short (bf16): head size, tokens (kAttnRowsMaxSeq)
 _GQA_HEAD, _GQA_MAX_SEQ = 128, 128                            # ts_attention_gqa (bf16): head size, tokens (kAttnGqaRowsMaxSeq)
+_BF16_TILED_MAX_SEQ = 32768                                   # ts_attention_flash: tokens (kAttnBf16TiledMaxSeq)
+_BF16_TILED_CHUNK = {64: 128, 128: 64, 256: 32}               # keys per staged chunk of K and V by head size (attn_bf16_tiled_chunk)
+# Where the bf16 forwards take ts_attention_flash: up to the longest measured length at which it was at least as fast as what the
+# forward did before - torch's attention with its layout copies - there and at every shorter measured length; 0: not routed
+# (tools/attention_bf16_timing.py, profiles/attention_bf16_timing.jsonl, 256 sequences - 64 from 1,024 tokens on -, us per call,
+# ts_attention_flash against torch).  Two tables, because torch runs two different kernels.
+# A batch WITH padding (torch gets the forward's additive mask and leaves its flash kernel):
+# heads of 256 (Gemma3) 20 / 153 at 32 tokens, 99 / 527 at 128, 331 / 1,356 at 256, 1,355 / 4,042 at 512: every measured length;
+# heads of 128 (Qwen3, causal) 265 / 2,097 at 129, 728 / 4,703 at 256, 2,523 / 14,721 at 512, 8,735 / 47,648 at 64 x 2,048: every one;
+# heads of 64 (BERT) 265 / 312 at 192, 448 / 514 at 256, but 930 / 609 at 384: up to 256.
+_BF16_TILED_ROUTED_MAX_SEQ = {64: 256, 128: 2048, 256: 512}
+# A batch WITHOUT padding (no mask: torch's tuned flash kernel, is_causal for Qwen3):
+# heads of 256: 18.4 / 21.2 at 32 tokens in isolation, 30.7 / 29.8 at 64 (and 259 / 186 at 256) - but the encoder-in-loop step at 32
+# tokens (bench.py --workload c5 --encoder gemma --encoder-dtype bf16, same box, three alternating pairs) ran 5.83 ms with it against
+# 5.70 without: the 3 us a layer do not survive the forward, not routed;
+# heads of 128: 202 / 604 at 129, 501 / 719 at 256, 712 / 1,161 at 384, but 1,702 / 1,672 at 512 (5,913 / 2,885 at 64 x 2,048): up to 384;
+# heads of 64: 180 / 152 at 192 already: not routed.
+_BF16_TILED_ROUTED_MAX_SEQ_NO_PADDING = {64: 0, 128: 384, 256: 0}
 _NORM_MAX_VECS = 256                                          # the norm kernels: 16-byte accesses per row (64 lanes x kLnMax)
 
 
@@ -121,6 +150,30 @@ def fp32_attention_kind(x: torch.Tensor, S: int, hd: int) -> Optional[str]:
 
 
 _FP32_ATTENTION = {"float": attention_float, "tiled": attention_tiled}
+
+
+def bf16_attention_kind(x: torch.Tensor, S: int, hd: int, causal: bool, padding: bool = True) -> Optional[str]:
+    """Which of the library's bf16 attentions serves bf16 hidden states ``x`` at ``S`` tokens and head size ``hd``: ``"short"``
+    (ts_attention_short: heads of 64, not causal, at most 128 tokens) and ``"gqa"`` (ts_attention_gqa: heads of 128, causal, at most
+    128 tokens, contiguous hidden states) exactly where the forwards took them before; ``"tiled"`` (ts_attention_flash) where
+    `_BF16_TILED_ROUTED_MAX_SEQ` routes the head size - `_BF16_TILED_ROUTED_MAX_SEQ_NO_PADDING` for a batch the caller knows to
+    have no padding (``padding=False``) -, heads of 64 / 128 past 128 tokens only; ``None`` - torch's attention - otherwise, for
+    another head size, for fp32 or with TS_ENCODER_ATTENTION=0.  TS_ENCODER_FLASH=0 takes out the ``"tiled"`` answer alone: the
+    routing of the commit before ts_attention_flash, for same-box comparisons."""
+    if x.dtype != torch.bfloat16 or os.environ.get("TS_ENCODER_ATTENTION", "1") == "0":
+        return None
+    if hd == _SHORT_HEAD and not causal and S <= _SHORT_MAX_SEQ:
+        return "short"
+    if hd == _GQA_HEAD and causal and S <= _GQA_MAX_SEQ and x.is_contiguous():
+        return "gqa"
+    if hd in (_SHORT_HEAD, _GQA_HEAD) and S <= max(_SHORT_MAX_SEQ, _GQA_MAX_SEQ):
+        return None
+    if os.environ.get("TS_ENCODER_FLASH", "1") == "0":       # same-box A/B against torch's attention (tools/ab_env.sh)
+        return None
+    routed = _BF16_TILED_ROUTED_MAX_SEQ if padding else _BF16_TILED_ROUTED_MAX_SEQ_NO_PADDING
+    if S <= min(routed.get(hd, 0), _BF16_TILED_MAX_SEQ):
+        return "tiled"
+    return None
 
 
 class FusedBertForward:
@@ -243,7 +296,8 @@ class FusedBertForward:
         # padding (every sequence as long as the batch: 50 instead of 60 us per layer for projections + attention)
         # short sequences (one sentence per query: app_showcase_model.py:92) of a bf16 model with 64-wide heads: the attention as
         # ONE wave per (sequence, head), straight from the fused projection to the context layout (``ts_attention_short``)
-        short = x.dtype == torch.bfloat16 and hd == _SHORT_HEAD and S <= _SHORT_MAX_SEQ and os.environ.get("TS_ENCODER_ATTENTION", "1") != "0"
+        kind16 = bf16_attention_kind(x, S, hd, False, not no_padding)        # bf16: ts_attention_short, past 128 tokens ts_attention_flash where routed
+        short = kind16 is not None
         # (the most negative finite value, not -inf: a sequence without a single token would otherwise soften to NaN)
         kind32 = fp32_attention_kind(x, S, hd)               # fp32: the library's fp32 attention (ts_attention_float / _tiled)
         short32 = kind32 is not None
@@ -255,8 +309,10 @@ class FusedBertForward:
             return self._forward_pieces(x, mask, key_mask, kind32, B, S, H, hd)
         for L in self.layers:
             qkv = F.linear(x, L["wqkv"], L["bqkv"])
-            if short:
+            if kind16 == "short":
                 ctx = self._attention(qkv, key_mask, B, S)
+            elif kind16 == "tiled":
+                ctx = attention_bf16(qkv, key_mask, B, S, self.heads, self.heads, hd, False, hd ** -0.5)
             elif short32:
                 ctx = _FP32_ATTENTION[kind32](qkv, key_mask, B, S, self.heads, self.heads, hd, False, hd ** -0.5)[0]
             else:
@@ -412,8 +468,8 @@ class FusedQwen3Forward:
         cos, sin = cos[0].contiguous(), sin[0].contiguous()
         mask = None
         # short sequences in bf16: the library's own causal grouped-query attention (TS_ENCODER_ATTENTION=0 keeps torch's)
-        short = (x.dtype == torch.bfloat16 and self.hd == _GQA_HEAD and S <= _GQA_MAX_SEQ and x.is_contiguous() and
-                 os.environ.get("TS_ENCODER_ATTENTION", "1") != "0")
+        kind16 = bf16_attention_kind(x, S, self.hd, True, not no_padding)    # ts_attention_gqa, past 128 tokens ts_attention_flash where routed
+        short = kind16 is not None
         kind32 = fp32_attention_kind(x, S, self.hd)           # fp32: the library's fp32 attention (causal, grouped-query)
         short32 = kind32 is not None
         key_mask = None if (no_padding or not (short or short32)) else attention_mask.to(torch.int64).contiguous()
@@ -446,7 +502,9 @@ class FusedQwen3Forward:
         for li, L in enumerate(self.layers):
             qkv = F.linear(h, L["wqkv"])
             _ffi.encoder_op("ts_qk_norm_rope", x, qkv, L["qn"], L["kn"], cos, sin, self.eps, B * S, S, self.hq, self.hkv, hd, dt)
-            if short:
+            if kind16 == "tiled":
+                ctx = attention_bf16(qkv, key_mask, B, S, self.hq, self.hkv, hd, True, hd ** -0.5)
+            elif short:
                 # one wave per (sequence, query head), straight from the stacked projection's output (ts_attention_gqa)
                 ctx = torch.empty((B, S, nq), dtype=x.dtype, device=x.device)
                 _ffi.encoder_op("ts_attention_gqa", x, qkv, key_mask, B, S, self.hq, self.hkv, hd, 1, ctx)
@@ -583,9 +641,10 @@ class FusedGemma3Forward:
             tables[lt] = (cos[0].contiguous(), sin[0].contiguous())
         mask = None
         kind32 = fp32_attention_kind(x, S, self.hd)           # fp32: the library's fp32 attention (every key visible, heads of 256)
+        kind16 = bf16_attention_kind(x, S, self.hd, False, not no_padding)   # bf16: ts_attention_flash where routed
         short32 = kind32 is not None
-        key_mask = attention_mask.to(torch.int64).contiguous() if (short32 and not no_padding) else None
-        if not no_padding and not short32:
+        key_mask = attention_mask.to(torch.int64).contiguous() if ((short32 or kind16) and not no_padding) else None
+        if not no_padding and not short32 and not kind16:
             neg = torch.finfo(x.dtype).min
             mask = torch.zeros((B, 1, 1, S), dtype=x.dtype, device=x.device).masked_fill_(~attention_mask[:, None, None, :].to(torch.bool), neg)
         nq, nkv, hd = self.hq * self.hd, self.hkv * self.hd, self.hd
@@ -603,6 +662,8 @@ class FusedGemma3Forward:
             cp = None
             if short32:
                 ctx, cp = _FP32_ATTENTION[kind32](qkv, key_mask, B, S, self.hq, self.hkv, hd, False, self.scaling, want_pieces=pieces, want_context=not pieces)
+            elif kind16 == "tiled":
+                ctx = attention_bf16(qkv, key_mask, B, S, self.hq, self.hkv, hd, False, self.scaling)
             else:
                 q = qkv[..., :nq].view(B, S, self.hq, hd).transpose(1, 2)
                 k = qkv[..., nq:nq + nkv].view(B, S, self.hkv, hd).transpose(1, 2)
