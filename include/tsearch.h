@@ -554,6 +554,18 @@ int ts_attention_gqa(int device, const void *qkv, const int64_t *attention_mask,
  * padding in front of it) comes back as zeros. */
 int ts_attention_flash(int device, const void *qkv, const int64_t *attention_mask, int32_t batch, int32_t seq, int32_t q_heads,
                       int32_t kv_heads, int32_t head_dim, int causal, float scale, void *out, void *stream);
+/* ts_attention_flash / ts_attention_tiled with a sliding window (Gemma3's local layers): query q reads key k only if
+ * |q - k| < window, and the key mask allows k, and k <= q under causal - transformers' convention on both sides; positions are
+ * token indices within the sequence.  Every other argument, layout, refusal and the arithmetic are the parent entry's; window < 1
+ * is TS_ERR_INVALID.  The same kernels walk only the chunks of 128 / 64 / 32 keys (aligned to multiples of the chunk from key 0)
+ * that hold a key some query of the workgroup's 64 may read, so the result is the parent entry's under the equivalent key mask,
+ * bit for bit, in less time; window >= seq hides nothing, launches the parent's kernel and returns its bits.  A query row without a
+ * single allowed key comes back as zeros. */
+int ts_attention_flash_window(int device, const void *qkv, const int64_t *attention_mask, int32_t batch, int32_t seq, int32_t q_heads,
+                              int32_t kv_heads, int32_t head_dim, int causal, int32_t window, float scale, void *out, void *stream);
+int ts_attention_tiled_window(int device, const void *qkv, const void *qkv_bias, const int64_t *attention_mask, int32_t batch,
+                              int32_t seq, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int causal, int32_t window,
+                              float scale, void *out, void *pieces, void *stream);
 
 /* The decoder-style encoder the production app embeds with (Qwen/Qwen3-Embedding-0.6B, streamlit_app.py:55;
  * ec2/generate_embeddings/embedders.py:1-4): RMSNorm, rotary positions, grouped-query attention, gated MLP.  Three kernels for

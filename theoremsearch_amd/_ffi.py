@@ -142,6 +142,10 @@ _SIGNATURES = {
                                    C.c_void_p, C.c_void_p]),
     "ts_attention_flash": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int,
                                     C.c_float, C.c_void_p, C.c_void_p]),
+    "ts_attention_flash_window": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int,
+                                           C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    "ts_attention_tiled_window": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ts_add_rmsnorm":(C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_int32, C.c_int, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
     "ts_qk_norm_rope": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_int32,

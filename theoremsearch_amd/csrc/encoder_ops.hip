@@ -204,9 +204,10 @@ extern "C" int ts_attention_float(int device, const void* qkv, const void* qkv_b
     });
 }
 
-extern "C" int ts_attention_tiled(int device, const void* qkv, const void* qkv_bias, const int64_t* attention_mask, int32_t batch, int32_t seq,
-                                  int32_t q_heads, int32_t kv_heads, int32_t head_dim, int causal, float scale, void* out, void* pieces,
-                                  void* stream) {
+// window = 0: none (ts_attention_tiled).  A window that reaches the sequence's length hides nothing and takes the same instantiation
+static int attention_tiled_impl(int device, const void* qkv, const void* qkv_bias, const int64_t* attention_mask, int32_t batch, int32_t seq,
+                                int32_t q_heads, int32_t kv_heads, int32_t head_dim, int causal, int32_t window, float scale, void* out,
+                                void* pieces, void* stream) {
     // ts_attention_float's checks, in its order, with its texts
     if (!qkv || (!out && !pieces)) return fail(TS_ERR_INVALID, "NULL argument");
     TS_TRY(aligned16({qkv_bias}, "qkv_bias must be 16-byte aligned"));
@@ -226,15 +227,33 @@ extern "C" int ts_attention_tiled(int device, const void* qkv, const void* qkv_b
     const float scale_log2e = scale * 1.4426950408889634f;
     return dispatch_value<64, 128, 256>(head_dim, [&](auto hd) {
         return dispatch_value<0, 1>(causal != 0, [&](auto c) {
-            return launch_lds<attention_f32_tiled_kernel<hd, c != 0>, attn_tiled_lds(hd)>(
-                device, p.grid, p.block, p.lds, st, (const float*)qkv, attention_mask, batch, seq, q_heads, kv_heads, scale_log2e,
-                (float*)out, (unsigned short*)pieces, (const float*)qkv_bias);
+            return dispatch_value<0, 1>(window > 0 && window < seq, [&](auto w) {
+                return launch_lds<attention_f32_tiled_kernel<hd, c != 0, w != 0>, attn_tiled_lds(hd)>(
+                    device, p.grid, p.block, p.lds, st, (const float*)qkv, attention_mask, batch, seq, q_heads, kv_heads, scale_log2e,
+                    (float*)out, (unsigned short*)pieces, (const float*)qkv_bias, (int)window);
+            });
         });
     });
 }
 
-extern "C" int ts_attention_flash(int device, const void* qkv, const int64_t* attention_mask, int32_t batch, int32_t seq, int32_t q_heads,
-                                 int32_t kv_heads, int32_t head_dim, int causal, float scale, void* out, void* stream) {
+extern "C" int ts_attention_tiled(int device, const void* qkv, const void* qkv_bias, const int64_t* attention_mask, int32_t batch, int32_t seq,
+                                  int32_t q_heads, int32_t kv_heads, int32_t head_dim, int causal, float scale, void* out, void* pieces,
+                                  void* stream) {
+    return attention_tiled_impl(device, qkv, qkv_bias, attention_mask, batch, seq, q_heads, kv_heads, head_dim, causal, 0, scale, out, pieces,
+                                stream);
+}
+
+extern "C" int ts_attention_tiled_window(int device, const void* qkv, const void* qkv_bias, const int64_t* attention_mask, int32_t batch,
+                                         int32_t seq, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int causal, int32_t window,
+                                         float scale, void* out, void* pieces, void* stream) {
+    if (window < 1) return fail(TS_ERR_INVALID, "window = %d must be at least 1", window);
+    return attention_tiled_impl(device, qkv, qkv_bias, attention_mask, batch, seq, q_heads, kv_heads, head_dim, causal, window, scale, out,
+                                pieces, stream);
+}
+
+// window = 0: none (ts_attention_flash), as in attention_tiled_impl
+static int attention_flash_impl(int device, const void* qkv, const int64_t* attention_mask, int32_t batch, int32_t seq, int32_t q_heads,
+                                int32_t kv_heads, int32_t head_dim, int causal, int32_t window, float scale, void* out, void* stream) {
     // ts_attention_tiled's checks, in its order, with its texts where they apply (no bias, no pieces)
     TS_TRY(require({qkv, out}));
     if (batch < 0 || seq < 1 || q_heads < 1 || kv_heads < 1 || q_heads % kv_heads != 0)
@@ -252,11 +271,25 @@ extern "C" int ts_attention_flash(int device, const void* qkv, const int64_t* at
     const float scale_log2e = scale * 1.4426950408889634f;
     return dispatch_value<64, 128, 256>(head_dim, [&](auto hd) {
         return dispatch_value<0, 1>(causal != 0, [&](auto c) {
-            return launch_lds<attention_bf16_tiled_kernel<hd, c != 0>, attn_bf16_tiled_lds(hd)>(
-                device, p.grid, p.block, p.lds, st, (const unsigned short*)qkv, attention_mask, batch, seq, q_heads, kv_heads, scale_log2e,
-                (unsigned short*)out);
+            return dispatch_value<0, 1>(window > 0 && window < seq, [&](auto w) {
+                return launch_lds<attention_bf16_tiled_kernel<hd, c != 0, w != 0>, attn_bf16_tiled_lds(hd)>(
+                    device, p.grid, p.block, p.lds, st, (const unsigned short*)qkv, attention_mask, batch, seq, q_heads, kv_heads,
+                    scale_log2e, (unsigned short*)out, (int)window);
+            });
         });
     });
+}
+
+extern "C" int ts_attention_flash(int device, const void* qkv, const int64_t* attention_mask, int32_t batch, int32_t seq, int32_t q_heads,
+                                 int32_t kv_heads, int32_t head_dim, int causal, float scale, void* out, void* stream) {
+    return attention_flash_impl(device, qkv, attention_mask, batch, seq, q_heads, kv_heads, head_dim, causal, 0, scale, out, stream);
+}
+
+extern "C" int ts_attention_flash_window(int device, const void* qkv, const int64_t* attention_mask, int32_t batch, int32_t seq,
+                                        int32_t q_heads, int32_t kv_heads, int32_t head_dim, int causal, int32_t window, float scale,
+                                        void* out, void* stream) {
+    if (window < 1) return fail(TS_ERR_INVALID, "window = %d must be at least 1", window);
+    return attention_flash_impl(device, qkv, attention_mask, batch, seq, q_heads, kv_heads, head_dim, causal, window, scale, out, stream);
 }
 
 extern "C" int ts_attention_gqa(int device, const void* qkv, const int64_t* attention_mask, int32_t batch, int32_t seq, int32_t q_heads,

@@ -196,6 +196,35 @@ inline AttnTiledPlan attn_bf16_tiled_plan(int batch, int seq, int q_heads, int h
     return p;
 }
 
+// ts_attention_flash_window / ts_attention_tiled_window: the same kernels with a sliding window - query q reads key k only if
+// |q - k| < window (transformers' convention on both sides).  What the workgroup of query block `qblk` (64 queries, chunks of C keys
+// aligned to multiples of C from key 0) and its wave `wave` (query tile qi = 4 qblk + wave) walk:
+//   chunks  c_first .. c_first + nchunk - 1: the ones that hold a key some query of the block may read - blockIdx, seq and window
+//           alone, so every wave of the workgroup counts the same barriers;
+//   tiles   [kt_first, kt_end) of 16 keys: the ones that hold a key some query of the WAVE's tile may read; a wave past the
+//           sequence (qi >= T) walks none.  They decide what a wave multiplies between the barriers, never how many it meets.
+// window >= seq hides nothing: the ranges are the unwindowed kernels' (c_first = 0, nchunk = ceil(kt_blk / CT), kt_first = 0).
+struct AttnWindowRange {
+    int c_first, nchunk;    // chunks of the block
+    int kt_first, kt_end;   // key tiles of the wave
+};
+constexpr AttnWindowRange attn_window_range(int seq, int window, bool causal, int C, int qblk, int wave) {
+    const int T = (seq + 15) / 16;
+    const int w1 = (window < seq ? window : seq) - 1;                  // |q - k| < seq always: no overflow at any window
+    const int q_first = 64 * qblk, q_last = q_first + 63 < seq - 1 ? q_first + 63 : seq - 1;
+    const int k_last = causal ? q_last : (q_last + w1 < seq - 1 ? q_last + w1 : seq - 1);
+    AttnWindowRange r = {};
+    r.c_first = (q_first - w1 > 0 ? q_first - w1 : 0) / C;
+    r.nchunk = k_last / C - r.c_first + 1;
+    const int qi = 4 * qblk + wave;
+    if (qi >= T) return r;                                              // kt_first = kt_end = 0
+    const int t_last = 16 * qi + 15 < seq - 1 ? 16 * qi + 15 : seq - 1;
+    const int kt_far = (t_last + w1) / 16 + 1;
+    r.kt_first = (16 * qi - w1 > 0 ? 16 * qi - w1 : 0) / 16;
+    r.kt_end = causal ? qi + 1 : (kt_far < T ? kt_far : T);
+    return r;
+}
+
 // ---------------------------------------------------------------------------------------------
 // the other grids
 // ---------------------------------------------------------------------------------------------

@@ -16,11 +16,19 @@
 //   * grouped-query: query head h reads key / value head h / (HQ / HKV); the heads of a group are neighbours in the grid (head-major
 //     block order), so what one reads of K and V the next finds in the L2.
 //
-// THE BARRIER RULE.  The number of barriers a workgroup executes is a function of blockIdx (and the launch's S) alone: nchunk
-// below.  Every wave stages its share of every chunk and arrives at every chunk's barrier - a wave whose query tile lies past
-// the sequence (a short last block), a wave that has run out of causal keys, a wave whose rows are all padding.  Such a wave
-// walks no key tile (kt_end = 0 or already reached) and stores nothing, but it never returns early, and nothing between the
-// barriers branches around one.  A wave that skips a barrier hangs the workgroup, and with it the machine.
+// THE BARRIER RULE.  The number of barriers a workgroup executes is a function of blockIdx, the launch's S and (WINDOW) its W
+// alone: nchunk below.  Every wave stages its share of every WALKED chunk and arrives at every walked chunk's barrier - a wave
+// whose query tile lies past the sequence (a short last block), a wave that has run out of causal keys, a wave whose rows are
+// all padding, a wave whose window has not begun or has ended.  Such a wave walks no key tile (kt_end = 0 or already reached,
+// kt_first not yet reached) and stores nothing, but it never returns early, and nothing between the barriers branches around
+// one.  A wave that skips a barrier hangs the workgroup, and with it the machine.
+//
+// WINDOW (a compile-time form; W a run-time argument): query q reads key k only if |q - k| < W, and the mask allows k, and
+// k <= q under causal.  The chunks stay aligned to multiples of C from key 0: a block walks chunks c_first .. c_first + nchunk - 1
+// of the unwindowed walk (attn_window_range, encoder_plan.h), a wave multiplies the key tiles [kt_first, kt_end) of them, and
+// the per-key predicate gains the window as one more select.  A chunk or tile that is skipped and one that is walked with
+// every key excluded leave m, l, o with the same bits, so the result is the unwindowed kernel's under the equivalent key mask,
+// bit for bit (tests/test_attention_window_gpu.py).  Without WINDOW nothing of this is compiled in.
 //
 // Arithmetic per (query tile, chunk) - tests/attention_bf16_tiled_common.py models it:
 //   1. fp32 scores of the chunk's keys from the bf16 MFMA (HD / 32 chained k-steps per key tile);
@@ -70,10 +78,11 @@ __device__ __forceinline__ bf16x4 lds_read_tr16(const unsigned short* p) {
 
 // grid = B * HQ * ceil(T / 4), T = ceil(S / 16); 256 threads; dynamic LDS attn_bf16_tiled_lds(HD).  Heads of 64 / 128 keep to the 256
 // registers of two workgroups per CU, as their LDS does; head 256 (32 + 64 registers of Q and O alone) takes one.
-template <int HD, bool CAUSAL>
+// WINDOW: query q reads key k only if |q - k| < W (ts_attention_flash_window; W is not read without it).
+template <int HD, bool CAUSAL, bool WINDOW>
 __global__ void __launch_bounds__(256, (HD <= 128 ? 2 : 1))
 attention_bf16_tiled_kernel(const unsigned short* __restrict__ qkv, const int64_t* __restrict__ mask, int B, int S, int HQ, int HKV,
-                            float scale_log2e, unsigned short* __restrict__ out) {
+                            float scale_log2e, unsigned short* __restrict__ out, int W) {
     constexpr int C = attn_bf16_tiled_chunk(HD);                         // keys per chunk
     constexpr int CT = C / 16;                                           // key tiles per chunk
     constexpr int CS = C / 32;                                           // 32-key steps of the second product per chunk
@@ -102,12 +111,16 @@ attention_bf16_tiled_kernel(const unsigned short* __restrict__ qkv, const int64_
     const unsigned short* vb = base + (int64_t)(HQ + HKV + hk) * HD;
     const int64_t* mrow = mask ? mask + (int64_t)b * S : nullptr;
 
-    // key tiles the BLOCK walks (its last wave's, cut at the sequence) and the chunks that hold them: blockIdx and S alone
+    // key tiles the BLOCK walks (its last wave's, cut at the sequence) and the chunks that hold them: blockIdx and S alone (with a
+    // window: and W - chunks c_first .. c_first + nchunk - 1 of the same walk, attn_window_range)
+    const AttnWindowRange wr = WINDOW ? attn_window_range(S, W, CAUSAL, C, qblk, wave) : AttnWindowRange{};
     const int kt_blk = CAUSAL ? min(4 * qblk + 4, T) : T;
-    const int nchunk = (kt_blk + CT - 1) / CT;
+    const int c_first = WINDOW ? wr.c_first : 0;
+    const int nchunk = WINDOW ? wr.nchunk : (kt_blk + CT - 1) / CT;
     // this wave's query tile; past the sequence (qi >= T) it walks no key tile and stores nothing
     const int qi = 4 * qblk + wave;
-    const int kt_end = qi < T ? (CAUSAL ? qi + 1 : T) : 0;              // key tiles that hold an allowed key
+    const int kt_first = WINDOW ? wr.kt_first : 0;                      // key tiles [kt_first, kt_end) hold an allowed key
+    const int kt_end = WINDOW ? wr.kt_end : (qi < T ? (CAUSAL ? qi + 1 : T) : 0);
     const int qrow = min(16 * qi + r16, S - 1);
     const int qpos = 16 * qi + r16;
 
@@ -137,7 +150,7 @@ attention_bf16_tiled_kernel(const unsigned short* __restrict__ qkv, const int64_
         }
     };
 
-    load_chunk(0);
+    load_chunk(c_first);
     bf16x8 qf[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) qf[ks] = *(const bf16x8*)(qb + (int64_t)qrow * tok + 32 * ks + 8 * g);
@@ -152,15 +165,17 @@ attention_bf16_tiled_kernel(const unsigned short* __restrict__ qkv, const int64_
     for (int c = 0; c < nchunk; ++c) {
         const unsigned short* cK = smem + (c & 1) * BUF;
         const unsigned short* cV = cK + KBUF;
-        if (c + 1 < nchunk) load_chunk(c + 1);                           // (uniform over the workgroup)
-        const int nt = min(CT, kt_end - c * CT);                         // this wave's key tiles inside the chunk: none (<= 0), some or all
-        if (nt > 0) {                                                    // (uniform over the wave; no barrier inside)
-            // S^T = K Q^T: D[key 4 g + r][query r16] of each key tile.  A tile past nt holds no allowed key: not multiplied
+        const int ck = c_first + c;                                      // the chunk's place in the unwindowed walk: keys ck C ..
+        if (c + 1 < nchunk) load_chunk(ck + 1);                          // (uniform over the workgroup)
+        const int nt = min(CT, kt_end - ck * CT);                        // this wave's key tiles inside the chunk: none (<= t0), some or all
+        const int t0 = WINDOW ? max(0, kt_first - ck * CT) : 0;          // ... the first of them (a window's near edge)
+        if (nt > t0) {                                                   // (uniform over the wave; no barrier inside)
+            // S^T = K Q^T: D[key 4 g + r][query r16] of each key tile.  A tile outside [t0, nt) holds no allowed key: not multiplied
             f32x4 sc[CT];
 #pragma unroll
             for (int t = 0; t < CT; ++t) {
                 f32x4 a = {0.f, 0.f, 0.f, 0.f};
-                if (t < nt) {
+                if (t >= t0 && t < nt) {
 #pragma unroll
                     for (int ks = 0; ks < KS; ++ks) {
                         const bf16x8 kf = *(const bf16x8*)(cK + (16 * t + r16) * KP + 32 * ks + 8 * g);
@@ -175,8 +190,9 @@ attention_bf16_tiled_kernel(const unsigned short* __restrict__ qkv, const int64_
             for (int t = 0; t < CT; ++t)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const int key = c * C + 16 * t + 4 * g + r;
+                    const int key = ck * C + 16 * t + 4 * g + r;
                     ok[t][r] = t < nt && key < S && (!CAUSAL || key <= qpos) && (!mrow || mrow[key] != 0);
+                    if constexpr (WINDOW) ok[t][r] = ok[t][r] && t >= t0 && key - qpos < W && qpos - key < W;
                     cmax = fmaxf(cmax, ok[t][r] ? sc[t][r] : -INFINITY);
                 }
             cmax = fmaxf(cmax, __shfl_xor(cmax, 16, 64));
@@ -203,7 +219,7 @@ attention_bf16_tiled_kernel(const unsigned short* __restrict__ qkv, const int64_
             // O^T += V^T P^T, 32 keys a step: B = the two packed score tiles, A = two transposed reads of V's rows in the same key order
 #pragma unroll
             for (int s = 0; s < CS; ++s) {
-                if (2 * s < nt) {
+                if (2 * s < nt && 2 * s + 1 >= t0) {                       // either of the step's two tiles is walked
                     union { uint4 u; bf16x8 v; } pf;
                     pf.u = make_uint4(pack_bf16_hw(sc[2 * s][0], sc[2 * s][1]), pack_bf16_hw(sc[2 * s][2], sc[2 * s][3]),
                                       pack_bf16_hw(sc[2 * s + 1][0], sc[2 * s + 1][1]), pack_bf16_hw(sc[2 * s + 1][2], sc[2 * s + 1][3]));

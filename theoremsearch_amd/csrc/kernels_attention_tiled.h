@@ -13,11 +13,19 @@
 //     the blocks of a (sequence, head) are launched from the far end, the longest first (they stay neighbours in the grid: what
 //     one reads of K and V, the next finds in the L2).
 //
-// THE BARRIER RULE.  The number of barriers a workgroup executes is a function of blockIdx (and the launch's S) alone: nchunk
-// below.  Every wave stages its share of every chunk and arrives at every chunk's barrier - a wave whose query tile lies past
-// the sequence (a short last block), a wave that has run out of causal keys, a wave whose rows are all padding.  Such a wave
-// walks no key tile (kt_end = 0 or already reached) and stores nothing, but it never returns early, and nothing between the
-// barriers branches around one.  A wave that skips a barrier hangs the workgroup, and with it the machine.
+// THE BARRIER RULE.  The number of barriers a workgroup executes is a function of blockIdx, the launch's S and (WINDOW) its W
+// alone: nchunk below.  Every wave stages its share of every WALKED chunk and arrives at every walked chunk's barrier - a wave
+// whose query tile lies past the sequence (a short last block), a wave that has run out of causal keys, a wave whose rows are
+// all padding, a wave whose window has not begun or has ended.  Such a wave walks no key tile (kt_end = 0 or already reached,
+// kt_first not yet reached) and stores nothing, but it never returns early, and nothing between the barriers branches around
+// one.  A wave that skips a barrier hangs the workgroup, and with it the machine.
+//
+// WINDOW (a compile-time form; W a run-time argument): query q reads key k only if |q - k| < W, and the mask allows k, and
+// k <= q under causal.  The chunks stay aligned to multiples of C from key 0: a block walks chunks c_first .. c_first + nchunk - 1
+// of the unwindowed walk (attn_window_range, encoder_plan.h), a wave multiplies the key tiles [kt_first, kt_end) of them, and
+// the per-key predicate gains the window as one more select.  A chunk or tile that is skipped and one that is walked with
+// every key excluded leave m, l, o with the same bits, so the result is the unwindowed kernel's under the equivalent key mask,
+// bit for bit (tests/test_attention_window_gpu.py).  Without WINDOW nothing of this is compiled in.
 //
 // The arithmetic of a (query tile, key tile) step is attention_f32_kernel's, operation for operation, in the same ascending key
 // order: the same two score chains over the same permutation of the head dimension, the same masking to -inf, exp2 with
@@ -44,10 +52,14 @@ namespace ts {
 // grid = B * HQ * ceil(T / 4), T = ceil(S / 16); 256 threads; dynamic LDS attn_tiled_lds(HD).  Heads of 64 / 128 keep to the 256
 // registers of two workgroups per CU, as their LDS does (head 128 takes 286 without the bound; no scratch with it); head 256 needs
 // the whole register file of a SIMD for qf, kf, o and the fragments: one workgroup per CU.
-template <int HD, bool CAUSAL>
+// WINDOW: query q reads key k only if |q - k| < W (ts_attention_tiled_window; W is not read without it).  The unwindowed heads of
+// 128 / 256 sit at 254 / 511 registers, and the run-time first chunk costs more than what is left: with WINDOW they take 256 / 512
+// and 12 / 44 bytes of scratch per lane (causal 36) - staging addresses of load_chunk, written once in front of the chunk loop
+// and reloaded once per chunk, none inside the key-tile loop (profiles/HISTORY.md, Round 26, has what was tried against it).
+template <int HD, bool CAUSAL, bool WINDOW>
 __global__ void __launch_bounds__(256, (HD <= 128 ? 2 : 1))
 attention_f32_tiled_kernel(const float* __restrict__ qkv, const int64_t* __restrict__ mask, int B, int S, int HQ, int HKV, float scale_log2e,
-                           float* __restrict__ out, unsigned short* __restrict__ pieces, const float* __restrict__ bias) {
+                           float* __restrict__ out, unsigned short* __restrict__ pieces, const float* __restrict__ bias, int W) {
     constexpr int C = attn_tiled_chunk(HD);                              // keys per chunk
     constexpr int CT = C / 16;                                           // key tiles per chunk
     constexpr int PP = C + 4;                                            // pitch of a V^T row (floats)
@@ -71,12 +83,16 @@ attention_f32_tiled_kernel(const float* __restrict__ qkv, const int64_t* __restr
     const float* vb = base + (int64_t)(HQ + HKV + hk) * HD;
     const float* vbias = bias ? bias + (int64_t)(HQ + HKV + hk) * HD : nullptr;
 
-    // key tiles the BLOCK walks (its last wave's, cut at the sequence) and the chunks that hold them: blockIdx and S alone
+    // key tiles the BLOCK walks (its last wave's, cut at the sequence) and the chunks that hold them: blockIdx and S alone (with a
+    // window: and W - chunks c_first .. c_first + nchunk - 1 of the same walk, attn_window_range)
+    const AttnWindowRange wr = WINDOW ? attn_window_range(S, W, CAUSAL, C, qblk, __builtin_amdgcn_readfirstlane(wave)) : AttnWindowRange{};
     const int kt_blk = CAUSAL ? min(4 * qblk + 4, T) : T;
-    const int nchunk = (kt_blk + CT - 1) / CT;
+    const int c_first = WINDOW ? wr.c_first : 0;
+    const int nchunk = WINDOW ? wr.nchunk : (kt_blk + CT - 1) / CT;
     // this wave's query tile; past the sequence (qi >= T) it walks no key tile and stores nothing
     const int qi = 4 * qblk + wave;
-    const int kt_end = qi < T ? (CAUSAL ? qi + 1 : T) : 0;              // key tiles that hold an allowed key
+    const int kt_first = WINDOW ? wr.kt_first : 0;                      // key tiles [kt_first, kt_end) hold an allowed key
+    const int kt_end = WINDOW ? wr.kt_end : (qi < T ? (CAUSAL ? qi + 1 : T) : 0);
     const int qrow = min(16 * qi + r16, S - 1);
     const int qpos = 16 * qi + r16;
 
@@ -110,7 +126,7 @@ attention_f32_tiled_kernel(const float* __restrict__ qkv, const int64_t* __restr
         }
     };
 
-    load_chunk(0);
+    load_chunk(c_first);
     float4 qf[KC], kf[KC], kbias[KC];
 #pragma unroll
     for (int s = 0; s < KC; ++s) {
@@ -123,7 +139,7 @@ attention_f32_tiled_kernel(const float* __restrict__ qkv, const int64_t* __restr
         }
     }
     {
-        const int krow = min(r16, S - 1);
+        const int krow = min(16 * kt_first + r16, S - 1);
 #pragma unroll
         for (int s = 0; s < KC; ++s) kf[s] = *(const float4*)(kb + (int64_t)krow * tok + 16 * s + 4 * g);
     }
@@ -137,9 +153,10 @@ attention_f32_tiled_kernel(const float* __restrict__ qkv, const int64_t* __restr
 #pragma unroll 1
     for (int c = 0; c < nchunk; ++c) {
         const float* cur = sVT + (c & 1) * BUF;
-        if (c + 1 < nchunk) load_chunk(c + 1);                           // (uniform over the workgroup)
-        const int kj_end = min((c + 1) * CT, kt_end);                    // this wave's key tiles inside the chunk: none, some or all
-        for (int kj = c * CT; kj < kj_end; ++kj) {
+        const int ck = c_first + c;                                      // the chunk's place in the unwindowed walk: keys ck C ..
+        if (c + 1 < nchunk) load_chunk(ck + 1);                          // (uniform over the workgroup)
+        const int kj_end = min((ck + 1) * CT, kt_end);                   // this wave's key tiles inside the chunk: none, some or all
+        for (int kj = WINDOW ? max(ck * CT, kt_first) : ck * CT; kj < kj_end; ++kj) {
             // scores of this tile: two accumulator chains (a dependent 16x16x4 MFMA waits 40 cycles, an independent one 32)
             f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
             if (bias) {
@@ -166,12 +183,14 @@ attention_f32_tiled_kernel(const float* __restrict__ qkv, const int64_t* __restr
             }
             float4 vf[KC];
 #pragma unroll
-            for (int dj = 0; dj < KC; ++dj) vf[dj] = *(const float4*)(cur + (16 * dj + r16) * PP + 16 * (kj - c * CT) + 4 * g);
+            for (int dj = 0; dj < KC; ++dj) vf[dj] = *(const float4*)(cur + (16 * dj + r16) * PP + 16 * (kj - ck * CT) + 4 * g);
             float sc[4], tmax = -INFINITY;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int key = 16 * kj + 4 * g + r;
-                const bool ok = key < S && (!mask || mask[(int64_t)b * S + key] != 0) && (!CAUSAL || key <= qpos);
+                bool ok = key < S && (!mask || mask[(int64_t)b * S + key] != 0) && (!CAUSAL || key <= qpos);
+                // key - qpos < W && qpos - key < W as one unsigned comparison (W < S here: no overflow)
+                if constexpr (WINDOW) ok = ok && (unsigned)(key - qpos + W - 1) < (unsigned)(2 * W - 1);
                 sc[r] = ok ? a0[r] + a1[r] : -INFINITY;
                 tmax = fmaxf(tmax, sc[r]);
             }

@@ -76,24 +76,34 @@ def attention_float(qkv: torch.Tensor, key_mask: Optional[torch.Tensor], B: int,
 
 
 def attention_tiled(qkv: torch.Tensor, key_mask: Optional[torch.Tensor], B: int, S: int, hq: int, hkv: int, hd: int, causal: bool,
-                    scale: float, want_pieces: bool = False, bias: Optional[torch.Tensor] = None, want_context: bool = True):
+                    scale: float, want_pieces: bool = False, bias: Optional[torch.Tensor] = None, want_context: bool = True,
+                    window: int = 0):
     """`attention_float` at any length from 1 to 32,768 tokens (``ts_attention_tiled``: V^T through LDS in chunks of keys, a
-    workgroup per 64 queries): the same arguments, the same return value, the same bits where both serve a shape."""
+    workgroup per 64 queries): the same arguments, the same return value, the same bits where both serve a shape.  ``window`` > 0:
+    a query reads the keys at a distance below ``window`` only (``ts_attention_tiled_window``, which walks only their chunks)."""
     qkv = qkv.contiguous()
     ctx = torch.empty((B, S, hq * hd), dtype=torch.float32, device=qkv.device) if (want_context or not want_pieces) else None
     pieces = torch.empty((B * S, 3 * hq * hd), dtype=torch.bfloat16, device=qkv.device) if want_pieces else None
-    _ffi.encoder_op("ts_attention_tiled", qkv, qkv, bias, key_mask, B, S, hq, hkv, hd, 1 if causal else 0, float(scale), ctx, pieces)
+    if window:
+        _ffi.encoder_op("ts_attention_tiled_window", qkv, qkv, bias, key_mask, B, S, hq, hkv, hd, 1 if causal else 0, int(window),
+                        float(scale), ctx, pieces)
+    else:
+        _ffi.encoder_op("ts_attention_tiled", qkv, qkv, bias, key_mask, B, S, hq, hkv, hd, 1 if causal else 0, float(scale), ctx, pieces)
     return ctx, pieces
 
 
 def attention_bf16(qkv: torch.Tensor, key_mask: Optional[torch.Tensor], B: int, S: int, hq: int, hkv: int, hd: int, causal: bool,
-                   scale: float) -> torch.Tensor:
+                   scale: float, window: int = 0) -> torch.Tensor:
     """bf16 attention at any length from 1 to 32,768 tokens for heads of 64 / 128 / 256 (``ts_attention_flash``: K and V through LDS in
     chunks of keys, a workgroup per 64 queries, online softmax), straight from the stacked projection's output ``qkv [B x S x (hq + 2
-    hkv) hd]``: the context, bf16 ``[B x S x hq hd]``."""
+    hkv) hd]``: the context, bf16 ``[B x S x hq hd]``.  ``window`` > 0: a query reads the keys at a distance below ``window`` only
+    (``ts_attention_flash_window``, which walks only their chunks)."""
     qkv = qkv.contiguous()
     ctx = torch.empty((B, S, hq * hd), dtype=torch.bfloat16, device=qkv.device)
-    _ffi.encoder_op("ts_attention_flash", qkv, qkv, key_mask, B, S, hq, hkv, hd, 1 if causal else 0, float(scale), ctx)
+    if window:
+        _ffi.encoder_op("ts_attention_flash_window", qkv, qkv, key_mask, B, S, hq, hkv, hd, 1 if causal else 0, int(window), float(scale), ctx)
+    else:
+        _ffi.encoder_op("ts_attention_flash", qkv, qkv, key_mask, B, S, hq, hkv, hd, 1 if causal else 0, float(scale), ctx)
     return ctx
 
 
@@ -127,6 +137,20 @@ _BF16_TILED_ROUTED_MAX_SEQ = {64: 256, 128: 2048, 256: 512}
 # heads of 128: 202 / 604 at 129, 501 / 719 at 256, 712 / 1,161 at 384, but 1,702 / 1,672 at 512 (5,913 / 2,885 at 64 x 2,048): up to 384;
 # heads of 64: 180 / 152 at 192 already: not routed.
 _BF16_TILED_ROUTED_MAX_SEQ_NO_PADDING = {64: 0, 128: 384, 256: 0}
+# Where a sliding layer of FusedGemma3Forward (S > window) takes the windowed entries, by head size: up to the longest measured
+# length at which the entry was at least as fast as what the forward runs otherwise - torch's attention with the additive mask of
+# padding and window and its layout copies - there and at every shorter measured length; 0: not routed
+# (tools/attention_window_timing.py, profiles/attention_window_timing.jsonl: heads of 256, 3 / 1 heads, window 257, 256 sequences -
+# 64 from 1,024 tokens on -, us per call with padding, windowed entry / unwindowed parent entry / torch;
+# tests/test_attention_window_timing_cpu.py derives both tables from the rows).  One table per type: torch gets an additive mask
+# with padding and without, and runs the same kernel (1,893 and 1,885 us at 258 tokens).
+# bf16 (ts_attention_flash_window): 454 / 429 / 1,893 at 258 tokens, 711 / 785 / 2,627 at 384, 1,251 / 1,361 / 4,092 at 512,
+# 698 / 1,163 / 3,462 at 64 x 1,024, 1,442 / 4,782 / 12,353 at 64 x 2,048: every measured length.
+# fp32 (ts_attention_tiled_window): 1,632 / 1,630 / 1,706 at 258 tokens, but 2,664 / 3,107 / 2,298 at 384 and 4,860 / 5,506 / 3,613 at
+# 512: up to 258.  (It wins again at 64 x 1,024 - 2,711 / 5,312 / 3,144 - and 64 x 2,048 - 5,409 / 20,552 / 11,460 -, where the window
+# leaves a half and a quarter of the chunks; the rule does not count a win behind a loss.)
+_WINDOW_ROUTED_MAX_SEQ_BF16 = {256: 2048}
+_WINDOW_ROUTED_MAX_SEQ_F32 = {256: 258}
 _NORM_MAX_VECS = 256                                          # the norm kernels: 16-byte accesses per row (64 lanes x kLnMax)
 
 
@@ -535,10 +559,14 @@ class FusedGemma3Forward:
       sliding and full attention layers have their own cos / sin tables);
     * ``gelu_tanh(gate) * up`` as ONE kernel (``ts_geglu``).
 
-    The attention (heads of 256, grouped-query, every key visible: sequences shorter than the sliding window) is the library's in
-    fp32 - ``ts_attention_float`` up to 128 tokens, ``ts_attention_tiled`` up to 256 (`fp32_attention_kind`) - and
-    ``scaled_dot_product_attention`` otherwise.  Same weights, same order of operations, the roundings of the modules replaced.  Longer sequences
-    than the sliding window take the model's own forward."""
+    The attention (heads of 256, grouped-query) of a full-attention layer, and of a sliding layer whose window hides nothing
+    (``S <= sliding_window``), is the library's in fp32 - ``ts_attention_float`` up to 128 tokens, ``ts_attention_tiled`` up to 256
+    (`fp32_attention_kind`) -, ``ts_attention_flash`` in bf16 where `bf16_attention_kind` routes it, and
+    ``scaled_dot_product_attention`` otherwise.  A sliding layer of a longer sequence (a query reads the keys at a distance below
+    ``sliding_window``: 257 for ``embeddinggemma-300m``) takes ``ts_attention_flash_window`` / ``ts_attention_tiled_window`` where
+    `_WINDOW_ROUTED_MAX_SEQ_BF16` / `_WINDOW_ROUTED_MAX_SEQ_F32` route its length, and ``scaled_dot_product_attention`` with one
+    additive mask of the padding and the window, built once per forward, otherwise.  Same weights, same order of operations, the
+    roundings of the modules replaced, at every length: the forward never hands a batch back to the model's own."""
 
     def __init__(self, model):
         cfg = model.config
@@ -603,7 +631,8 @@ class FusedGemma3Forward:
         return (new_res if new_res is not None else x), out
 
     def _sdpa(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor]) -> torch.Tensor:
-        """torch's attention (sequences past 128 tokens, bf16): every key visible, grouped-query, Gemma3's own scaling."""
+        """torch's attention (where no kernel of the library is routed): the keys the additive ``mask`` leaves - every key, the
+        real tokens, or those within a sliding layer's window -, grouped-query, Gemma3's own scaling."""
         F = torch.nn.functional
         if self._gqa_native:
             try:
@@ -628,8 +657,6 @@ class FusedGemma3Forward:
                  no_padding: bool = False):
         F = torch.nn.functional
         B, S = input_ids.shape
-        if S >= int(self.cfg.sliding_window):                        # the sliding layers would hide keys: the model's own masks
-            return self.model(input_ids=input_ids, attention_mask=attention_mask).last_hidden_state
         self._refresh()
         m = self.model
         x = m.embed_tokens(input_ids).contiguous()                    # scaled by sqrt(hidden) in the storage type, as the module does
@@ -643,10 +670,21 @@ class FusedGemma3Forward:
         kind32 = fp32_attention_kind(x, S, self.hd)           # fp32: the library's fp32 attention (every key visible, heads of 256)
         kind16 = bf16_attention_kind(x, S, self.hd, False, not no_padding)   # bf16: ts_attention_flash where routed
         short32 = kind32 is not None
-        key_mask = attention_mask.to(torch.int64).contiguous() if ((short32 or kind16) and not no_padding) else None
+        # the sliding layers hide keys once S > window: the windowed entries where routed, else torch's attention with ONE additive
+        # mask of padding and window for all of them
+        window = int(self.cfg.sliding_window or 0)
+        windowed = 0 < window < S and any(L["type"] == "sliding_attention" for L in self.layers)
+        win_routed = _WINDOW_ROUTED_MAX_SEQ_BF16 if x.dtype == torch.bfloat16 else _WINDOW_ROUTED_MAX_SEQ_F32
+        win_lib = windowed and S <= win_routed.get(self.hd, 0) and os.environ.get("TS_ENCODER_ATTENTION", "1") != "0"
+        key_mask = attention_mask.to(torch.int64).contiguous() if ((short32 or kind16 or win_lib) and not no_padding) else None
+        neg = torch.finfo(x.dtype).min
         if not no_padding and not short32 and not kind16:
-            neg = torch.finfo(x.dtype).min
             mask = torch.zeros((B, 1, 1, S), dtype=x.dtype, device=x.device).masked_fill_(~attention_mask[:, None, None, :].to(torch.bool), neg)
+        wmask = None
+        if windowed and not win_lib:
+            far = (pos[0, :, None] - pos[0, None, :]).abs() >= window        # [S x S]: |q - k| >= window
+            hidden = far[None, None] if no_padding else far[None, None] | ~attention_mask[:, None, None, :].to(torch.bool)
+            wmask = torch.zeros(hidden.shape, dtype=x.dtype, device=x.device).masked_fill_(hidden, neg)
         nq, nkv, hd = self.hq * self.hd, self.hkv * self.hd, self.hd
         pieces = self.pieces and x.dtype == torch.float32 and "wo_p" in self.layers[0]
         H = x.shape[-1]
@@ -660,7 +698,18 @@ class FusedGemma3Forward:
             cos, sin = tables[L["type"]]
             _ffi.encoder_op("ts_gemma_qk_norm_rope", x, qkv, L["qn"], L["kn"], cos, sin, self.eps, B * S, S, self.hq, self.hkv, hd, dt)
             cp = None
-            if short32:
+            win = windowed and L["type"] == "sliding_attention"
+            if win and win_lib and dt:
+                ctx = attention_bf16(qkv, key_mask, B, S, self.hq, self.hkv, hd, False, self.scaling, window=window)
+            elif win and win_lib:
+                ctx, cp = attention_tiled(qkv, key_mask, B, S, self.hq, self.hkv, hd, False, self.scaling, want_pieces=pieces,
+                                          want_context=not pieces, window=window)
+            elif win:
+                q = qkv[..., :nq].view(B, S, self.hq, hd).transpose(1, 2)
+                k = qkv[..., nq:nq + nkv].view(B, S, self.hkv, hd).transpose(1, 2)
+                v = qkv[..., nq + nkv:].view(B, S, self.hkv, hd).transpose(1, 2)
+                ctx = self._sdpa(q, k, v, wmask).transpose(1, 2).reshape(B, S, nq)
+            elif short32:
                 ctx, cp = _FP32_ATTENTION[kind32](qkv, key_mask, B, S, self.hq, self.hkv, hd, False, self.scaling, want_pieces=pieces, want_context=not pieces)
             elif kind16 == "tiled":
                 ctx = attention_bf16(qkv, key_mask, B, S, self.hq, self.hkv, hd, False, self.scaling)
