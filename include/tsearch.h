@@ -67,8 +67,9 @@ extern "C" {
 #define TS_ALGO_SCAN 1 /* streaming dot-product scan with per-wave running top-k (any dtype, any d) */
 /* MFMA contraction with thresholded candidate selection, bf16 or fp32 index: d = 384, 512, 768 or 1024 on the hand-laid kernels;
  * any other d that is a multiple of 64, from 128 up to a 4,096-byte row (bf16 d <= 2048, fp32 d <= 960), on the general-width
- * kernel (256 queries per pass; only under the default two-level search, and for fp32 not with TS_MFMA_F32=0, which takes
- * fp32 indexes off the matrix path at every width).  Other widths: TS_ERR_UNSUPPORTED.  Scores are reproducible per width and storage type: the
+ * kernel; wider rows whose d is a multiple of 256, up to a 16,384-byte row (bf16 d = 2304 .. 8192, fp32 d = 1280 .. 4096), on
+ * the k-chunked kernel (both: 256 queries per pass; only under the default two-level search, and for fp32 not with
+ * TS_MFMA_F32=0, which takes fp32 indexes off the matrix path at every width).  Other widths: TS_ERR_UNSUPPORTED.  Scores are reproducible per width and storage type: the
  * same (query, row) pair gets the same score bits whatever the batch size and the launch shape. */
 #define TS_ALGO_MFMA 2
 
@@ -149,7 +150,9 @@ int ts_index_info(const ts_index *ix, int64_t *n, int32_t *d, int32_t *dtype, in
  * Contract of all of them: ids and score bits of every search are identical with the option on and off, for every batch size and
  * whichever form the unscreened pass would take (TS_MFMA_PAIR, TS_MFMA_GRID at bf16 d = 1024) - for every query that neither
  * call sent to the exact re-run, which has the scan's arithmetic either way; views and attached rows are never screened.
- * ts_search_stats.screened tells which pass a call ran. */
+ * ts_search_stats.screened tells which pass a call ran.
+ * "TS_MFMA_WIDE_SERIAL" (default 0): 1 = the k-chunked kernel (rows wider than 4,096 bytes) runs the plain form of its chunk
+ * loop, two barriers per k-chunk instead of one: the timing partner of the default; ids and score bits are the same. */
 int ts_index_set_option(ts_index *ix, const char *name, int32_t value);
 int ts_index_reset_option(ts_index *ix, const char *name);
 
@@ -191,7 +194,9 @@ int ts_index_download(ts_index *ix, void *host_rows, int64_t row0, int64_t nrows
  * A batch (more than 4 queries; when k > 64, where the scan serves one query per pass, more than 1 - more than 2 on the fp32
  * general-width kernel: measured) over at least 16,384
  * rows runs on the matrix path where the index has one: bf16 / fp32 at d = 384, 512, 768, 1024 (hand-laid kernels), and at
- * every other multiple of 64 from 128 up to a 4,096-byte row (the general-width kernel); anything else on the streaming scan,
+ * every other multiple of 64 from 128 up to a 4,096-byte row (the general-width kernel), and at every multiple of 256 with a
+ * wider row of up to 16,384 bytes (the k-chunked kernel: bf16 d = 2304 .. 8192, fp32 d = 1280 .. 4096).  The same holds for
+ * ts_search_ex, ts_search_filtered*, ts_search_rowset and ts_search_biased_ex.  Anything else runs on the streaming scan,
  * four queries per pass.  Either way the answer is the exact top k; matrix-path scores are reproducible per width and storage
  * type (the same score bits for a (query, row) pair in any batch) and may differ from the scan's in the last bits.
  */
@@ -265,7 +270,9 @@ int ts_search_biased(ts_index *ix, const void *queries, int q_dtype, int q_on_de
  *   TS_ALGO_MFMA  the biased matrix search: a dense threshold sample, then ONE pass of the general-width matrix kernel per 256
  *                 queries with fmaf(weight, bias[row], score) in its epilogue - that value is tested against the query's
  *                 threshold, written into the key and returned.  Served: a bf16 or fp32 index whose width is a multiple of 64
- *                 from 128 up to a 4,096-byte row (bf16 d <= 2048, fp32 d <= 1024; 384 / 512 / 768 / 1024 included).
+ *                 from 128 up to a 4,096-byte row (bf16 d <= 2048, fp32 d <= 1024; 384 / 512 / 768 / 1024 included), or a
+ *                 multiple of 256 with a wider row of up to 16,384 bytes (bf16 d = 2304 .. 8192, fp32 d = 1280 .. 4096: the
+ *                 k-chunked kernel with the same epilogue).
  *                 TS_ERR_UNSUPPORTED for a subset index, any other width, without the two-level search (TS_MFMA_STAT=0 or
  *                 TS_MFMA_SAMPLE=0), an fp32 index with TS_MFMA_F32=0, a mask in device memory, or a host mask too sparse by
  *                 the rule of ts_search_filtered_ex (fewer than a tenth of the rows, or a batch the matrix path does not take).

@@ -24,6 +24,7 @@
 #include "scan_plan.h"
 #include "anyd_plan.h"
 #include "bias_plan.h"
+#include "wide_plan.h"
 #include "encoder_plan.h"
 #include "meta_plan.h"
 #include "dev_array.h"
@@ -108,14 +109,14 @@ enum Knob {
     K_MFMA_MIN_RANK, K_MFMA_VARIANT, K_MFMA_GROUPS, K_MFMA_GRID, K_MFMA_STAT, K_MFMA_STAT_CANDS, K_MFMA_TAIL_FIT,
     K_MFMA_NO_IDLE, K_MFMA_AHEAD, K_MFMA_TARGET_CANDS, K_MFMA_FIRST_ROWS, K_MFMA_TARGET_SPARSE, K_MFMA_RUN,
     K_MFMA_MIN_ROWS, K_MFMA_SHAPE, K_MFMA_F32, K_SCAN_GENERIC, K_SCAN_MAX_QUERIES, K_MFMA_BALANCE, K_PROBE_SPREAD, K_MFMA_SAMPLE,
-    K_MFMA_PAIR, K_MFMA_PAIR_LAG, K_MFMA_SCREEN, K_MFMA_SCREEN_WIDE, K_MFMA_SCREEN_F32, K_MFMA_SCREEN_LATE, K_COUNT
+    K_MFMA_PAIR, K_MFMA_PAIR_LAG, K_MFMA_SCREEN, K_MFMA_SCREEN_WIDE, K_MFMA_SCREEN_F32, K_MFMA_SCREEN_LATE, K_MFMA_WIDE_SERIAL, K_COUNT
 };
 inline const char* const kKnobNames[K_COUNT] = {
     "TS_MFMA_MIN_RANK", "TS_MFMA_VARIANT", "TS_MFMA_GROUPS", "TS_MFMA_GRID", "TS_MFMA_STAT", "TS_MFMA_STAT_CANDS",
     "TS_MFMA_TAIL_FIT", "TS_MFMA_NO_IDLE", "TS_MFMA_AHEAD", "TS_MFMA_TARGET_CANDS", "TS_MFMA_FIRST_ROWS",
     "TS_MFMA_TARGET_SPARSE", "TS_MFMA_RUN", "TS_MFMA_MIN_ROWS", "TS_MFMA_SHAPE", "TS_MFMA_F32", "TS_SCAN_GENERIC",
     "TS_SCAN_MAX_QUERIES", "TS_MFMA_BALANCE", "TS_PROBE_SPREAD", "TS_MFMA_SAMPLE", "TS_MFMA_PAIR", "TS_MFMA_PAIR_LAG",
-    "TS_MFMA_SCREEN", "TS_MFMA_SCREEN_WIDE", "TS_MFMA_SCREEN_F32", "TS_MFMA_SCREEN_LATE"};
+    "TS_MFMA_SCREEN", "TS_MFMA_SCREEN_WIDE", "TS_MFMA_SCREEN_F32", "TS_MFMA_SCREEN_LATE", "TS_MFMA_WIDE_SERIAL"};
 struct Knobs {
     int v[K_COUNT];
     bool set[K_COUNT];
@@ -366,8 +367,14 @@ static inline bool bias_index(const ts_index* ix) {
     if (ix->dtype == TS_F32 && ix->knobs.get(K_MFMA_F32, 16) == 0) return false;
     return ix->ld == ix->d && ix->n >= 1 && bias_served(ix->dtype, ix->d, two_level_search(ix));
 }
+// wider rows, d % 256 == 0 up to a 16,384-byte row: the k-chunked kernel (kernels_mfma_wide.h; wide_plan.h holds the rule), under
+// the same conditions.  Disjoint from anyd_index, bias_index and the hand-laid widths; it serves the biased search too
+static inline bool wide_index(const ts_index* ix) {
+    if (ix->dtype == TS_F32 && ix->knobs.get(K_MFMA_F32, 16) == 0) return false;
+    return ix->ld == ix->d && wide_served(ix->dtype, ix->d, two_level_search(ix));
+}
 static inline bool mfma_index(const ts_index* ix) {
-    if (anyd_index(ix)) return true;
+    if (anyd_index(ix) || wide_index(ix)) return true;
     if (ix->dtype == TS_BF16) return mfma_dim(ix->d);
     if (ix->knobs.get(K_MFMA_F32, 16) == 0) return false;
     return ix->d == 768 || ix->d == 1024 || ((ix->d == 384 || ix->d == 512) && two_level_search(ix));
@@ -392,7 +399,7 @@ static inline bool use_shape16(const ts_index* ix) {
 // ---------------------------------------------------------------------------------------------
 // functions one translation unit defines for the others
 // ---------------------------------------------------------------------------------------------
-namespace ts { struct MfmaArgs; }
+namespace ts { struct MfmaArgs; struct SampleArgs; }
 // index.hip: normalise / convert / pad rows (uploads, query preparation)
 int prep_dispatch(int src_dtype, int dst_dtype, bool normalize, const void* src, int64_t src_ld, void* dst, float* f32copy,
                   int64_t ld, int d, int64_t nrows, int64_t rows_total, hipStream_t st);
@@ -446,5 +453,9 @@ int launch_pass_mfma_anyd(const ts_index* ix, int grid, hipStream_t st, const ts
 // launch_mfma_anyd_biased.hip: the same pass with the call's bias term in the epilogue (ix->active_bias, active_bias_w), at any
 // width of bias_index
 int launch_pass_mfma_anyd_biased(const ts_index* ix, int grid, hipStream_t st, const ts::MfmaArgs& a);
+// launch_mfma_wide.hip: the same two passes and the threshold sample of an index the k-chunked kernels serve (wide_index)
+int launch_pass_mfma_wide(const ts_index* ix, int grid, hipStream_t st, const ts::MfmaArgs& a);
+int launch_pass_mfma_wide_biased(const ts_index* ix, int grid, hipStream_t st, const ts::MfmaArgs& a);
+int launch_sample_wide(const ts_index* ix, dim3 grid, hipStream_t st, const ts::SampleArgs& sa);
 int launch_pass_mfma32(int dev, int d, int groups, bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);
 int launch_pass_mfma32_f32(int dev, bool full_pass, int variant, int grid, hipStream_t st, const ts::MfmaArgs& a);

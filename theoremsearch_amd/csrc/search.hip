@@ -216,7 +216,8 @@ static int search_validate(const ts_index* ix, const void* queries, int q_dtype,
     if (algo < TS_ALGO_AUTO || algo > TS_ALGO_MFMA) return fail(TS_ERR_INVALID, "algo %d", algo);
     if (algo == TS_ALGO_MFMA && !(mfma_index(ix) && ix->n >= 1))
         return fail(TS_ERR_UNSUPPORTED, "the MFMA path needs a bf16 or fp32 index with d = 384, 512, 768 or 1024, or with any other multiple of 64 "
-                                        "from 128 up to a 4,096-byte row (bf16 d <= 2048, fp32 d <= 960) under the default two-level search");
+                                        "from 128 up to a 4,096-byte row (bf16 d <= 2048, fp32 d <= 960) or any multiple of 256 from there up to a "
+                                        "16,384-byte row (bf16 d = 2304 .. 8192, fp32 d = 1280 .. 4096) under the default two-level search");
     return TS_OK;
 }
 
@@ -256,10 +257,12 @@ static int search_choose(ts_index* ix, int algo, int nq, int k, const BiasSpec* 
     in.mfma_min_rows = ix->knobs.get(K_MFMA_MIN_ROWS, 16384);
     // the general-width kernel's limit comes from its own measurement (anyd_plan.h)
     const bool anyd = anyd_index(ix);
-    in.scan_max_queries = ix->knobs.get(K_SCAN_MAX_QUERIES, anyd ? anyd_scan_max_queries(ix->dtype) : 4);
+    const bool wide = wide_index(ix);                      // ... and the k-chunked kernel's from wide_plan.h
+    in.scan_max_queries = ix->knobs.get(K_SCAN_MAX_QUERIES, anyd ? anyd_scan_max_queries(ix->dtype) : wide ? wide_scan_max_queries(ix->dtype) : 4);
     // k > 64 on the fp32 general-width kernel: choose_algo() lets every batch of two through, the measured limit is two
     // (anyd_scan_limit); the kernel is then not offered to AUTO.  TS_SCAN_MAX_QUERIES, when set, is the only limit.
     if (anyd && algo == TS_ALGO_AUTO && !ix->knobs.set[K_SCAN_MAX_QUERIES] && nq <= anyd_scan_limit(ix->dtype, k)) in.mfma_ok = false;
+    if (wide && algo == TS_ALGO_AUTO && !ix->knobs.set[K_SCAN_MAX_QUERIES] && nq <= wide_scan_limit(ix->dtype, k)) in.mfma_ok = false;
     in.bias = bias != nullptr;
     in.subset = ix->id_map != nullptr;
     in.mask = row_mask != nullptr;
@@ -270,10 +273,13 @@ static int search_choose(ts_index* ix, int algo, int nq, int k, const BiasSpec* 
     if (bias && bias->ex) {
         // ts_search_biased_ex decides with its own rule (bias_plan.h): the biased general-width pass serves the hand-laid
         // widths too, and its AUTO limit is its own
-        const bool served = bias_index(ix);
+        // (bias_served is the narrower widths' rule; at the k-chunked widths the biased pass is mfma_wide_kernel's)
+        const bool served = bias_index(ix) || (wide && ix->n >= 1);
         in.scan_max_queries = ix->knobs.get(K_SCAN_MAX_QUERIES, bias_scan_max_queries(ix->dtype));
         if (mask_wants_count(bias_algo_inputs(in, served))) ix->active_allowed = in.allowed = count_allowed_rows(row_mask, ix->n);
         const AlgoChoice c = choose_bias_algo(in, served);
+        if (c.unsupported && algo == TS_ALGO_MFMA && !served && !in.subset)
+            return fail(TS_ERR_UNSUPPORTED, "%s, or one whose width is a multiple of 256 up to a 16,384-byte row", c.unsupported);
         if (c.unsupported) return fail(TS_ERR_UNSUPPORTED, "%s", c.unsupported);
         *use = c.algo;
         ix->active_bias_matrix = c.algo == TS_ALGO_MFMA;

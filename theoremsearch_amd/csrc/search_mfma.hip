@@ -118,7 +118,8 @@ static int mfma_grid(const ts_index* ix) { return std::max(1, std::min(ix->knobs
 // The search in progress is a biased one on the matrix path: whatever the width, its pass is the general-width kernel (256
 // queries per launch, full pass only, shared lists only; no screen, pairs, balancing or private lists).
 static bool biased_search(const ts_index* ix) { return ix->active_bias_matrix; }
-static bool general_width(const ts_index* ix) { return anyd_index(ix) || biased_search(ix); }
+// (the k-chunked kernel of the wider rows is the same form of search: kernels_mfma_wide.h)
+static bool general_width(const ts_index* ix) { return anyd_index(ix) || wide_index(ix) || biased_search(ix); }
 static bool mfma_pairs(const ts_index* ix, int nq) {
     return !biased_search(ix) && ix->dtype == TS_BF16 && ix->d == 1024 && nq > 192 && use_shape16(ix) && two_level_search(ix) &&
            ix->knobs.get(K_MFMA_PAIR, 1) != 0 && mfma_grid(ix) % 16 == 0;
@@ -190,6 +191,7 @@ struct MfmaPlan {
     std::vector<Level> lv;      // threshold levels, sparsest first; the last one is the full pass
     int kk, variant;
     bool anyd;                  // the general-width kernel (kernels_mfma_anyd.h): full pass only, shared lists only, no screen / pairs / balancing
+    bool wide;                  // ... at a width of wide_plan.h: the k-chunked pass and sample (kernels_mfma_wide.h), biased or not
     bool biased;                // ... with the call's bias term in its epilogue, and the biased sample select (any served width)
     bool shape16, statistical, dense_sample, dense0;
     bool screen_diag, screen, screen_rider, ksplit_form, pair;
@@ -210,6 +212,7 @@ static MfmaPlan mfma_plan(const ts_index* ix, int nq, int k) {
     p.variant = ix->knobs.get(K_MFMA_VARIANT, 0);
     p.biased = biased_search(ix);
     p.anyd = general_width(ix);
+    p.wide = wide_index(ix);
     p.shape16 = !p.anyd && use_shape16(ix);               // (false for the general-width form, and with it screen, pair and balance)
     p.nq_launch = mfma_block_queries(ix, nq);
     p.groups = p.shape16 ? 0 : p.nq_launch / 128;
@@ -354,8 +357,10 @@ static int mfma_sample(ts_index* ix, const MfmaPlan& p, int nq, const void* qmat
     const dim3 sgrid((unsigned)(sa.row_stride / wg_rows), (unsigned)(nchunks + ((sa.part || sa.scr_qimg) ? 1 : 0)));
     const int slds = sample_lds_bytes(wg_rows, (int)(ix->ld * ix->elem()));
     constexpr int kSampleLdsMax = 144 * 1024;   // dynamic part; the kernel also has a few hundred static bytes (rebalance_tiles)
-    if (slds > kSampleLdsMax) return fail(TS_ERR_INTERNAL, "threshold sample: rows of %lld bytes do not fit the LDS", (long long)(ix->ld * ix->elem()));
-    if (f32) TS_TRY((launch_lds<sample_scores_kernel<true, 2>, kSampleLdsMax>(ix->device, sgrid, 256, slds, st, sa)));
+    static_assert(kSampleLdsMax == kWideSampleLdsLimit, "wide_plan.h restates the sample's limit");
+    if (p.wide) TS_TRY(launch_sample_wide(ix, sgrid, st, sa));       // rows staged k-chunk by k-chunk: its LDS does not follow the width
+    else if (slds > kSampleLdsMax) return fail(TS_ERR_INTERNAL, "threshold sample: rows of %lld bytes do not fit the LDS", (long long)(ix->ld * ix->elem()));
+    else if (f32) TS_TRY((launch_lds<sample_scores_kernel<true, 2>, kSampleLdsMax>(ix->device, sgrid, 256, slds, st, sa)));
     else TS_TRY((launch_lds<sample_scores_kernel<false, 2>, kSampleLdsMax>(ix->device, sgrid, 256, slds, st, sa)));
     LevelArgs l;
     memset(&l, 0, sizeof(l));
@@ -503,7 +508,8 @@ static int mfma_level(ts_index* ix, const MfmaPlan& p, size_t i, int nq, int k, 
     if (p.anyd && !full_pass) return fail(TS_ERR_INTERNAL, "the general-width matrix kernel has no sparse level");
     hipEvent_t stop = full_pass ? prof_begin(ix, st, ix->n) : nullptr;  // only the full pass is bracketed
     int rc;
-    if (p.biased) rc = launch_pass_mfma_anyd_biased(ix, p.grid, st, a);
+    if (p.wide) rc = p.biased ? launch_pass_mfma_wide_biased(ix, p.grid, st, a) : launch_pass_mfma_wide(ix, p.grid, st, a);
+    else if (p.biased) rc = launch_pass_mfma_anyd_biased(ix, p.grid, st, a);
     else if (p.anyd) rc = launch_pass_mfma_anyd(ix, p.grid, st, a);
     else if (p.screen && full_pass) rc = screen_full_pass(ix, p.nb16, nq, p.grid, p.screen_diag ? p.variant : kVariantProduct, p.ksplit_form, st, a);
     else if (ix->dtype == TS_F32 && p.shape16) rc = launch_pass_mfma16_f32(ix->device, ix->d, p.nb16, full_pass, p.grid, st, a);
