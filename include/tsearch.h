@@ -380,9 +380,12 @@ int ts_rank_of(ts_index *ix, const void *queries, int q_dtype, int q_on_device, 
  * A list may be empty and may repeat a row (repeats share one rank).  Target rows are global ids (row_offset applies);
  * subset indexes are refused.  Queries are prepared as ts_search prepares them.  Host pointers; out_score may be NULL.
  * bf16 and fp32 indexes at every d that is a multiple of 64 from 128 up to a 4,096-byte row (bf16 up to d = 2048, fp32 up to
- * d = 1024): one matrix pass over the corpus per block of 256 queries and per 16 targets of the longest list (a gather launch
- * computes the targets' scores by the same arithmetic first).  Other widths (d = 64, widths that are no multiple of 64): one
- * ts_rank_of pass per target column - correct and slow.
+ * d = 1024), and at every d that is a multiple of 256 with a wider row of up to 16,384 bytes (bf16 d = 2304 .. 8192, fp32
+ * d = 1280 .. 4096: the k-chunked form of the pass; the option "TS_MFMA_GRID" sets the workgroups of its counting launch):
+ * one matrix pass over the corpus per block of 256 queries and per 16 targets of the longest list (a gather launch
+ * computes the targets' scores by the same arithmetic first; at the k-chunked widths a score has the bits the batched search
+ * returns for the row).  Other widths (d = 64, widths that are no multiple of 64, rows wider than 4,096 bytes whose d is no
+ * multiple of 256): one ts_rank_of pass per target column - correct and slow.
  * Arithmetic contract: the ranks are consistent with the scores returned here (distinct targets of one query have
  * distinct ranks, ordered by (score, -row)).  Where the fp64 truth cannot separate a target from its neighbours, a rank may
  * differ from ts_rank_of's and from the search paths' positions by the count of those neighbours. */

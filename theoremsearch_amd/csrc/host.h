@@ -373,6 +373,10 @@ static inline bool wide_index(const ts_index* ix) {
     if (ix->dtype == TS_F32 && ix->knobs.get(K_MFMA_F32, 16) == 0) return false;
     return ix->ld == ix->d && wide_served(ix->dtype, ix->d, two_level_search(ix));
 }
+// Workgroups of one matrix pass: one per CU, or TS_MFMA_GRID clamped to 1 .. kMfmaMaxGrid (search_mfma.hip: the pairs' position
+// words are sized by it).  The k-chunked rank pass (rank_many.hip) takes the same grid.
+constexpr int kMfmaMaxGrid = 2048;
+static inline int mfma_grid(const ts_index* ix) { return std::max(1, std::min(ix->knobs.get(K_MFMA_GRID, ix->cu_count), kMfmaMaxGrid)); }
 static inline bool mfma_index(const ts_index* ix) {
     if (anyd_index(ix) || wide_index(ix)) return true;
     if (ix->dtype == TS_BF16) return mfma_dim(ix->d);

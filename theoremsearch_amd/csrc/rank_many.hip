@@ -1,16 +1,22 @@
 // libtsearch.so - C ABI (include/tsearch.h), part 5: ts_rank_many, the ranks of many target rows per query, and
 // ts_count_above_many, its form for documents that live on other shards: one matrix pass per block of 256 queries and per
-// kRankT targets (kernels_rank_mfma.h) at every width of rank_many_served (rank_plan.h).  Other widths fall back to ts_rank_of
-// / ts_count_above, one streaming pass per target column: correct and slow.
+// kRankT targets at every width of rank_many_served (rank_plan.h; kernels_rank_mfma.h, whole rows in LDS) and of rank_wide_served
+// (rank_wide_plan.h; kernels_rank_wide.h, rows staged k-chunk by k-chunk).  Other widths fall back to ts_rank_of /
+// ts_count_above, one streaming pass per target column: correct and slow.
 #include <algorithm>
 #include <vector>
 
 #include "host.h"
 #include "kernels_rank_mfma.h"
+#include "kernels_rank_wide.h"
 
 static_assert(kRankQueries == kQBlock, "one launch holds one block of the query feed");
+static_assert(kRowPad % rank_wide_tile_rows() == 0, "whole 64-row tiles inside the padded allocation");
 
 static inline bool rank_many_width(const ts_index* ix) { return rank_many_served(ix->dtype, ix->d) && ix->ld == ix->d; }
+// the k-chunked widths: whatever TS_MFMA_F32 says and whatever the index size, as the narrower rank pass
+static inline bool rank_wide_width(const ts_index* ix) { return rank_wide_served(ix->dtype, ix->d) && ix->ld == ix->d; }
+static inline bool rank_matrix_width(const ts_index* ix) { return rank_many_width(ix) || rank_wide_width(ix); }
 
 static u64 host_key(float s, int64_t row) {
     return ((u64)host_ord_f32(s) << 32) | (u64)(0xFFFFFFFFu - (u32)row);
@@ -24,6 +30,15 @@ static int launch_rank_many_t(int dev, bool gather, int grid, int lds, hipStream
 
 // every served width has its kernel: storage type x RB (rank_rb) x tail group (rank_tail, bf16 only) x mode
 static int launch_rank_many(const ts_index* ix, bool gather, int grid, hipStream_t st, const RankManyArgs& a) {
+    if (rank_wide_width(ix)) {
+        // the k-chunked form: storage type x mode, the two chunk buffers whatever the width
+        constexpr int lds = rank_wide_lds_bytes();
+        if (ix->dtype == TS_F32)
+            return gather ? launch_lds<rank_wide_kernel<true, true>, lds>(ix->device, grid, kWideThreads, lds, st, a)
+                          : launch_lds<rank_wide_kernel<true, false>, lds>(ix->device, grid, kWideThreads, lds, st, a);
+        return gather ? launch_lds<rank_wide_kernel<false, true>, lds>(ix->device, grid, kWideThreads, lds, st, a)
+                      : launch_lds<rank_wide_kernel<false, false>, lds>(ix->device, grid, kWideThreads, lds, st, a);
+    }
     const int row_bytes = (int)ix->ld * ix->elem();
     const int rb = rank_rb(row_bytes);
     const int lds = rank_lds_bytes(rb, row_bytes);
@@ -46,6 +61,13 @@ static int rank_many_check(const ts_index* ix, const void* queries, int q_dtype,
     *empty = nq == 0 || off[nq] == 0;
     return TS_OK;
 }
+
+// rows of a tile of this index's pass (gather: slots), and the workgroups of its counting launch: one per CU; the k-chunked form
+// takes TS_MFMA_GRID where set, clamped as the search's pass
+static int64_t rank_tile_rows_of(const ts_index* ix) {
+    return rank_wide_width(ix) ? rank_wide_tile_rows() : rank_tile_rows((int)ix->ld * (int)ix->elem());
+}
+static int rank_count_grid(const ts_index* ix) { return rank_wide_width(ix) ? mfma_grid(ix) : ix->cu_count; }
 
 // One pass (kRankT targets of every query of one block) on the device and on the host.  A slot is one target of the pass:
 // gquery = its query within the block, tslot = its index in the caller's target arrays, skey = its key in this index's key
@@ -114,7 +136,7 @@ static int count_pass(ts_index* ix, hipStream_t st, RankPass& w, int nb, int64_t
         HIP_TRY(hipMemcpyAsync(w.d_tcount, w.tcount.data(), (size_t)nb * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(w.d_tworst, w.tworst.data(), (size_t)nb * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemsetAsync(w.d_counts, 0, (size_t)nb * kRankT * 4, st));
-        const int64_t tile_rows = rank_tile_rows((int)ix->ld * (int)ix->elem());
+        const int64_t tile_rows = rank_tile_rows_of(ix);
         RankManyArgs a = rank_many_args(ix, nb);
         a.ntiles = (ix->n + tile_rows - 1) / tile_rows;
         a.tkeys = w.d_tkeys;
@@ -122,7 +144,7 @@ static int count_pass(ts_index* ix, hipStream_t st, RankPass& w, int nb, int64_t
         a.tworst = w.d_tworst;
         a.counts = w.d_counts;
         hipEvent_t stop = prof_begin(ix, st, ix->n);
-        const int rc = launch_rank_many(ix, false, ix->cu_count, st, a);
+        const int rc = launch_rank_many(ix, false, rank_count_grid(ix), st, a);
         prof_end(stop, st);
         TS_TRY(rc);
         HIP_TRY(hipMemcpyAsync(w.counts.data(), w.d_counts, (size_t)nb * kRankT * 4, hipMemcpyDeviceToHost, st));
@@ -191,7 +213,7 @@ extern "C" int ts_rank_many(ts_index* ix, const void* queries, int q_dtype, int 
     if (empty) return TS_OK;
     if (!target_rows) return fail(TS_ERR_INVALID, "target_rows is NULL");
     if (ix->id_map) return fail(TS_ERR_UNSUPPORTED, "rank / count on a subset index");
-    if (!rank_many_width(ix))
+    if (!rank_matrix_width(ix))
         return rank_many_fallback(ix, queries, q_dtype, q_on_device, nq, target_offsets, target_rows, out_rank, out_score, stream);
 
     std::lock_guard<std::mutex> lock(ix->mu);
@@ -204,7 +226,7 @@ extern "C" int ts_rank_many(ts_index* ix, const void* queries, int q_dtype, int 
     RankPass w;
     TS_TRY(w.open(ix));
     const float nan = __builtin_nanf("");
-    const int64_t tile_rows = rank_tile_rows((int)ix->ld * (int)ix->elem());
+    const int64_t tile_rows = rank_tile_rows_of(ix);
 
     for (int q0 = 0; q0 < nq; q0 += kQBlock) {
         const int nb = std::min(kQBlock, nq - q0);
@@ -264,7 +286,7 @@ extern "C" int ts_count_above_many(ts_index* ix, const void* queries, int q_dtyp
     if (empty) return TS_OK;
     if (!target_scores || !target_ids) return fail(TS_ERR_INVALID, "target_scores or target_ids is NULL");
     if (ix->id_map) return fail(TS_ERR_UNSUPPORTED, "rank / count on a subset index");
-    if (!rank_many_width(ix))
+    if (!rank_matrix_width(ix))
         return count_above_many_fallback(ix, queries, q_dtype, q_on_device, nq, target_offsets, target_scores, target_ids, out_counts, stream);
 
     std::lock_guard<std::mutex> lock(ix->mu);

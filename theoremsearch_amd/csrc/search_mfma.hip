@@ -113,8 +113,7 @@ static std::vector<Level> plan_levels(const Knobs& kn, int64_t n, int kk, bool s
 // workgroup.  A batch of 193 .. 256 queries runs as ONE launch of workgroup PAIRS (MfmaArgs::pair): both workgroups of a pair
 // walk the same tiles with 128 queries each, two blocks per wave, so the corpus crosses HBM once for the whole batch (the
 // pair's second read of a tile is served by the XCD's L2 / the memory-side cache) instead of once per 128 queries.
-constexpr int kMfmaMaxGrid = 2048;   // workgroups of one pass (TS_MFMA_GRID is clamped to it; the pairs' position words are sized by it)
-static int mfma_grid(const ts_index* ix) { return std::max(1, std::min(ix->knobs.get(K_MFMA_GRID, ix->cu_count), kMfmaMaxGrid)); }
+// (mfma_grid, kMfmaMaxGrid: host.h - the k-chunked rank pass takes the same grid)
 // The search in progress is a biased one on the matrix path: whatever the width, its pass is the general-width kernel (256
 // queries per launch, full pass only, shared lists only; no screen, pairs, balancing or private lists).
 static bool biased_search(const ts_index* ix) { return ix->active_bias_matrix; }

@@ -368,7 +368,8 @@ class TheoremIndex:
 
     def rank_many(self, queries, targets):
         """Ranks of several rows per query in one matrix pass per block of 256 queries (every width that is a multiple of 64
-        from 128 up to a 4,096-byte row; other widths: one `rank_of` pass per target column): ``targets`` holds one integer
+        from 128 up to a 4,096-byte row, every multiple of 256 with a wider row of up to 16,384 bytes; other widths: one
+        `rank_of` pass per target column): ``targets`` holds one integer
         sequence per query (ragged, possibly empty, repeats allowed).  Returns ``(ranks, scores)``, lists of per-query
         int64 / float32 arrays aligned with ``targets``; ``-1`` / NaN for rows not in the index or with a NaN score.
         The ranks are consistent with the returned scores (score descending, row ascending); where the fp64 truth cannot
