@@ -421,6 +421,37 @@ int ts_count_above_many(ts_index *ix, const void *queries, int q_dtype, int q_on
 int ts_scores(ts_index *ix, const void *queries, int q_dtype, int q_on_device, int32_t nq,
               float *out, int out_on_device, void *stream);
 
+/* ---- moments of the stored rows -----------------------------------------------------------------------
+ * What a PCA over the whole table needs (experiments/pca_plotting.py streams the table out of Postgres twice for it), from the
+ * rows where they lie in HBM (a sums pass and a Gram pass): the host side is a d x d eigenproblem (theoremsearch_amd/pca.py).
+ *
+ * ts_index_moments: count, column sums and Gram matrix X^T X of the STORED rows (what the kernels multiply: normalised for
+ * metric cos, rounded for bf16) over all rows, or over the rows a row set allows (rows may be NULL).  out_sum [d] and
+ * out_gram [d x d] (row-major, full and symmetric: out_gram[i][j] and out_gram[j][i] are the same bits) are host doubles;
+ * out_gram may be NULL (sums and count only).
+ * ts_index_group_sums: count and column sums per code of scalar column `col` of `m`: a row whose int32 value v satisfies
+ * 0 <= v < ngroups goes to group v; TS_META_NULL and every other value go nowhere.  out_counts [ngroups], out_sums
+ * [ngroups x d], host.
+ *
+ * Served: bf16 and fp32 indexes (owned, attached, views, subsets), d a multiple of 64 in [128, 1024], 1 <= ngroups <= 256;
+ * anything else TS_ERR_UNSUPPORTED.  TS_ERR_INVALID for NULL arguments, a list column or a column never set, and a row set or a
+ * meta table with another n or on another device (the rules of ts_search_rowset).  n = 0 or a row set that allows nothing:
+ * count 0 and zeros.  A row the row set disallows, and the padding past n, contribute nothing whatever their bytes are (NaN
+ * and Inf included), and so do the rows of ts_index_group_sums whose code goes nowhere; a non-finite value in a row that counts
+ * propagates as it does in numpy (NaN / Inf in every sum and product that row's column takes part in) - with one difference in
+ * ts_index_group_sums: the row multiplies every group's indicator, 0 x NaN is NaN, so that column is non-finite in EVERY
+ * group's sum, not only in the row's own.  Products are added in fp32 over at most L = 8,192 consecutive rows and those
+ * sums in double, in a fixed order: |error| <= (L + 2) 2^-23 sum_r |x_ri x_rj| per element, and the same bits on every call
+ * with the same index and arguments.  Counts are integers.  Both calls wait for their result.  Moments are additive: those
+ * of a sharded corpus are the sums over its shards.
+ * ts_moments_plan: the constants of that pass for tests and tools - L, the panel width, and for (dtype, d, n, cu_count) the
+ * number of row ranges and the bytes of the partial tiles (each pointer may be NULL); needs no device. */
+int ts_index_moments(ts_index *ix, const ts_rowset *rows, int64_t *out_count, double *out_sum, double *out_gram, void *stream);
+int ts_index_group_sums(ts_index *ix, const ts_meta *m, int32_t col, int32_t ngroups, const ts_rowset *rows,
+                        int64_t *out_counts, double *out_sums, void *stream);
+int ts_moments_plan(int32_t dtype, int32_t d, int64_t n, int32_t cu_count, int32_t *flush_rows, int32_t *panel,
+                    int32_t *ranges, int64_t *partial_bytes);
+
 /* Merge `nparts` partial top-k lists per query (e.g. the all-gathered per-shard results,
  * SURVEY.md section 8e) into the global top-k_out under the same ordering rule.
  * scores/idx: [nparts x nq x k_in]; entries with idx < 0 are padding. */

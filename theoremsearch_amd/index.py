@@ -428,6 +428,39 @@ class TheoremIndex:
                                        _ffi.as_ptr(out), 0, None))
         return out
 
+    # -- moments ----------------------------------------------------------------------------
+    def moments(self, rowset: Optional[RowSet] = None, gram=True):
+        """``(count, sum float64 [d], gram float64 [d x d])`` of the STORED rows (normalised for "cos", rounded for bf16) - all of
+        them, or those ``rowset`` allows - from the rows in HBM (``ts_index_moments``: a sums pass and a Gram pass): what `pca.fit` turns into
+        a PCA.  ``gram`` false or None: the sums and the count only, and ``gram`` is returned as None.  The same bits on every call."""
+        count = C.c_int64(0)
+        s = np.zeros(self.d, dtype=np.float64)
+        g = np.zeros((self.d, self.d), dtype=np.float64) if gram else None
+        _ffi.check(self._lib.ts_index_moments(self._h, rowset.handle if rowset is not None else None, C.byref(count), _ffi.as_ptr(s),
+                                              _ffi.as_ptr(g) if g is not None else None, None))
+        return count.value, s, g
+
+    def group_sums(self, meta, column, rowset: Optional[RowSet] = None, ngroups: Optional[int] = None):
+        """``(names, counts int64 [G], sums float64 [G x d])``: per code of scalar column ``column`` (a name or a number) of the
+        `metadata.MetaTable` ``meta``, the number of (allowed) rows that carry it and the sum of those rows
+        (``ts_index_group_sums``).  The groups are the column's dictionary, in code order, and ``names`` its values; a column
+        without a dictionary is taken as codes 0 .. max, named by number (``ngroups`` sets their number instead).  NULLs and codes
+        outside the range go nowhere."""
+        col = meta.col[column] if isinstance(column, str) else int(column)
+        name = meta.names[col]
+        if ngroups is not None:
+            names = list(range(int(ngroups)))
+        elif name in meta.dicts and len(meta.dicts[name]):
+            names = list(meta.dicts[name].values)
+        else:
+            codes = np.asarray(meta.columns[col])
+            names = list(range(int(codes.max(initial=-1)) + 1)) or [0]
+        counts = np.zeros(len(names), dtype=np.int64)
+        sums = np.zeros((len(names), self.d), dtype=np.float64)
+        _ffi.check(self._lib.ts_index_group_sums(self._h, meta._h, col, len(names), rowset.handle if rowset is not None else None,
+                                                 _ffi.as_ptr(counts), _ffi.as_ptr(sums), None))
+        return names, counts, sums
+
     # -- profiling ---------------------------------------------------------------------------
     def profile_enable(self, enable: bool = True) -> None:
         _ffi.check(self._lib.ts_index_profile_enable(self._h, 1 if enable else 0))
