@@ -365,6 +365,69 @@ int ts_search_biased_rowset(ts_index *ix, const void *queries, int q_dtype, int 
                             float *out_scores, float *out_sims, int64_t *out_idx, int out_on_device, void *stream,
                             int algo, ts_search_stats *stats);
 
+/* ---- grouped search: the k best distinct groups, one row per group ------------------------------------
+ * What a user of the search engine ranks is papers and theorems, not rows: a paper contributes tens of rows that lie close
+ * together, and theorem_slogan holds several slogans per theorem, which the production query collapses with
+ * SELECT DISTINCT ON (ts.theorem_id) before it ranks (streamlit_app.py:254-259, 320-325).  In SQL terms:
+ * DISTINCT ON (group) ... ORDER BY group, score DESC, then ORDER BY score DESC LIMIT k - exactly, however large a group is.
+ *
+ * For query i: take the rows the row set allows (all rows when rows is NULL) whose score is not NaN, in the canonical order
+ * (score descending, then global row ascending).  The group of a row is its int32 value in scalar column `col` of `m`; a row
+ * whose value is TS_META_NULL is a group of its own (orphans are never merged); every other value, negative ones included,
+ * is a group id.  The answer is the first k rows in that order that are the first of their group: each is its group's best
+ * row (among equal best scores the lowest row), and the groups come in the order of their best rows.  out_groups (optional,
+ * [nq x k]) receives their codes.  Padding is (-inf, -1, TS_META_NULL) when fewer than k groups have an allowed, rankable row.
+ *
+ * Method: the searches themselves are ts_search_ex / ts_search_rowset, untouched.  Stage 1 searches
+ * at depth first = min(TS_MAX_K, max(2 k, k + 16)) and collapses each list to its group-firsts on the device; a list that
+ * holds k groups, or padding (the allowed rows are exhausted), is certified: a prefix of the row order determines a prefix of
+ * the group order.  Stage 2 searches the other queries again, gathered, at depth deep = TS_MAX_K (TS_ALGO_AUTO unless the
+ * caller forced the scan).  Stage 3 serves what is still open one query at a time on the scan, behind a mask without the
+ * groups found so far (ts_rowset_exclude's kernel), until k groups are found or no row is left: at most k passes over the
+ * corpus per such query - it can cost time, never an answer.  ts_grouped_stats tells what ran.
+ *
+ * ts_search_grouped waits for its result (the ladder reads the certificates back), with host and with device outputs.  m and
+ * rows must have the index's n and device (the rules of ts_search_rowset and ts_index_group_sums); col must be a scalar
+ * column that was set; 1 <= k <= TS_MAX_K; TS_ALGO_MFMA is refused exactly where ts_search_ex / ts_search_rowset would refuse
+ * stage 1.  Views and attached rows are served, row_offset is honoured; a subset index is TS_ERR_UNSUPPORTED.
+ * Not served: the citation-weighted ranking under grouping, sharded indexes (ts_shards_*, ts_comm_*: a sharded caller merges the
+ * per-shard grouped results and runs ts_collapse_topk on the merged lists when no group spans shards), subset indexes, bare
+ * masks without a row set, and the host-only search (ts_search_cpu).
+ *
+ * ts_collapse_topk: the collapse step alone, for sorted lists from anywhere.  scores / idx [nq x k_in], each list in the
+ * canonical order; column [n] holds the group code of local row id - row_offset; an id outside [row_offset, row_offset + n),
+ * or an entry with a NaN score, is padding.  Entry j is kept when its code is TS_META_NULL or no earlier entry of the list has
+ * its code; the kept entries are written in order into k_out slots per query (out_scores, out_idx, out_groups - optional),
+ * padded with (-inf, -1, TS_META_NULL).  out_found (optional) [nq]: the group-firsts of the WHOLE list (may exceed k_out);
+ * out_complete (optional) [nq]: 1 when found >= k_out or the list held padding - the slots are then the exact answer given
+ * that the list was a prefix of the query's row order.  The list is never re-sorted.  on_device: every pointer, column
+ * included, is device memory and the work is enqueued on `stream`; else every pointer is host memory and the call waits.
+ * 1 <= k_in <= TS_MAX_K, 1 <= k_out, nq >= 0, n >= 0, row_offset >= 0.
+ *
+ * ts_rowset_exclude: the row set  base AND NOT (code of the row in codes) AND NOT (row in local_rows)  over column col of m
+ * ("hide these papers"): a row set like any other.  base may be NULL (every row).  ncodes, nrows in [0, 256]; a code equal to
+ * TS_META_NULL or a row outside [0, n) is TS_ERR_INVALID; the lists need not be sorted or unique (the call sorts its copies).
+ * Waits for the count, as ts_meta_eval does.
+ *
+ * ts_group_depth: first and deep of the ladder for k (each pointer may be NULL); needs no device. */
+typedef struct ts_grouped_stats {
+    int32_t algo;             /* path of stage 1: TS_ALGO_SCAN or TS_ALGO_MFMA */
+    int32_t depth;            /* first depth used */
+    int32_t deep_queries;     /* queries that entered stage 2 */
+    int32_t excluded_queries; /* queries that entered stage 3 */
+    int32_t exclusion_passes; /* scan passes run in stage 3, all queries */
+} ts_grouped_stats;
+
+int ts_search_grouped(ts_index *ix, const void *queries, int q_dtype, int q_on_device, int32_t nq, int32_t k,
+                      ts_meta *m, int32_t col, const ts_rowset *rows, float *out_scores, int64_t *out_idx,
+                      int32_t *out_groups, int out_on_device, void *stream, int algo, ts_grouped_stats *stats);
+int ts_collapse_topk(int device, const float *scores, const int64_t *idx, int32_t nq, int32_t k_in, int32_t k_out,
+                     const int32_t *column, int64_t n, int64_t row_offset, float *out_scores, int64_t *out_idx,
+                     int32_t *out_groups, int32_t *out_found, int32_t *out_complete, int on_device, void *stream);
+int ts_rowset_exclude(ts_meta *m, int32_t col, const ts_rowset *base, const int32_t *codes, int32_t ncodes,
+                      const int64_t *local_rows, int32_t nrows, ts_rowset **out, void *stream);
+int ts_group_depth(int32_t k, int32_t *first, int32_t *deep);
+
 /* Rank of one given row per query in the canonical order of that query's scores over the whole index (0 = best):
  * the number of rows whose (score, -row) beats the target's.  One streaming pass that counts; replaces ranking the
  * full [nq x N] matrix and looking the relevant document up - np.argsort(-sim_matrix) followed by the position of

@@ -36,6 +36,12 @@ class SearchStats(C.Structure):
                 ("screened", C.c_int32), ("candidates", C.c_int64)]
 
 
+class GroupedStats(C.Structure):
+    """ts_grouped_stats: what the ladder of one grouped search ran."""
+    _fields_ = [("algo", C.c_int32), ("depth", C.c_int32), ("deep_queries", C.c_int32), ("excluded_queries", C.c_int32),
+                ("exclusion_passes", C.c_int32)]
+
+
 class Atom(C.Structure):
     """ts_atom: one atom of a metadata filter program (``set``: host uint32 words, copied by ts_meta_eval)."""
     _fields_ = [("kind", C.c_int32), ("col", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32), ("negate", C.c_int32),
@@ -101,6 +107,13 @@ _SIGNATURES = {
     "ts_search_biased_rowset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_int,
                                           C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                           C.POINTER(SearchStats)]),
+    "ts_search_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(GroupedStats)]),
+    "ts_collapse_topk": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "ts_rowset_exclude": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                    C.POINTER(C.c_void_p), C.c_void_p]),
+    "ts_group_depth": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ts_rank_of": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                              C.c_void_p]),
     "ts_count_above": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -410,6 +410,11 @@ int prep_dispatch(int src_dtype, int dst_dtype, bool normalize, const void* src,
 // search.hip: the streaming scan + its select (also the exact re-run of the matrix path: qlist / qcount on the device)
 int scan_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx, const int* qlist, const int* qcount,
                 hipStream_t st, const float* qbuf = nullptr, const unsigned short* qb16 = nullptr);
+// search.hip: a whole search as ts_search_ex / ts_search_rowset run it (validation, lock, stream order, path choice, read-back),
+// for a unit that builds on searches (grouped.hip).  row_mask: NULL, or a DEVICE mask that allows known_allowed rows
+int search_core(ts_index* ix, const void* queries, int q_dtype, int q_on_device, int32_t nq, int32_t k, float* out_scores,
+                int64_t* out_idx, int out_on_device, void* stream, int algo, ts_search_stats* stats, const uint32_t* row_mask,
+                int64_t known_allowed);
 // search.hip: the queries of a call, one block of at most kQBlock at a time.  query_feed_open makes sure of ix->qstore (f32copy:
 // and ix->qf32) and, for host queries, sizes the staging buffer once; query_feed_block copies a block of host queries there and
 // prepares it (prep_dispatch: normalise (COS), round to the storage type, zero-pad to 256 rows x ld; f32copy: the fp32 copy the

@@ -419,6 +419,14 @@ static int search_impl(ts_index* ix, const void* queries, int q_dtype, int q_on_
     return search_read_back(ix, use, block, nq, k, dscores, didx, out_scores, out_idx, out_on_device, stats, st);
 }
 
+// search_impl for the other translation units (grouped.hip): row_mask, when given, is a device mask that allows known_allowed rows
+int search_core(ts_index* ix, const void* queries, int q_dtype, int q_on_device, int32_t nq, int32_t k, float* out_scores,
+                int64_t* out_idx, int out_on_device, void* stream, int algo, ts_search_stats* stats, const uint32_t* row_mask,
+                int64_t known_allowed) {
+    return search_impl(ix, queries, q_dtype, q_on_device, nq, k, out_scores, out_idx, out_on_device, stream, algo, stats, row_mask,
+                       row_mask ? 1 : 0, nullptr, known_allowed);
+}
+
 extern "C" int ts_search_ex(ts_index* ix, const void* queries, int q_dtype, int q_on_device, int32_t nq, int32_t k,
                             float* out_scores, int64_t* out_idx, int out_on_device, void* stream, int algo,
                             ts_search_stats* stats) {

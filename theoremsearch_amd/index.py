@@ -276,6 +276,57 @@ class TheoremIndex:
                                           C.c_void_p(out_scores_ptr), C.c_void_p(out_idx_ptr), 1,
                                           C.c_void_p(stream), _ALGOS[algo], None))
 
+    # -- grouped search ---------------------------------------------------------------------
+    @staticmethod
+    def _group_column(meta, column) -> int:
+        return meta.col[column] if isinstance(column, str) else int(column)
+
+    def search_grouped(self, queries, k: int, meta, column, mask=None, algo: str = "auto", return_groups: bool = False,
+                       return_stats: bool = False):
+        """The ``k`` best distinct groups, one row per group (``ts_search_grouped``): ``SELECT DISTINCT ON (group)`` before the
+        ranking, exactly, however large a group is.  The group of a row is its value in scalar column ``column`` (a name or a
+        number) of the `metadata.MetaTable` ``meta``; a NULL is a group of its own.  ``mask``: a `metadata.RowSet` or None.
+        Returns ``(scores, indices)`` shaped and ordered like `search` - each row is its group's best row - then the group codes
+        ``int32 [nq x k]`` with ``return_groups`` and the ladder's counters (``algo, depth, deep_queries, excluded_queries,
+        exclusion_passes``) with ``return_stats``.  Padding is ``(-inf, -1, NULL)``."""
+        if self._cpu_rows is not None:
+            raise ValueError("the host-only index (device=-1) has no grouped search")
+        if mask is not None and not isinstance(mask, RowSet):
+            raise TypeError("search_grouped takes a metadata.RowSet as its mask (MetaTable.eval / MetaTable.exclude), not a bare mask")
+        q = _host_rows(queries)
+        if q.shape[1] != self.d:
+            raise ValueError(f"queries have d={q.shape[1]}, index has d={self.d}")
+        nq, k = q.shape[0], int(k)
+        scores = np.empty((nq, max(k, 0)), dtype=np.float32)
+        idx = np.empty((nq, max(k, 0)), dtype=np.int64)
+        groups = np.empty((nq, max(k, 0)), dtype=np.int32)
+        stats = _ffi.GroupedStats()
+        _ffi.check(self._lib.ts_search_grouped(self._h, _ffi.as_ptr(q), _ffi.np_dtype_code(q), 0, nq, k, meta._h,
+                                               self._group_column(meta, column), mask.handle if mask is not None else None,
+                                               _ffi.as_ptr(scores), _ffi.as_ptr(idx), _ffi.as_ptr(groups), 0, None, _ALGOS[algo],
+                                               C.byref(stats)))
+        out = (scores, idx)
+        if return_groups:
+            out += (groups,)
+        if return_stats:
+            out += ({"algo": stats.algo, "depth": stats.depth, "deep_queries": stats.deep_queries,
+                     "excluded_queries": stats.excluded_queries, "exclusion_passes": stats.exclusion_passes},)
+        return out
+
+    def search_grouped_device(self, q_ptr: int, q_dtype: str, nq: int, k: int, meta, column, out_scores_ptr: int, out_idx_ptr: int,
+                              out_groups_ptr: int = 0, stream: int = 0, algo: str = "auto", rowset: Optional[RowSet] = None) -> dict:
+        """`search_grouped` on device buffers (queries [nq x d] dense; outputs [nq x k] f32 / i64 / i32, ``out_groups_ptr`` may be
+        0) on ``stream`` (0 = the index's own).  Unlike `search_device` the call WAITS for its result - the ladder reads its
+        certificates back between the stages - and returns the ladder's counters."""
+        stats = _ffi.GroupedStats()
+        _ffi.check(self._lib.ts_search_grouped(self._h, C.c_void_p(q_ptr), _DTYPES[q_dtype], 1, int(nq), int(k), meta._h,
+                                               self._group_column(meta, column), rowset.handle if rowset is not None else None,
+                                               C.c_void_p(out_scores_ptr), C.c_void_p(out_idx_ptr),
+                                               C.c_void_p(out_groups_ptr) if out_groups_ptr else None, 1, C.c_void_p(stream),
+                                               _ALGOS[algo], C.byref(stats)))
+        return {"algo": stats.algo, "depth": stats.depth, "deep_queries": stats.deep_queries,
+                "excluded_queries": stats.excluded_queries, "exclusion_passes": stats.exclusion_passes}
+
     def search_biased(self, queries, k: int, bias, weight: float, mask=None, algo: Optional[str] = None,
                       return_stats: bool = False):
         """Top-k of ``score + weight * bias[row]`` over all rows (all rows ``mask`` allows): the citation-weighted
@@ -507,6 +558,37 @@ def merge_topk(scores: np.ndarray, idx: np.ndarray, k_out: int, device: int = 0)
     _ffi.check(_ffi.load().ts_merge_topk(device, _ffi.as_ptr(s), _ffi.as_ptr(i), nparts, nq, k_in, k_out,
                                          _ffi.as_ptr(os_), _ffi.as_ptr(oi), 0, None))
     return os_, oi
+
+
+def group_depth(k: int) -> Tuple[int, int]:
+    """``(first, deep)``: the depths of the grouped search's ladder for ``k`` (``ts_group_depth``; needs no device)."""
+    first, deep = C.c_int32(0), C.c_int32(0)
+    _ffi.check(_ffi.load().ts_group_depth(int(k), C.byref(first), C.byref(deep)))
+    return first.value, deep.value
+
+
+def collapse_topk(scores: np.ndarray, idx: np.ndarray, column, k_out: int, row_offset: int = 0, device: int = 0):
+    """The collapse step of the grouped search alone (``ts_collapse_topk``), for sorted ``[nq x k_in]`` lists from anywhere -
+    merged per-shard grouped results, a caller's own: the first ``k_out`` entries of each list that are the first of their group
+    (``column[id - row_offset]``; NULL: a group of its own), in order.  Returns ``(scores, indices, groups, found, complete)``:
+    ``found [nq]`` counts the group-firsts of the whole list, ``complete [nq]`` is true where ``found >= k_out`` or the list
+    held padding."""
+    s = np.ascontiguousarray(scores, dtype=np.float32)
+    i = np.ascontiguousarray(idx, dtype=np.int64)
+    col = np.ascontiguousarray(column, dtype=np.int32).reshape(-1)
+    if s.ndim != 2 or s.shape != i.shape:
+        raise ValueError("scores and idx are [nq x k_in], the same shape")
+    nq, k_in = s.shape
+    k_out = int(k_out)
+    os_ = np.empty((nq, max(k_out, 0)), dtype=np.float32)
+    oi = np.empty((nq, max(k_out, 0)), dtype=np.int64)
+    og = np.empty((nq, max(k_out, 0)), dtype=np.int32)
+    found = np.zeros(nq, dtype=np.int32)
+    complete = np.zeros(nq, dtype=np.int32)
+    _ffi.check(_ffi.load().ts_collapse_topk(device, _ffi.as_ptr(s), _ffi.as_ptr(i), nq, k_in, k_out, _ffi.as_ptr(col), col.shape[0],
+                                            int(row_offset), _ffi.as_ptr(os_), _ffi.as_ptr(oi), _ffi.as_ptr(og), _ffi.as_ptr(found),
+                                            _ffi.as_ptr(complete), 0, None))
+    return os_, oi, og, found, complete.astype(bool)
 
 
 class Timer:

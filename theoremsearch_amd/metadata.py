@@ -346,6 +346,22 @@ class MetaTable:
         _ffi.check(self._lib.ts_meta_eval(self._h, arr, len(atoms), C.byref(h), C.c_void_p(stream)))
         return RowSet(h)
 
+    def exclude(self, column, codes, rows=(), base: Optional[RowSet] = None, stream: int = 0) -> RowSet:
+        """``base AND NOT (the row's code in column `column` is in codes) AND NOT (the row is in rows)`` as a `RowSet`
+        (``ts_rowset_exclude``): "hide these papers", and the mask the grouped search's last stage runs behind.  ``column``: a
+        name or a number; ``codes``: up to 256 int32 codes (`NULL` is not one: NULL rows are excluded by row); ``rows``: up to
+        256 local rows; neither needs to be sorted or unique.  ``base`` None: every row."""
+        if self._lib is None or not self._h.value:
+            raise ValueError("this MetaTable only encodes (device=None): there is no host evaluator")
+        col = self.col[column] if isinstance(column, str) else int(column)
+        c = np.ascontiguousarray(np.asarray(list(codes), dtype=np.int32).reshape(-1))
+        r = np.ascontiguousarray(np.asarray(list(rows), dtype=np.int64).reshape(-1))
+        h = C.c_void_p()
+        _ffi.check(self._lib.ts_rowset_exclude(self._h, col, base.handle if base is not None else None,
+                                               _ffi.as_ptr(c) if c.size else None, c.shape[0],
+                                               _ffi.as_ptr(r) if r.size else None, r.shape[0], C.byref(h), C.c_void_p(stream)))
+        return RowSet(h)
+
     # -- lifetime -----------------------------------------------------------------------------
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h.value:

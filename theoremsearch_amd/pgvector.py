@@ -86,15 +86,21 @@ def citation_bias(citations: Sequence[Optional[int]]) -> np.ndarray:
 
 
 def search(index: TheoremIndex, query_vec, top_k: int, citation_weight: float = 0.0,
-           citations: Optional[Sequence[Optional[int]]] = None, mask=None, exact: bool = False, bias=None):
+           citations: Optional[Sequence[Optional[int]]] = None, mask=None, exact: bool = False, bias=None, distinct=None):
     """Returns a list of dicts ``{"row", "similarity", "score"}`` ordered like the SQL result.  ``mask`` (bool per row,
     e.g. `filters.sql_filter_mask`, or a `metadata.RowSet` evaluated on the device: ``MetaTable.from_sql_rows(rows).eval(f)``)
     plays the WHERE clause: only those rows are ranked.
     ``exact=False`` (default) is the reference's form: the ``max(50, 10 k)`` nearest rows re-ranked by the weighted score.
     ``exact=True`` ranks EVERY (allowed) row by the weighted score on the device (``ts_search_biased``): the same answer
     whenever the pool holds it, and the right one when a heavily cited theorem sits outside the pool; ``bias`` may carry
-    a ready-made `citation_bias` array for repeated searches."""
+    a ready-made `citation_bias` array for repeated searches.
+    ``distinct=(meta, column)`` - a `metadata.MetaTable` and one of its scalar columns, e.g. ``(meta, "paper")`` - returns one
+    hit per group: ``SELECT DISTINCT ON`` in front of the ranking (streamlit_app.py:254-259), each group's best row, exactly
+    (`TheoremIndex.search_grouped`); the hits then carry ``"group"``.  ``mask`` must then be a `metadata.RowSet` or None; not
+    with a citation weight."""
     q = np.asarray(query_vec, dtype=np.float32).reshape(1, -1)
+    if distinct is not None:
+        return _search_distinct(index, q, top_k, citation_weight, mask, distinct)[0]
     if citation_weight == 0.0:
         scores, idx = index.search(q, int(top_k), mask=mask)
         return [{"row": int(i), "similarity": 1.0 + float(s), "score": 1.0 + float(s)}
@@ -132,14 +138,27 @@ def search(index: TheoremIndex, query_vec, top_k: int, citation_weight: float = 
     return rows[: int(top_k)]
 
 
+def _search_distinct(index: TheoremIndex, q, top_k: int, citation_weight: float, mask, distinct):
+    """One list of hits per query of ``q``, one hit per group of ``distinct = (meta, column)``."""
+    if citation_weight != 0.0:
+        raise ValueError("distinct hits are ranked by similarity alone: the citation-weighted ranking has no grouped form")
+    meta, column = distinct
+    scores, idx, groups = index.search_grouped(q, int(top_k), meta, column, mask=mask, return_groups=True)
+    return [[{"row": int(i), "similarity": 1.0 + float(s), "score": 1.0 + float(s), "group": int(g)}
+             for s, i, g in zip(srow, irow, grow) if i >= 0] for srow, irow, grow in zip(scores, idx, groups)]
+
+
 def search_batch(index: TheoremIndex, query_vecs, top_k: int, citation_weight: float,
-                 citations: Optional[Sequence[Optional[int]]] = None, bias=None, mask=None):
+                 citations: Optional[Sequence[Optional[int]]] = None, bias=None, mask=None, distinct=None):
     """`search` with ``exact=True`` for many queries at once: every (allowed) row ranked by the weighted score, one corpus
     pass per 256 queries where the index has the biased matrix search (``ts_search_biased_ex`` on ``auto``), the scan
     otherwise.  Returns one list per query, each shaped like the result of ``search(..., exact=True)``.  ``mask``: bool per
-    row, or a `metadata.RowSet` - whose batch stays on the matrix pass (a row set knows its count)."""
+    row, or a `metadata.RowSet` - whose batch stays on the matrix pass (a row set knows its count).
+    ``distinct=(meta, column)``: one hit per group for every query, as in `search`; ``citation_weight`` must then be 0."""
     q = np.asarray(query_vecs, dtype=np.float32)
     q = q.reshape(1, -1) if q.ndim == 1 else q
+    if distinct is not None:
+        return _search_distinct(index, q, top_k, citation_weight, mask, distinct)
     if citations is None and bias is None:
         raise ValueError("citation-weighted search needs the per-row citation counts")
     b = citation_bias(citations) if bias is None else np.asarray(bias, dtype=np.float32)
