@@ -365,6 +365,51 @@ int ts_search_biased_rowset(ts_index *ix, const void *queries, int q_dtype, int 
                             float *out_scores, float *out_sims, int64_t *out_idx, int out_on_device, void *stream,
                             int algo, ts_search_stats *stats);
 
+/* ---- a row set per query: one matrix pass for a batch whose queries sit behind different filters -------
+ * Query q is searched behind sets[which[q]], or behind no filter when which[q] == -1 (`which`: host memory, nq entries;
+ * sets: host array of nsets <= TS_MAX_ROWSETS handles, entries nobody names may be NULL).  Output row q is what
+ * ts_search_rowset defines for query q alone behind its set (ts_search_ex for -1): the exact top k of the allowed rows, by
+ * score descending, then id ascending, padded with -inf / -1, ids global.
+ *
+ * Routing (csrc/rowsets_plan.h holds the rules):
+ *   - all queries name one set: the call IS ts_search_rowset with that set (all -1: ts_search_ex), its paths and its bits;
+ *   - otherwise the queries whose set allows at least a tenth of the rows ride ONE pass of the general-width matrix kernel per
+ *     256 of them (a dense threshold sample and a threshold per query from that query's own rows, the query's mask bit tested
+ *     only for scores that pass its threshold, a final select that sends a query with too few or too many candidates to an
+ *     exact re-run behind its own set) - when the index is bf16 or fp32, has at least TS_MFMA_MIN_ROWS rows and a width that
+ *     is a multiple of 64 from 128 up to a 4,096-byte row (384 / 512 / 768 / 1024 included), under the default two-level
+ *     search, and those queries number more than one scan pass serves (4; fp32: 8; k > 64: 1) and name at least two sets;
+ *   - every other query (a sparse or empty set, a width or option the pass does not serve, the k-chunked widths, a small
+ *     remainder) is grouped by set, one call of the existing search per set under TS_ALGO_AUTO; a set that allows nothing
+ *     returns the padding without a launch.
+ * algo: TS_ALGO_SCAN runs every set's queries on the scan (the A/B partner of the pass); TS_ALGO_MFMA is refused with
+ * TS_ERR_UNSUPPORTED unless every query rides the pass; a delegated call hands algo on.
+ *
+ * Score bits of a query of the shared pass are the general-width kernel's single MFMA chain, as for ts_search_biased_ex: at
+ * the widths that kernel serves for ts_search_rowset they equal that call's bits; at 384 / 512 / 768 / 1024 they are the
+ * general-width kernel's, not the hand-laid kernels'.  Nothing more is promised across the two paths.
+ *
+ * TS_ERR_INVALID: nsets outside [0, TS_MAX_ROWSETS], a which[q] outside [-1, nsets), a named set that is NULL, has another n
+ * or lives on another device than the index, k outside [1, TS_MAX_K], NULL queries or outputs.  TS_ERR_UNSUPPORTED: a subset
+ * index.  nq == 0 does nothing.  The call waits for its pass (the re-run list is read back per block of 256 queries); the
+ * row sets must stay alive until it returns. */
+#define TS_MAX_ROWSETS 256
+typedef struct ts_rowsets_stats {
+    int32_t algo;             /* TS_ALGO_MFMA when at least one query ran in the shared pass, else TS_ALGO_SCAN
+                                 (a delegated call: what the call it became reports) */
+    int32_t sets_used;        /* distinct entries of sets[] that which[] names */
+    int32_t pass_queries;     /* queries answered by the shared matrix pass(es) */
+    int32_t scan_queries;     /* queries answered by per-set calls of the existing search (a delegated call: all of them;
+                                 the queries of an empty set count here) */
+    int32_t scan_calls;       /* ... and how many such calls (an empty set makes none) */
+    int32_t fallback_queries; /* pass queries re-run exactly */
+    int64_t candidates;       /* as ts_search_stats, summed over the blocks of the pass */
+} ts_rowsets_stats;
+
+int ts_search_rowsets(ts_index *ix, const void *queries, int q_dtype, int q_on_device, int32_t nq, int32_t k,
+                      const ts_rowset *const *sets, int32_t nsets, const int32_t *which, float *out_scores,
+                      int64_t *out_idx, int out_on_device, void *stream, int algo, ts_rowsets_stats *stats);
+
 /* ---- grouped search: the k best distinct groups, one row per group ------------------------------------
  * What a user of the search engine ranks is papers and theorems, not rows: a paper contributes tens of rows that lie close
  * together, and theorem_slogan holds several slogans per theorem, which the production query collapses with

@@ -18,6 +18,7 @@ TS_F32, TS_BF16 = 0, 1
 TS_METRIC_IP, TS_METRIC_COS = 0, 1
 TS_ALGO_AUTO, TS_ALGO_SCAN, TS_ALGO_MFMA = 0, 1, 2
 TS_MAX_K = 256
+TS_MAX_ROWSETS = 256
 
 # TS_LIB overrides the library file (A/B builds of the same ABI during kernel tuning)
 _LIB_PATH = os.environ.get("TS_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtsearch.so")
@@ -40,6 +41,12 @@ class GroupedStats(C.Structure):
     """ts_grouped_stats: what the ladder of one grouped search ran."""
     _fields_ = [("algo", C.c_int32), ("depth", C.c_int32), ("deep_queries", C.c_int32), ("excluded_queries", C.c_int32),
                 ("exclusion_passes", C.c_int32)]
+
+
+class RowsetsStats(C.Structure):
+    """ts_rowsets_stats: how one search behind a row set per query was routed."""
+    _fields_ = [("algo", C.c_int32), ("sets_used", C.c_int32), ("pass_queries", C.c_int32), ("scan_queries", C.c_int32),
+                ("scan_calls", C.c_int32), ("fallback_queries", C.c_int32), ("candidates", C.c_int64)]
 
 
 class Atom(C.Structure):
@@ -107,6 +114,8 @@ _SIGNATURES = {
     "ts_search_biased_rowset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_int,
                                           C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                           C.POINTER(SearchStats)]),
+    "ts_search_rowsets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(RowsetsStats)]),
     "ts_search_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(GroupedStats)]),
     "ts_collapse_topk": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,

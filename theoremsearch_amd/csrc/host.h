@@ -24,6 +24,7 @@
 #include "scan_plan.h"
 #include "anyd_plan.h"
 #include "bias_plan.h"
+#include "rowsets_plan.h"
 #include "wide_plan.h"
 #include "encoder_plan.h"
 #include "meta_plan.h"
@@ -175,6 +176,15 @@ struct IndexQueue {
     }
 };
 
+// ts_search_rowsets: the block of pass queries in progress (under the handle's `mu`).  mfma_search reads the sets, makes the
+// block's table from them and adds what the block's final select and re-run counted.
+struct RowsetsCall {
+    const ts_rowset* const* sets = nullptr;
+    const int32_t* which = nullptr;      // [nq of the block]: the set of each query of the block, -1 = every row
+    int fallback_queries = 0;            // summed over the blocks so far
+    int64_t candidates = 0;
+};
+
 struct ts_index : IndexQueue {
     int device = 0;
     int64_t n = 0, n_pad = 0, ld = 0, row_offset = 0;
@@ -206,6 +216,9 @@ struct ts_index : IndexQueue {
     DevArray<void> rank_buf;                                 // ts_rank_of: targets | counts | target scores, one query block
     DevArray<void> rank_many_buf;                            // ts_rank_many: slots | keys | counts of one pass of one query block
     const u32* active_mask = nullptr;                        // bitmask of the search in progress (under `mu`)
+    RowsetsCall* active_rowsets = nullptr;                   // ts_search_rowsets' shared pass in progress: a mask per query (active_mask is NULL then)
+    DevArray<void> rowsets_dev;                              // ... the block's RowsetsTable, then its re-run lists [256] and their counts [256]
+    std::vector<unsigned char> rowsets_host;                 // ... and the host copy both are uploaded from
     int64_t active_allowed = 0;                              // rows that bitmask allows (host masks: counted; a row set's: known; else n)
     Knobs knobs;                                             // env at creation, then ts_index_set_option
     hipStream_t last_stream = nullptr;                       // stream the previous call ran on: compared, never used (it may be gone)
@@ -403,7 +416,7 @@ static inline bool use_shape16(const ts_index* ix) {
 // ---------------------------------------------------------------------------------------------
 // functions one translation unit defines for the others
 // ---------------------------------------------------------------------------------------------
-namespace ts { struct MfmaArgs; struct SampleArgs; }
+namespace ts { struct MfmaArgs; struct SampleArgs; struct LevelArgs; }
 // index.hip: normalise / convert / pad rows (uploads, query preparation)
 int prep_dispatch(int src_dtype, int dst_dtype, bool normalize, const void* src, int64_t src_ld, void* dst, float* f32copy,
                   int64_t ld, int d, int64_t nrows, int64_t rows_total, hipStream_t st);
@@ -462,6 +475,12 @@ int launch_pass_mfma_anyd(const ts_index* ix, int grid, hipStream_t st, const ts
 // launch_mfma_anyd_biased.hip: the same pass with the call's bias term in the epilogue (ix->active_bias, active_bias_w), at any
 // width of bias_index
 int launch_pass_mfma_anyd_biased(const ts_index* ix, int grid, hipStream_t st, const ts::MfmaArgs& a);
+// launch_mfma_anyd_rowsets.hip: the pass, the threshold sample, its select and the final select of ts_search_rowsets (a row set per
+// query: ix->rowsets_dev holds the block's table), at any width of bias_index
+int launch_pass_mfma_anyd_rowsets(const ts_index* ix, int grid, hipStream_t st, const ts::MfmaArgs& a);
+int launch_sample_rowsets(const ts_index* ix, dim3 grid, int lds, hipStream_t st, const ts::SampleArgs& sa);
+int launch_sample_select_rowsets(const ts_index* ix, int nq, hipStream_t st, const ts::LevelArgs& l, const float* scores, int row_stride);
+int launch_level_select_rowsets(const ts_index* ix, int nq, hipStream_t st, const ts::LevelArgs& l);
 // launch_mfma_wide.hip: the same two passes and the threshold sample of an index the k-chunked kernels serve (wide_index)
 int launch_pass_mfma_wide(const ts_index* ix, int grid, hipStream_t st, const ts::MfmaArgs& a);
 int launch_pass_mfma_wide_biased(const ts_index* ix, int grid, hipStream_t st, const ts::MfmaArgs& a);

@@ -23,12 +23,14 @@
 //     Lane-private lists are not used (the select is told nwriters = 0).  NaN scores never pass.
 //   * mfma_anyd_biased_kernel (ts_search_biased_ex) is the same pass with s = fmaf(w, bias[row], <row, query>) in the epilogue; it
 //     also runs the four hand-laid widths (bias_plan.h: bias_served), since the row length is a run-time value.
+//   * mfma_anyd_rowsets_kernel (ts_search_rowsets) is the same pass with the filter of the epilogue taken per query, at the same widths.
 //
 // Full pass only: tile_stride == 1 and run == 1 (the host guarantees it); the kernel covers rows [0, 32 * ntiles), the
 // allocation is padded to 256 rows, so whole staging tiles are in bounds.  It may be the first level of a search (a tiny
 // index under algo = mfma): thresholds -inf, every real row a candidate.
 #pragma once
 #include "anyd_plan.h"
+#include "rowsets_plan.h"
 #include "kernels_mfma16_ops.h"
 
 namespace ts {
@@ -56,17 +58,38 @@ struct AnydBiasArgs {
 template <bool F32, int RB>
 __global__ void __launch_bounds__(kAnydThreads) mfma_anyd_kernel(AnydArgs aa) {
     constexpr bool BIAS = false;
+    constexpr bool ROWSETS = false;
     const float* const bias = nullptr;
     const float bias_w = 0.0f;
+    const RowsetsTable* const rowsets = nullptr;
 #include "kernels_mfma_anyd_pass.inc"
 }
 
 template <bool F32, int RB>
 __global__ void __launch_bounds__(kAnydThreads) mfma_anyd_biased_kernel(AnydBiasArgs ba) {
     constexpr bool BIAS = true;
+    constexpr bool ROWSETS = false;
     const AnydArgs& aa = ba.a;
     const float* const bias = ba.bias;
     const float bias_w = ba.w;
+    const RowsetsTable* const rowsets = nullptr;
+#include "kernels_mfma_anyd_pass.inc"
+}
+
+// A row set per query (ts_search_rowsets): the plain pass with the mask of the epilogue's test taken per query from the
+// block's table (rowsets_plan.h: RowsetsTable; m.row_mask is not read).  Thresholds are per query already.
+struct AnydRowsetsArgs {
+    AnydArgs a;
+    const RowsetsTable* table;       // device
+};
+template <bool F32, int RB>
+__global__ void __launch_bounds__(kAnydThreads) mfma_anyd_rowsets_kernel(AnydRowsetsArgs ra) {
+    constexpr bool BIAS = false;
+    constexpr bool ROWSETS = true;
+    const AnydArgs& aa = ra.a;
+    const float* const bias = nullptr;
+    const float bias_w = 0.0f;
+    const RowsetsTable* const rowsets = ra.table;
 #include "kernels_mfma_anyd_pass.inc"
 }
 

@@ -1,12 +1,16 @@
-// The general-width full pass (kernels_mfma_anyd.h), the text of the kernels' bodies: included inside mfma_anyd_kernel and
-// mfma_anyd_biased_kernel, which define   F32, RB (template parameters), BIAS (constexpr bool), aa (AnydArgs), bias (const
-// float*, read only where BIAS), bias_w (float); it declares the dynamic LDS array srows itself and uses the names of
+// The general-width full pass (kernels_mfma_anyd.h), the text of the kernels' bodies: included inside mfma_anyd_kernel,
+// mfma_anyd_biased_kernel and mfma_anyd_rowsets_kernel, which define   F32, RB (template parameters), BIAS, ROWSETS (constexpr
+// bool), aa (AnydArgs), bias (const float*, read only where BIAS), bias_w (float), rowsets (const RowsetsTable*, read only where
+// ROWSETS); it declares the dynamic LDS array srows itself and uses the names of
 // kernels_mfma_anyd.h (kAnydThreads, kAnydWaves, kAnydNBW, kAnydSeg, kAnydRowPad) and kernels_mfma.h.  Text and not a function
 // template: inside a __device__ __forceinline__ function the compiler simplifies the body on its own before it inlines it, and
 // the plain kernel comes out with other block placement and register numbers (make devasm + tools/devasm_diff.py show it);
 // that kernel's instructions are to stay what they are.
 // BIAS: per staging tile a lane loads the bias of its rows p0 + 16 rb + 4 kq + {0..3} once, before the tile's rows have
 // landed (the loads' latency lies under the DMA wait), for both of the wave's query blocks.
+// ROWSETS: a row set per query (ts_search_rowsets).  A lane keeps the set NUMBER of its query of each block (one register per
+// block; the pointer would be two, and this kernel's budget is the plain kernel's: 8 waves per workgroup) and takes the mask
+// pointer from the table only behind s >= thr, where a.row_mask is tested otherwise.
     extern __shared__ __attribute__((aligned(16))) unsigned char srows[];
     const MfmaArgs& a = aa.m;
     constexpr int kRows = 16 * RB;
@@ -32,6 +36,11 @@
     for (int b = 0; b < kAnydNBW; ++b) {
         qid[b] = (wave + kAnydWaves * b) * 16 + r16;
         thr[b] = mfma_level_thr(a, qid[b]);
+    }
+    int qset[ROWSETS ? kAnydNBW : 1];
+    if constexpr (ROWSETS) {
+#pragma unroll
+        for (int b = 0; b < kAnydNBW; ++b) qset[b] = rowsets->set[qid[b]];     // qid < 256: inside the table
     }
 
     const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) unsigned char*)srows;
@@ -130,6 +139,15 @@
                         const float s = acc[rb][g];
                         const int64_t row = p0 + 16 * rb + 4 * kq + g;
                         // padding rows of the last tile, and the metadata filter: tested only for scores that pass the threshold
+                        if constexpr (ROWSETS) {
+                            if (s >= thr[b] && row < a.n) {
+                                const u32* const qmask = qset[b] < 0 ? nullptr : rowsets->mask[qset[b]];
+                                if (!qmask || ((qmask[row >> 5] >> (row & 31)) & 1u)) {
+                                    const u32 pos = atomicAdd(&a.count[qid[b]], 1u);
+                                    if (pos < (u32)a.cap) a.cand[(int64_t)qid[b] * a.cap + pos] = make_key(s, (u32)row);
+                                }
+                            }
+                        } else
                         if (s >= thr[b] && row < a.n && (!a.row_mask || ((a.row_mask[row >> 5] >> (row & 31)) & 1u))) {
                             const u32 pos = atomicAdd(&a.count[qid[b]], 1u);
                             if (pos < (u32)a.cap) a.cand[(int64_t)qid[b] * a.cap + pos] = make_key(s, (u32)row);

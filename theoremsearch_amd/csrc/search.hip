@@ -518,6 +518,208 @@ extern "C" int ts_search_biased_rowset(ts_index* ix, const void* queries, int q_
                        &b, rows->allowed);
 }
 
+// ---- ts_search_rowsets: a row set per query (rowsets_plan.h holds the rules) ---------------------------------------------------
+// The shared pass for `nq` queries that all ride it (validated, routed): search_impl's stages with a mask per query.  which[q]:
+// the set of query q.  Blocks of kRowsetsBlock queries; each block waits for its re-run list (search_mfma.hip: rowsets_rerun).
+static int rowsets_pass(ts_index* ix, const void* queries, int q_dtype, int q_on_device, int32_t nq, int32_t k, const ts_rowset* const* sets,
+                        const int32_t* which, float* out_scores, int64_t* out_idx, int out_on_device, void* stream, ts_rowsets_stats* stats) {
+    std::lock_guard<std::mutex> lock(ix->mu);
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st;
+    StreamScope scope;
+    TS_TRY(enter_stream(ix, stream, &st, &scope));
+    TS_TRY(ensure_search_scratch(ix, k));
+    RowsetsCall call;
+    call.sets = sets;
+    struct Scope {      // the sets are properties of this call only
+        ts_index* ix;
+        ~Scope() { ix->active_rowsets = nullptr; ix->active_mask = nullptr; }
+    } call_scope{ix};
+    ix->active_rowsets = &call;
+    float* dscores = out_scores;
+    int64_t* didx = out_idx;
+    TS_TRY(result_buffers(ix, (size_t)nq * k, out_on_device, &dscores, &didx));
+    QueryFeed feed;
+    TS_TRY(query_feed_open(&feed, ix, queries, q_dtype, q_on_device, nq, true, st));
+    const int block = mfma_block_queries(ix, nq);
+    if (block != kRowsetsBlock) return fail(TS_ERR_INTERNAL, "a block of the row-set pass holds %d queries, not %d", kRowsetsBlock, block);
+    for (int q0 = 0; q0 < nq; q0 += block) {
+        const int nb = std::min(block, nq - q0);
+        const void* qsrc = feed.at(q0);
+        call.which = which + q0;
+        // device queries that already are what the kernels multiply are read where they lie (search_blocks' rule)
+        if (feed.on_device && feed.q_dtype == ix->dtype && ix->metric == TS_METRIC_IP && ix->ld == ix->d && nb == block && ((uintptr_t)qsrc & 15) == 0) {
+            TS_TRY(mfma_search(ix, nb, k, dscores + (size_t)q0 * k, didx + (size_t)q0 * k, st, nullptr, qsrc, true));
+            continue;
+        }
+        TS_TRY(query_feed_block(feed, q0, nb));
+        TS_TRY(mfma_search(ix, nb, k, dscores + (size_t)q0 * k, didx + (size_t)q0 * k, st, nullptr, ix->qstore, false));
+    }
+    if (stats) {
+        stats->fallback_queries += call.fallback_queries;
+        stats->candidates += call.candidates;
+    }
+    if (out_on_device) return TS_OK;
+    HIP_TRY(hipMemcpyAsync(out_scores, dscores, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out_idx, didx, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return TS_OK;
+}
+
+// Some of a call's queries (`sel`, ascending) as a call of their own: gathered into contiguous rows where the caller's lie (host or
+// device), run(queries, out_scores, out_idx), and the result rows put back at their places.  Device temporaries are the call's own
+// (the per-handle scratch belongs to the searches `run` makes); the stream is drained before they go.
+template <class Run>
+static int rowsets_subset(ts_index* ix, const std::vector<int32_t>& sel, const void* queries, size_t q_row_bytes, int q_on_device, int32_t nq,
+                          int32_t k, float* out_scores, int64_t* out_idx, int out_on_device, void* stream, Run&& run) {
+    const size_t m = sel.size();
+    if (m == 0) return TS_OK;
+    if (m == (size_t)nq) return run(queries, out_scores, out_idx);
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = stream ? (hipStream_t)stream : ix->stream;
+    std::vector<unsigned char> hq;
+    std::vector<float> hs;
+    std::vector<int64_t> hi;
+    DevBuf dq, dout;
+    const void* q_sub = nullptr;
+    float* s_sub = nullptr;
+    int64_t* i_sub = nullptr;
+    int rc = TS_OK;
+    auto enqueue = [&]() -> int {
+        if (q_on_device) {
+            DEV_TRY(dq.need(m * q_row_bytes));
+            for (size_t j = 0; j < m; ++j)
+                HIP_TRY(hipMemcpyAsync(dq.as<unsigned char>() + j * q_row_bytes, (const unsigned char*)queries + (size_t)sel[j] * q_row_bytes, q_row_bytes,
+                                       hipMemcpyDeviceToDevice, st));
+            q_sub = dq;
+        } else {
+            hq.resize(m * q_row_bytes);
+            for (size_t j = 0; j < m; ++j) memcpy(hq.data() + j * q_row_bytes, (const unsigned char*)queries + (size_t)sel[j] * q_row_bytes, q_row_bytes);
+            q_sub = hq.data();
+        }
+        if (out_on_device) {
+            DEV_TRY(dout.need(m * k * 12));
+            i_sub = dout.as<int64_t>();
+            s_sub = (float*)(i_sub + m * k);
+        } else {
+            hs.resize(m * k);
+            hi.resize(m * k);
+            s_sub = hs.data();
+            i_sub = hi.data();
+        }
+        TS_TRY(run(q_sub, s_sub, i_sub));
+        for (size_t j = 0; j < m; ++j) {
+            if (out_on_device) {
+                HIP_TRY(hipMemcpyAsync(out_scores + (size_t)sel[j] * k, s_sub + j * k, (size_t)k * 4, hipMemcpyDeviceToDevice, st));
+                HIP_TRY(hipMemcpyAsync(out_idx + (size_t)sel[j] * k, i_sub + j * k, (size_t)k * 8, hipMemcpyDeviceToDevice, st));
+            } else {
+                memcpy(out_scores + (size_t)sel[j] * k, s_sub + j * k, (size_t)k * 4);
+                memcpy(out_idx + (size_t)sel[j] * k, i_sub + j * k, (size_t)k * 8);
+            }
+        }
+        return TS_OK;
+    };
+    rc = enqueue();
+    // every path drains the stream before the device temporaries are freed
+    if (q_on_device || out_on_device) {
+        const hipError_t e = hipStreamSynchronize(st);
+        if (rc == TS_OK && e != hipSuccess) rc = fail(TS_ERR_HIP, "stream synchronize failed: %s", hipGetErrorString(e));
+    }
+    return rc;
+}
+
+// the padding of a query whose set allows nothing: -inf / -1, without a launch of the search
+static int rowsets_padding(ts_index* ix, const std::vector<int32_t>& sel, int32_t k, float* out_scores, int64_t* out_idx, int out_on_device,
+                           void* stream) {
+    std::vector<float> s((size_t)k, -INFINITY);
+    std::vector<int64_t> i((size_t)k, -1);
+    if (!out_on_device) {
+        for (int32_t q : sel) {
+            memcpy(out_scores + (size_t)q * k, s.data(), (size_t)k * 4);
+            memcpy(out_idx + (size_t)q * k, i.data(), (size_t)k * 8);
+        }
+        return TS_OK;
+    }
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = stream ? (hipStream_t)stream : ix->stream;
+    for (int32_t q : sel) {
+        HIP_TRY(hipMemcpyAsync(out_scores + (size_t)q * k, s.data(), (size_t)k * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(out_idx + (size_t)q * k, i.data(), (size_t)k * 8, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));      // the two host rows are locals
+    return TS_OK;
+}
+
+extern "C" int ts_search_rowsets(ts_index* ix, const void* queries, int q_dtype, int q_on_device, int32_t nq, int32_t k,
+                                 const ts_rowset* const* sets, int32_t nsets, const int32_t* which, float* out_scores, int64_t* out_idx,
+                                 int out_on_device, void* stream, int algo, ts_rowsets_stats* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (const char* bad = rowsets_args_invalid(queries, out_scores, out_idx, sets, which, q_dtype, nq, k, nsets, algo))
+        return fail(TS_ERR_INVALID, "ts_search_rowsets (nq = %d, k = %d, nsets = %d): %s", nq, k, nsets, bad);
+    std::vector<RowsetsSet> info((size_t)std::max(nsets, 1));
+    for (int s = 0; s < nsets; ++s) {
+        const ts_rowset* r = sets[s];
+        info[(size_t)s] = r ? RowsetsSet{true, r->n, r->allowed, r->device} : RowsetsSet{false, 0, 0, 0};
+    }
+    if (const char* bad = rowsets_sets_invalid(info.data(), nsets, which, nq, ix != nullptr, ix ? ix->n : 0, ix ? ix->device : 0))
+        return fail(TS_ERR_INVALID, "ts_search_rowsets (nq = %d, nsets = %d, index of %lld rows): %s", nq, nsets, (long long)(ix ? ix->n : 0), bad);
+    if (ix->id_map) return fail(TS_ERR_UNSUPPORTED, "a row set per query on a subset index");
+    if (nq == 0) return TS_OK;
+    RowsetsIndex ri;
+    ri.dtype = ix->dtype;
+    ri.d = ix->d;
+    ri.n = ix->n;
+    ri.unpadded = ix->ld == ix->d;
+    ri.two_level = two_level_search(ix);
+    ri.f32_matrix = ix->knobs.get(K_MFMA_F32, 16) != 0;
+    ri.mfma_min_rows = ix->knobs.get(K_MFMA_MIN_ROWS, 16384);
+    ri.scan_max_knob = ix->knobs.get(K_SCAN_MAX_QUERIES, bias_scan_max_queries(ix->dtype));
+    const RowsetsRoute route = rowsets_route(ri, info.data(), nsets, which, nq, k, algo);
+    if (route.kind == kRowsetsUnsupported) return fail(TS_ERR_UNSUPPORTED, "%s", route.unsupported);
+    if (stats) stats->sets_used = route.sets_used;
+    if (route.kind == kRowsetsSearchEx || route.kind == kRowsetsSearchRowset) {
+        const ts_rowset* one = route.kind == kRowsetsSearchRowset ? sets[route.one_set] : nullptr;
+        ts_search_stats ss;
+        TS_TRY(search_core(ix, queries, q_dtype, q_on_device, nq, k, out_scores, out_idx, out_on_device, stream, algo, &ss,
+                           one ? (const uint32_t*)one->mask : nullptr, one ? one->allowed : -1));
+        if (stats) {
+            stats->algo = ss.algo;
+            stats->scan_queries = nq;
+            stats->scan_calls = 1;
+            stats->fallback_queries = ss.fallback_queries;
+            stats->candidates = ss.candidates;
+        }
+        return TS_OK;
+    }
+    const size_t q_row_bytes = (size_t)ix->d * (q_dtype == TS_BF16 ? 2 : 4);
+    if (stats) {
+        stats->algo = route.pass.empty() ? TS_ALGO_SCAN : TS_ALGO_MFMA;
+        stats->pass_queries = (int32_t)route.pass.size();
+        stats->scan_queries = route.scan_queries();
+        stats->scan_calls = route.scan_calls();
+    }
+    std::vector<int32_t> which_pass(route.pass.size());
+    for (size_t j = 0; j < route.pass.size(); ++j) which_pass[j] = which[route.pass[j]];
+    TS_TRY(rowsets_subset(ix, route.pass, queries, q_row_bytes, q_on_device, nq, k, out_scores, out_idx, out_on_device, stream,
+                          [&](const void* q, float* os, int64_t* oi) {
+                              return rowsets_pass(ix, q, q_dtype, q_on_device, (int32_t)route.pass.size(), k, sets, which_pass.data(), os, oi,
+                                                  out_on_device, stream, stats);
+                          }));
+    for (const RowsetsGroup& g : route.groups) {
+        if (g.empty) {
+            TS_TRY(rowsets_padding(ix, g.queries, k, out_scores, out_idx, out_on_device, stream));
+            continue;
+        }
+        const ts_rowset* one = g.set >= 0 ? sets[g.set] : nullptr;
+        TS_TRY(rowsets_subset(ix, g.queries, queries, q_row_bytes, q_on_device, nq, k, out_scores, out_idx, out_on_device, stream,
+                              [&](const void* q, float* os, int64_t* oi) {
+                                  return search_core(ix, q, q_dtype, q_on_device, (int32_t)g.queries.size(), k, os, oi, out_on_device, stream,
+                                                     route.group_algo, nullptr, one ? (const uint32_t*)one->mask : nullptr, one ? one->allowed : -1);
+                              }));
+    }
+    return TS_OK;
+}
+
 template <int DT, int CH, int G>
 static int launch_rank_spec(int qb, int grid, hipStream_t st, const RankArgs& a) {
     if (qb == 4) rank_kernel<DT, CH, G, 4><<<grid, 256, 0, st>>>(a);

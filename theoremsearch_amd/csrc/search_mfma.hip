@@ -2,7 +2,9 @@
 // select, the full pass (launch_mfma*.hip hold the kernel instantiations), the final select, the exact re-run.
 // mfma_search runs the stages in order: mfma_plan (what this search is), mfma_scratch (the handle's buffers), then per level
 // mfma_sample (level 0 as the dense sample) or mfma_level (a matrix kernel + its select).  A biased search (ts_search_biased_ex)
-// is the general-width form of all this at any served width, with its own sample select (kernels_sample_biased.h).
+// is the general-width form of all this at any served width, with its own sample select (kernels_sample_biased.h).  A search with
+// a row set per query (ts_search_rowsets: ix->active_rowsets) is that form too, with the row-set kernels of
+// launch_mfma_anyd_rowsets.hip, a table per block of queries (rowsets_table) and a re-run per set (rowsets_rerun).
 //
 // What the plan fixes, as tests/threshold_common.py restates it and tests/test_threshold_gpu.py observes it: level i visits
 // tiles j * stride_i, so the sample is the rows 32 j stride + r (r < 32) below n - a partial last tile gives its real rows
@@ -28,27 +30,7 @@ struct Level { int64_t stride, ntiles; int run; };
 // kk * rows(i+1) / rows(i): the full pass is planned for `target` candidates (few trips through
 // the append path), the sparser levels for up to kCandCap / 4 (they are short anyway); the first
 // level is small enough to run unthresholded.
-// Inverse of the standard normal CDF (Acklam's rational approximation, |error| < 1.2e-9): the z with P(X > z) = p.
-static double normal_tail_z(double p) {
-    if (p <= 0.0) return 8.0;
-    if (p >= 0.5) return 0.0;
-    const double q = std::sqrt(-2.0 * std::log(p));
-    static const double c[] = {-7.784894002430293e-03, -3.223964580411365e-01, -2.400758277161838e+00,
-                               -2.549732539343734e+00, 4.374664141464968e+00, 2.938163982698783e+00};
-    static const double d[] = {7.784695709041462e-03, 3.224671290700398e-01, 2.445134137142996e+00, 3.754408661907416e+00};
-    if (p < 0.02425)
-        return -(((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) /
-               ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1.0);
-    // central region
-    static const double a[] = {-3.969683028665376e+01, 2.209460984245205e+02, -2.759285104469687e+02,
-                               1.383577518672690e+02, -3.066479806614716e+01, 2.506628277459239e+00};
-    static const double b[] = {-5.447609879822406e+01, 1.615858368580409e+02, -1.556989798598866e+02,
-                               6.680131188771972e+01, -1.328068155288572e+01};
-    const double x = (1.0 - p) - 0.5, r = x * x;
-    return (((((a[0] * r + a[1]) * r + a[2]) * r + a[3]) * r + a[4]) * r + a[5]) * x /
-           (((((b[0] * r + b[1]) * r + b[2]) * r + b[3]) * r + b[4]) * r + 1.0);
-}
-
+// (normal_tail_z, the inverse of the standard normal CDF the estimates use: rowsets_plan.h, which restates them per query)
 static int mfma_target_cands(const Knobs& kn, int64_t n, int kk) {
     // Cost model fitted on 10M / 1.25M x 768, batch 256: a sample row costs ~0.4 ns, a candidate of the next
     // level ~0.27 us per query (the append path is ~1 us of wave time).  Minimising kk * N * c_row / F + c_cand * F
@@ -118,9 +100,11 @@ static std::vector<Level> plan_levels(const Knobs& kn, int64_t n, int kk, bool s
 // queries per launch, full pass only, shared lists only; no screen, pairs, balancing or private lists).
 static bool biased_search(const ts_index* ix) { return ix->active_bias_matrix; }
 // (the k-chunked kernel of the wider rows is the same form of search: kernels_mfma_wide.h)
-static bool general_width(const ts_index* ix) { return anyd_index(ix) || wide_index(ix) || biased_search(ix); }
+// ... or the shared pass of ts_search_rowsets (a row set per query): the general-width kernel again, at the biased search's widths
+static bool rowsets_search(const ts_index* ix) { return ix->active_rowsets != nullptr; }
+static bool general_width(const ts_index* ix) { return anyd_index(ix) || wide_index(ix) || biased_search(ix) || rowsets_search(ix); }
 static bool mfma_pairs(const ts_index* ix, int nq) {
-    return !biased_search(ix) && ix->dtype == TS_BF16 && ix->d == 1024 && nq > 192 && use_shape16(ix) && two_level_search(ix) &&
+    return !biased_search(ix) && !rowsets_search(ix) && ix->dtype == TS_BF16 && ix->d == 1024 && nq > 192 && use_shape16(ix) && two_level_search(ix) &&
            ix->knobs.get(K_MFMA_PAIR, 1) != 0 && mfma_grid(ix) % 16 == 0;
 }
 
@@ -137,7 +121,7 @@ static bool screen_diag_variant(int variant) {
 // pass (mfma_plan) and for the queries a launch holds (mfma_block_queries).
 static bool mfma_screened(const ts_index* ix) {
     const int variant = ix->knobs.get(K_MFMA_VARIANT, 0);
-    return !biased_search(ix) && use_shape16(ix) && (variant == kVariantProduct || screen_diag_variant(variant)) && thresholded_pass(ix) && screen_usable(ix);
+    return !biased_search(ix) && !rowsets_search(ix) && use_shape16(ix) && (variant == kVariantProduct || screen_diag_variant(variant)) && thresholded_pass(ix) && screen_usable(ix);
 }
 
 int mfma_block_queries(const ts_index* ix, int nq) {
@@ -192,6 +176,7 @@ struct MfmaPlan {
     bool anyd;                  // the general-width kernel (kernels_mfma_anyd.h): full pass only, shared lists only, no screen / pairs / balancing
     bool wide;                  // ... at a width of wide_plan.h: the k-chunked pass and sample (kernels_mfma_wide.h), biased or not
     bool biased;                // ... with the call's bias term in its epilogue, and the biased sample select (any served width)
+    bool rowsets;               // ... with a row set per query (ts_search_rowsets): pop, z_tail, tail_p and min_fill come per query from the block's table
     bool shape16, statistical, dense_sample, dense0;
     bool screen_diag, screen, screen_rider, ksplit_form, pair;
     int nq_launch, groups, nb16;
@@ -210,8 +195,9 @@ static MfmaPlan mfma_plan(const ts_index* ix, int nq, int k) {
     p.kk = std::max(k, ix->knobs.get(K_MFMA_MIN_RANK, 1));
     p.variant = ix->knobs.get(K_MFMA_VARIANT, 0);
     p.biased = biased_search(ix);
+    p.rowsets = rowsets_search(ix);
     p.anyd = general_width(ix);
-    p.wide = wide_index(ix);
+    p.wide = wide_index(ix) && !p.rowsets;                // (the routing keeps the k-chunked widths off the shared pass)
     p.shape16 = !p.anyd && use_shape16(ix);               // (false for the general-width form, and with it screen, pair and balance)
     p.nq_launch = mfma_block_queries(ix, nq);
     p.groups = p.shape16 ? 0 : p.nq_launch / 128;
@@ -357,7 +343,8 @@ static int mfma_sample(ts_index* ix, const MfmaPlan& p, int nq, const void* qmat
     const int slds = sample_lds_bytes(wg_rows, (int)(ix->ld * ix->elem()));
     constexpr int kSampleLdsMax = 144 * 1024;   // dynamic part; the kernel also has a few hundred static bytes (rebalance_tiles)
     static_assert(kSampleLdsMax == kWideSampleLdsLimit, "wide_plan.h restates the sample's limit");
-    if (p.wide) TS_TRY(launch_sample_wide(ix, sgrid, st, sa));       // rows staged k-chunk by k-chunk: its LDS does not follow the width
+    if (p.rowsets) TS_TRY(launch_sample_rowsets(ix, sgrid, slds, st, sa));          // liveness per (sample position, query): no riders
+    else if (p.wide) TS_TRY(launch_sample_wide(ix, sgrid, st, sa));       // rows staged k-chunk by k-chunk: its LDS does not follow the width
     else if (slds > kSampleLdsMax) return fail(TS_ERR_INTERNAL, "threshold sample: rows of %lld bytes do not fit the LDS", (long long)(ix->ld * ix->elem()));
     else if (f32) TS_TRY((launch_lds<sample_scores_kernel<true, 2>, kSampleLdsMax>(ix->device, sgrid, 256, slds, st, sa)));
     else TS_TRY((launch_lds<sample_scores_kernel<false, 2>, kSampleLdsMax>(ix->device, sgrid, 256, slds, st, sa)));
@@ -393,6 +380,7 @@ static int mfma_sample(ts_index* ix, const MfmaPlan& p, int nq, const void* qmat
         if (p.kk <= 64) return launch_lds<sample_select_biased_kernel<1>>(ix->device, nq, kLevelThreads, kBiasSelectLds, st, b);
         return launch_lds<sample_select_biased_kernel<4>>(ix->device, nq, kLevelThreads, kBiasSelectLds, st, b);
     }
+    if (p.rowsets) return launch_sample_select_rowsets(ix, nq, st, l, ix->sample, sa.row_stride);     // z_tail, tail_p, z_sel: the table's
     sample_select_fast_kernel<kSelThreads><<<nq, kSelThreads, 0, st>>>(l, ix->sample, sa.row_stride, z_sel);
     HIP_TRY(hipGetLastError());
     return TS_OK;
@@ -507,7 +495,8 @@ static int mfma_level(ts_index* ix, const MfmaPlan& p, size_t i, int nq, int k, 
     if (p.anyd && !full_pass) return fail(TS_ERR_INTERNAL, "the general-width matrix kernel has no sparse level");
     hipEvent_t stop = full_pass ? prof_begin(ix, st, ix->n) : nullptr;  // only the full pass is bracketed
     int rc;
-    if (p.wide) rc = p.biased ? launch_pass_mfma_wide_biased(ix, p.grid, st, a) : launch_pass_mfma_wide(ix, p.grid, st, a);
+    if (p.rowsets) rc = launch_pass_mfma_anyd_rowsets(ix, p.grid, st, a);
+    else if (p.wide) rc = p.biased ? launch_pass_mfma_wide_biased(ix, p.grid, st, a) : launch_pass_mfma_wide(ix, p.grid, st, a);
     else if (p.biased) rc = launch_pass_mfma_anyd_biased(ix, p.grid, st, a);
     else if (p.anyd) rc = launch_pass_mfma_anyd(ix, p.grid, st, a);
     else if (p.screen && full_pass) rc = screen_full_pass(ix, p.nb16, nq, p.grid, p.screen_diag ? p.variant : kVariantProduct, p.ksplit_form, st, a);
@@ -548,8 +537,81 @@ static int mfma_level(ts_index* ix, const MfmaPlan& p, size_t i, int nq, int k, 
     l.fb_count = ix->fb_count;
     l.stat_q = ix->stat;
     l.nq = nq;
+    if (p.rowsets) return launch_level_select_rowsets(ix, nq, st, l);      // min_fill: the table's, per query
     if (p.kk <= 64) return launch_lds<level_select_kernel<1>>(ix->device, nq, kLevelThreads, kLevelLds, st, l);
     return launch_lds<level_select_kernel<4>>(ix->device, nq, kLevelThreads, kLevelLds, st, l);
+}
+
+// ts_search_rowsets: the block's table (rowsets_plan.h: RowsetsTable) from the call's sets and this plan, made on the host and
+// uploaded before the block's first launch.  The host copy is the handle's: the previous block's upload has run (every block
+// ends by waiting for its re-run list).
+static int rowsets_table(ts_index* ix, const MfmaPlan& p, int nq, int k, hipStream_t st) {
+    const RowsetsCall& call = *ix->active_rowsets;
+    constexpr size_t kBytes = sizeof(RowsetsTable) + 2 * kRowsetsBlock * sizeof(int);
+    DEV_TRY(ix->rowsets_dev.need(kBytes));
+    ix->rowsets_host.resize(kBytes);
+    RowsetsTable* t = reinterpret_cast<RowsetsTable*>(ix->rowsets_host.data());
+    const bool estimate = p.statistical && p.lv.size() == 2;
+    const bool tail_fit = ix->knobs.get(K_MFMA_TAIL_FIT, 1) != 0;
+    for (int s = 0; s < kRowsetsBlock; ++s) t->mask[s] = nullptr;
+    for (int q = 0; q < kRowsetsBlock; ++q) {
+        const int32_t s = q < nq ? call.which[q] : -1;
+        const int64_t pop = s < 0 ? ix->n : call.sets[s]->allowed;
+        if (s >= 0) t->mask[s] = call.sets[s]->mask;
+        const RowsetsNumbers num = rowsets_numbers(pop, ix->n, k, p.kk, p.stat_cands, p.sample_rows, kCandCap, estimate, tail_fit);
+        t->z_tail[q] = num.z_tail;
+        t->tail_p[q] = num.tail_p;
+        t->min_fill[q] = num.min_fill;
+        t->z_sel[q] = rowsets_z_sel(pop, ix->n, p.kk, num.tail_p, p.sample_rows);
+        t->set[q] = s;
+    }
+    HIP_TRY(hipMemcpyAsync(ix->rowsets_dev, t, sizeof(RowsetsTable), hipMemcpyHostToDevice, st));
+    return TS_OK;
+}
+
+// ... and its exact re-run: the final select's list is read back, grouped by set on the host, and each group runs through the scan
+// behind its own set (one launch per set that has a query to re-run; none in the usual case).  Waits for the stream.
+static int rowsets_rerun(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx, hipStream_t st, const void* qmat, bool in_place) {
+    RowsetsCall& call = *ix->active_rowsets;
+    int fb = 0;
+    std::vector<int> list((size_t)kRowsetsBlock);
+    std::vector<u32> cands((size_t)nq);
+    HIP_TRY(hipMemcpyAsync(&fb, ix->fb_count, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(list.data(), ix->fb_list, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(cands.data(), ix->stat, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (u32 c : cands) call.candidates += c;
+    if (fb < 0 || fb > nq) return fail(TS_ERR_INTERNAL, "the re-run list of a row-set pass holds %d of %d queries", fb, nq);
+    call.fallback_queries += fb;
+    if (fb == 0) return TS_OK;
+    for (int i = 0; i < fb; ++i)
+        if (list[i] < 0 || list[i] >= nq) return fail(TS_ERR_INTERNAL, "the re-run list of a row-set pass names query %d of %d", list[i], nq);
+    std::stable_sort(list.begin(), list.begin() + fb, [&](int x, int y) { return call.which[x] < call.which[y]; });
+    // lists [256] | counts [256] behind the table, both in the handle's host copy
+    int* hl = reinterpret_cast<int*>(ix->rowsets_host.data() + sizeof(RowsetsTable));
+    int* hc = hl + kRowsetsBlock;
+    int* dl = reinterpret_cast<int*>(ix->rowsets_dev.as<unsigned char>() + sizeof(RowsetsTable));
+    int* dc = dl + kRowsetsBlock;
+    int ngroups = 0;
+    for (int i = 0; i < fb; ++i) {
+        hl[i] = list[i];
+        if (i == 0 || call.which[list[i]] != call.which[list[i - 1]]) hc[ngroups++] = 0;
+        ++hc[ngroups - 1];
+    }
+    HIP_TRY(hipMemcpyAsync(dl, hl, (size_t)fb * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dc, hc, (size_t)ngroups * 4, hipMemcpyHostToDevice, st));
+    int rc = TS_OK;
+    for (int g = 0, at = 0; g < ngroups && rc == TS_OK; at += hc[g], ++g) {
+        const int32_t s = call.which[hl[at]];
+        ix->active_mask = s < 0 ? nullptr : (const u32*)call.sets[s]->mask;
+        if (!in_place) rc = scan_search(ix, nq, k, out_scores, out_idx, dl + at, dc + g, st);
+        else if (ix->dtype == TS_F32) rc = scan_search(ix, nq, k, out_scores, out_idx, dl + at, dc + g, st, (const float*)qmat);
+        else rc = scan_search(ix, nq, k, out_scores, out_idx, dl + at, dc + g, st, nullptr, (const unsigned short*)qmat);
+    }
+    ix->active_mask = nullptr;
+    TS_TRY(rc);
+    HIP_TRY(hipStreamSynchronize(st));       // the lists are the handle's: the next block writes them
+    return TS_OK;
 }
 
 // `qmat`: the queries as the kernels multiply them (storage dtype, row stride d = ld, a whole launch's worth of rows):
@@ -558,6 +620,7 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
                        const void* qmat, bool in_place) {
     const MfmaPlan p = mfma_plan(ix, nq, k);
     TS_TRY(mfma_scratch(ix, p, st));
+    if (p.rowsets) TS_TRY(rowsets_table(ix, p, nq, k, st));
     if (p.screen) TS_TRY(screen_prepare(ix, qmat, p.nq_launch, !(p.dense0 && p.screen_rider), st));
     for (size_t i = 0; i < p.lv.size(); ++i) {
         if (i == 0 && p.dense0) TS_TRY(mfma_sample(ix, p, nq, qmat, st));
@@ -568,13 +631,14 @@ int mfma_search(ts_index* ix, int nq, int k, float* out_scores, int64_t* out_idx
     ix->rebalance_pending = p.balance;
     ix->rebalance_grid = p.wgs;
     ix->rebalance_in_rerun = !(p.dense_sample && p.lv.size() == 2);
-    // exact fall-back for queries that lost candidates (device-side count; one empty launch when 0)
-    if (!in_place) TS_TRY(scan_search(ix, nq, k, out_scores, out_idx, ix->fb_list, ix->fb_count, st));
-    else if (ix->dtype == TS_F32) TS_TRY(scan_search(ix, nq, k, out_scores, out_idx, ix->fb_list, ix->fb_count, st, (const float*)qmat));
-    else TS_TRY(scan_search(ix, nq, k, out_scores, out_idx, ix->fb_list, ix->fb_count, st, nullptr, (const unsigned short*)qmat));
     if (stats) {
         stats->levels = (int)p.lv.size();
         stats->screened = p.screen ? 1 : 0;
     }
+    if (p.rowsets) return rowsets_rerun(ix, nq, k, out_scores, out_idx, st, qmat, in_place);
+    // exact fall-back for queries that lost candidates (device-side count; one empty launch when 0)
+    if (!in_place) TS_TRY(scan_search(ix, nq, k, out_scores, out_idx, ix->fb_list, ix->fb_count, st));
+    else if (ix->dtype == TS_F32) TS_TRY(scan_search(ix, nq, k, out_scores, out_idx, ix->fb_list, ix->fb_count, st, (const float*)qmat));
+    else TS_TRY(scan_search(ix, nq, k, out_scores, out_idx, ix->fb_list, ix->fb_count, st, nullptr, (const unsigned short*)qmat));
     return TS_OK;
 }

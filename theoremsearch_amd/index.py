@@ -276,6 +276,59 @@ class TheoremIndex:
                                           C.c_void_p(out_scores_ptr), C.c_void_p(out_idx_ptr), 1,
                                           C.c_void_p(stream), _ALGOS[algo], None))
 
+    # -- a row set per query ----------------------------------------------------------------
+    @staticmethod
+    def _rowsets_args(rowsets, which, nq):
+        """The handle array and the ``which`` array of ``ts_search_rowsets`` (both must outlive the call)."""
+        rowsets = list(rowsets)
+        if len(rowsets) > _ffi.TS_MAX_ROWSETS:
+            raise ValueError(f"{len(rowsets)} row sets in one call, at most {_ffi.TS_MAX_ROWSETS}")
+        for r in rowsets:
+            if r is not None and not isinstance(r, RowSet):
+                raise TypeError("rowsets holds metadata.RowSet objects (MetaTable.eval / MetaTable.eval_many)")
+        w = np.ascontiguousarray(np.asarray(which).reshape(-1), dtype=np.int32)
+        if w.shape[0] != nq:
+            raise ValueError(f"which has {w.shape[0]} entries for {nq} queries")
+        handles = (C.c_void_p * max(len(rowsets), 1))(*[r.handle if r is not None else None for r in rowsets])
+        return rowsets, handles, w
+
+    @staticmethod
+    def _rowsets_stats(stats) -> dict:
+        return {"algo": stats.algo, "sets_used": stats.sets_used, "pass_queries": stats.pass_queries, "scan_queries": stats.scan_queries,
+                "scan_calls": stats.scan_calls, "fallback_queries": stats.fallback_queries, "candidates": stats.candidates}
+
+    def search_rowsets(self, queries, k: int, rowsets, which, algo: str = "auto", return_stats: bool = False):
+        """`search` with a row set per query (``ts_search_rowsets``): query ``i`` is searched behind ``rowsets[which[i]]``, or
+        behind no filter where ``which[i] == -1``.  ``rowsets``: a sequence of `metadata.RowSet` (at most 256); ``which``: an int
+        array, one entry per query.  Each output row is what `search` returns for that query alone with ``mask=`` its set; a batch
+        with several dense sets crosses the corpus once.  Returns ``(scores, indices)`` and, with ``return_stats``, the routing's
+        counters (``algo, sets_used, pass_queries, scan_queries, scan_calls, fallback_queries, candidates``)."""
+        if self._cpu_rows is not None:
+            raise ValueError("the host-only index (device=-1) has one algorithm and no filters")
+        q = _host_rows(queries)
+        if q.shape[1] != self.d:
+            raise ValueError(f"queries have d={q.shape[1]}, index has d={self.d}")
+        nq, k = q.shape[0], int(k)
+        rowsets, handles, w = self._rowsets_args(rowsets, which, nq)
+        scores = np.empty((nq, max(k, 0)), dtype=np.float32)
+        idx = np.empty((nq, max(k, 0)), dtype=np.int64)
+        stats = _ffi.RowsetsStats()
+        _ffi.check(self._lib.ts_search_rowsets(self._h, _ffi.as_ptr(q), _ffi.np_dtype_code(q), 0, nq, k, handles, len(rowsets),
+                                               _ffi.as_ptr(w), _ffi.as_ptr(scores), _ffi.as_ptr(idx), 0, None, _ALGOS[algo], C.byref(stats)))
+        return (scores, idx, self._rowsets_stats(stats)) if return_stats else (scores, idx)
+
+    def search_rowsets_device(self, q_ptr: int, q_dtype: str, nq: int, k: int, rowsets, which, out_scores_ptr: int, out_idx_ptr: int,
+                              stream: int = 0, algo: str = "auto") -> dict:
+        """`search_rowsets` on device buffers (queries [nq x d] dense; outputs [nq x k] f32 / i64) on ``stream`` (0 = the index's
+        own); ``which`` stays a host array.  Unlike `search_device` the call WAITS for its pass - the re-run list is read back
+        per block of 256 queries - and returns the routing's counters."""
+        rowsets, handles, w = self._rowsets_args(rowsets, which, int(nq))
+        stats = _ffi.RowsetsStats()
+        _ffi.check(self._lib.ts_search_rowsets(self._h, C.c_void_p(q_ptr), _DTYPES[q_dtype], 1, int(nq), int(k), handles, len(rowsets),
+                                               _ffi.as_ptr(w), C.c_void_p(out_scores_ptr), C.c_void_p(out_idx_ptr), 1, C.c_void_p(stream),
+                                               _ALGOS[algo], C.byref(stats)))
+        return self._rowsets_stats(stats)
+
     # -- grouped search ---------------------------------------------------------------------
     @staticmethod
     def _group_column(meta, column) -> int:

@@ -346,6 +346,32 @@ class MetaTable:
         _ffi.check(self._lib.ts_meta_eval(self._h, arr, len(atoms), C.byref(h), C.c_void_p(stream)))
         return RowSet(h)
 
+    @staticmethod
+    def _program_key(atoms) -> tuple:
+        """A program as a hashable value: equal filter states compile to equal keys."""
+        return tuple((int(a.kind), int(a.col), int(a.lo), int(a.hi), int(a.negate), int(a.group), int(a.set_bits),
+                      None if a.set is None else np.ascontiguousarray(a.set, dtype=np.uint32).tobytes()) for a in atoms)
+
+    def eval_many(self, states, stream: int = 0):
+        """One `RowSet` per DISTINCT program of ``states`` (filter states or programs, one per session) and the ``which``
+        array that names each session's set: ``(rowsets, which)`` as `TheoremIndex.search_rowsets` takes them.  Sessions with
+        the same sidebar state share a set (a ``None`` state is "no filter": ``which`` = -1).  At most 256 distinct states per
+        call (``ts_search_rowsets``' limit), else ``ValueError`` - before anything is evaluated."""
+        programs, keys, which = [], {}, []
+        for st in states:
+            if st is None:
+                which.append(-1)
+                continue
+            atoms = self.compile(st) if isinstance(st, Mapping) else list(st)
+            key = self._program_key(atoms)
+            if key not in keys:
+                if len(programs) == _ffi.TS_MAX_ROWSETS:
+                    raise ValueError(f"more than {_ffi.TS_MAX_ROWSETS} distinct filter states in one call: split the batch")
+                keys[key] = len(programs)
+                programs.append(atoms)
+            which.append(keys[key])
+        return [self.eval(atoms, stream=stream) for atoms in programs], np.asarray(which, dtype=np.int32)
+
     def exclude(self, column, codes, rows=(), base: Optional[RowSet] = None, stream: int = 0) -> RowSet:
         """``base AND NOT (the row's code in column `column` is in codes) AND NOT (the row is in rows)`` as a `RowSet`
         (``ts_rowset_exclude``): "hide these papers", and the mask the grouped search's last stage runs behind.  ``column``: a

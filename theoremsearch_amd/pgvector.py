@@ -175,3 +175,33 @@ def search_batch(index: TheoremIndex, query_vecs, top_k: int, citation_weight: f
         rows.sort(key=lambda r: (-r["score"], -r["similarity"]))
         out.append(rows)
     return out
+
+
+def search_sessions(index: TheoremIndex, query_vecs, top_ks, masks):
+    """The plain queries (citation weight 0) of many sessions in one call: session ``i`` asks for its ``top_ks[i]`` best rows
+    behind ``masks[i]``, a `metadata.RowSet` or None (`MetaTable.eval_many` makes them, shared between sessions with the same
+    sidebar state).  One `TheoremIndex.search_rowsets` at ``max(top_ks)`` - sessions behind different dense filters share one
+    pass over the corpus - and each list cut to its own ``top_k``: a prefix of the canonical top k is the top k of the smaller
+    k.  Returns one list per session, each shaped like the result of `search`."""
+    q = np.asarray(query_vecs, dtype=np.float32)
+    q = q.reshape(1, -1) if q.ndim == 1 else q
+    top_ks = [int(t) for t in top_ks]
+    masks = list(masks)
+    if len(top_ks) != q.shape[0] or len(masks) != q.shape[0]:
+        raise ValueError(f"{q.shape[0]} queries, {len(top_ks)} top_ks and {len(masks)} masks")
+    if not top_ks:
+        return []
+    if min(top_ks) < 1:
+        raise ValueError("every top_k must be at least 1")
+    rowsets, number, which = [], {}, []
+    for m in masks:
+        if m is None:
+            which.append(-1)
+            continue
+        if id(m) not in number:
+            number[id(m)] = len(rowsets)
+            rowsets.append(m)
+        which.append(number[id(m)])
+    scores, idx = index.search_rowsets(q, max(top_ks), rowsets, np.asarray(which, dtype=np.int32))
+    return [[{"row": int(i), "similarity": 1.0 + float(s), "score": 1.0 + float(s)} for s, i in zip(srow[:k], irow[:k]) if i >= 0]
+            for srow, irow, k in zip(scores, idx, top_ks)]
