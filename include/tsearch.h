@@ -410,6 +410,43 @@ int ts_search_rowsets(ts_index *ix, const void *queries, int q_dtype, int q_on_d
                       const ts_rowset *const *sets, int32_t nsets, const int32_t *which, float *out_scores,
                       int64_t *out_idx, int out_on_device, void *stream, int algo, ts_rowsets_stats *stats);
 
+/* ---- a weight and a row set per query: the citation-weighted search of a batch of sessions in one matrix pass -------
+ * ts_search_rowsets for the biased ranking: query q is ranked by fmaf(weights[q], bias[row], score) over the rows
+ * sets[which[q]] allows (every row when which[q] == -1).  `bias`: n floats, host or device, one array for the call;
+ * `weights`: host memory, nq finite floats.  Output row q is what ts_search_biased_rowset defines for query q alone with
+ * weights[q] behind its set (ts_search_biased_ex with no mask for -1): the exact weighted top k of the allowed rows, by
+ * weighted score descending, then id ascending, padded with -inf / -1, ids global; rows whose weighted score is NaN (an
+ * infinite bias under weight 0, a NaN bias) are ranked as the biased search ranks them.  out_sims (optional) receives the
+ * raw similarities, fmaf(-weights[q], bias[row], weighted score), as ts_search_biased.
+ *
+ * Routing (csrc/biased_rowsets_plan.h holds the rules).  A query's CLASS is the pair (which[q],
+ * weights[q] by value):
+ *   - all queries in one class: the call IS ts_search_biased_rowset for that set and weight (ts_search_biased_ex for -1), its
+ *     paths and its bits;
+ *   - otherwise the queries whose set allows at least a tenth of the rows ride ONE pass of the general-width matrix kernel per
+ *     256 of them - the weight of the bias term and the mask taken per query, a threshold per query from its own sample rows,
+ *     its own weight and a histogram of the raw bias over its set's rows (one histogram per distinct set and call), an exact
+ *     re-run behind the query's own set with its own weight for a query the final select rejects - under the conditions of
+ *     ts_search_rowsets' pass (index, width, options, more queries than one scan pass serves), when they span at least two
+ *     classes;
+ *   - every other query is grouped by class, one ts_search_biased_rowset / ts_search_biased_ex call per class under
+ *     TS_ALGO_AUTO; a set that allows nothing returns the padding without a launch.
+ * algo: TS_ALGO_SCAN runs every class on the scan; TS_ALGO_MFMA is refused with TS_ERR_UNSUPPORTED unless every query rides
+ * the pass; a delegated call hands algo on.
+ *
+ * Score bits follow ts_search_rowsets' promise: on the shared pass they are the general-width kernel's single MFMA chain plus
+ * the one fmaf; on a delegated or per-class call they are whatever that call gives.  The exact re-run can cost time, never an
+ * answer.
+ *
+ * TS_ERR_INVALID: NULL bias, NULL weights with nq > 0, a weight that is not finite, and everything ts_search_rowsets rejects.
+ * TS_ERR_UNSUPPORTED: a subset index.  nq == 0 does nothing.  A host bias is copied to the device once per split call.  The
+ * call waits for its pass; the row sets must stay alive until it returns.  `stats`: ts_rowsets_stats with the same meanings
+ * (scan_calls counts the per-class calls). */
+int ts_search_biased_rowsets(ts_index *ix, const void *queries, int q_dtype, int q_on_device, int32_t nq, int32_t k,
+                             const float *bias, int bias_on_device, const float *weights, const ts_rowset *const *sets,
+                             int32_t nsets, const int32_t *which, float *out_scores, float *out_sims, int64_t *out_idx,
+                             int out_on_device, void *stream, int algo, ts_rowsets_stats *stats);
+
 /* ---- grouped search: the k best distinct groups, one row per group ------------------------------------
  * What a user of the search engine ranks is papers and theorems, not rows: a paper contributes tens of rows that lie close
  * together, and theorem_slogan holds several slogans per theorem, which the production query collapses with

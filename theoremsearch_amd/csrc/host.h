@@ -25,6 +25,7 @@
 #include "anyd_plan.h"
 #include "bias_plan.h"
 #include "rowsets_plan.h"
+#include "biased_rowsets_plan.h"
 #include "wide_plan.h"
 #include "encoder_plan.h"
 #include "meta_plan.h"
@@ -183,6 +184,10 @@ struct RowsetsCall {
     const int32_t* which = nullptr;      // [nq of the block]: the set of each query of the block, -1 = every row
     int fallback_queries = 0;            // summed over the blocks so far
     int64_t candidates = 0;
+    // ts_search_biased_rowsets (with ix->active_bias, active_bias_matrix): a weight per query; NULL for ts_search_rowsets
+    const float* weights = nullptr;      // [nq of the block]
+    const int32_t* hist_of = nullptr;    // [nq of the block]: which of the call's histograms of the raw bias is the query's set's
+    int nhists = 0;                      // histograms in ix->bias_sets_hist
 };
 
 struct ts_index : IndexQueue {
@@ -206,6 +211,7 @@ struct ts_index : IndexQueue {
     DevArray<u32> mask_dev;                                  // filtered search: device copy of a host bitmask
     DevArray<float> bias_dev;                                // biased search: device copy of a host bias array
     DevArray<u32> bias_hist;                                 // biased matrix search: histogram of w * bias over the call's rows + its range (kernels_sample_biased.h)
+    DevArray<u32> bias_sets_hist;                            // biased search with a weight and a set per query: [sets][kBiasBins] counts of the raw bias, then the range (kernels_biased_rowsets.h)
     const float* active_bias = nullptr; float active_bias_w = 0.f;   // per-row additive term of the search in progress (under `mu`)
     bool active_bias_matrix = false;                         // ... which runs on the matrix path (ts_search_biased_ex): the biased general-width pass
     DevArray<int64_t> id_map;                                // subset index: local row -> global id (a view of one borrows it)
@@ -217,7 +223,7 @@ struct ts_index : IndexQueue {
     DevArray<void> rank_many_buf;                            // ts_rank_many: slots | keys | counts of one pass of one query block
     const u32* active_mask = nullptr;                        // bitmask of the search in progress (under `mu`)
     RowsetsCall* active_rowsets = nullptr;                   // ts_search_rowsets' shared pass in progress: a mask per query (active_mask is NULL then)
-    DevArray<void> rowsets_dev;                              // ... the block's RowsetsTable, then its re-run lists [256] and their counts [256]
+    DevArray<void> rowsets_dev;                              // ... the block's RowsetsTable (BiasedRowsetsTable under a weight per query), then its re-run lists [256] and their counts [256]
     std::vector<unsigned char> rowsets_host;                 // ... and the host copy both are uploaded from
     int64_t active_allowed = 0;                              // rows that bitmask allows (host masks: counted; a row set's: known; else n)
     Knobs knobs;                                             // env at creation, then ts_index_set_option
@@ -481,6 +487,15 @@ int launch_pass_mfma_anyd_rowsets(const ts_index* ix, int grid, hipStream_t st, 
 int launch_sample_rowsets(const ts_index* ix, dim3 grid, int lds, hipStream_t st, const ts::SampleArgs& sa);
 int launch_sample_select_rowsets(const ts_index* ix, int nq, hipStream_t st, const ts::LevelArgs& l, const float* scores, int row_stride);
 int launch_level_select_rowsets(const ts_index* ix, int nq, hipStream_t st, const ts::LevelArgs& l);
+// ts_search_biased_rowsets (a weight and a row set per query: ix->rowsets_dev holds the block's BiasedRowsetsTable, ix->active_bias
+// the call's bias).  launch_mfma_anyd_biased_rowsets.hip: the pass.  search_mfma.hip: the histograms of the raw bias per set
+// (masks[h]: NULL = every row), the sample select that reads them, and out_sims under a weight per query
+int launch_pass_mfma_anyd_biased_rowsets(const ts_index* ix, int grid, hipStream_t st, const ts::MfmaArgs& a);
+int biased_rowsets_histograms(ts_index* ix, const uint32_t* const* masks, int nhists, hipStream_t st);
+int launch_sample_select_biased_rowsets(const ts_index* ix, int nq, int kk, int nhists, double target, const float* scores, int row_stride,
+                                        int64_t ntiles, int64_t tile_stride, int run, hipStream_t st);
+int launch_unbias_rows(const ts_index* ix, const float* scores, const int64_t* idx, const float* bias, const float* weights, int k, float* sims,
+                       int64_t count, hipStream_t st);
 // launch_mfma_wide.hip: the same two passes and the threshold sample of an index the k-chunked kernels serve (wide_index)
 int launch_pass_mfma_wide(const ts_index* ix, int grid, hipStream_t st, const ts::MfmaArgs& a);
 int launch_pass_mfma_wide_biased(const ts_index* ix, int grid, hipStream_t st, const ts::MfmaArgs& a);

@@ -24,6 +24,8 @@
 //   * mfma_anyd_biased_kernel (ts_search_biased_ex) is the same pass with s = fmaf(w, bias[row], <row, query>) in the epilogue; it
 //     also runs the four hand-laid widths (bias_plan.h: bias_served), since the row length is a run-time value.
 //   * mfma_anyd_rowsets_kernel (ts_search_rowsets) is the same pass with the filter of the epilogue taken per query, at the same widths.
+//   * mfma_anyd_biased_rowsets_kernel (ts_search_biased_rowsets) has both: s = fmaf(w[query], bias[row], <row, query>) with a
+//     weight per query, and the filter per query.
 //
 // Full pass only: tile_stride == 1 and run == 1 (the host guarantees it); the kernel covers rows [0, 32 * ntiles), the
 // allocation is padded to 256 rows, so whole staging tiles are in bounds.  It may be the first level of a search (a tiny
@@ -31,6 +33,7 @@
 #pragma once
 #include "anyd_plan.h"
 #include "rowsets_plan.h"
+#include "biased_rowsets_plan.h"
 #include "kernels_mfma16_ops.h"
 
 namespace ts {
@@ -62,6 +65,8 @@ __global__ void __launch_bounds__(kAnydThreads) mfma_anyd_kernel(AnydArgs aa) {
     const float* const bias = nullptr;
     const float bias_w = 0.0f;
     const RowsetsTable* const rowsets = nullptr;
+    constexpr bool QWEIGHT = false;
+    const float* const qweight = nullptr;
 #include "kernels_mfma_anyd_pass.inc"
 }
 
@@ -73,6 +78,8 @@ __global__ void __launch_bounds__(kAnydThreads) mfma_anyd_biased_kernel(AnydBias
     const float* const bias = ba.bias;
     const float bias_w = ba.w;
     const RowsetsTable* const rowsets = nullptr;
+    constexpr bool QWEIGHT = false;
+    const float* const qweight = nullptr;
 #include "kernels_mfma_anyd_pass.inc"
 }
 
@@ -90,6 +97,28 @@ __global__ void __launch_bounds__(kAnydThreads) mfma_anyd_rowsets_kernel(AnydRow
     const float* const bias = nullptr;
     const float bias_w = 0.0f;
     const RowsetsTable* const rowsets = ra.table;
+    constexpr bool QWEIGHT = false;
+    const float* const qweight = nullptr;
+#include "kernels_mfma_anyd_pass.inc"
+}
+
+// A weight and a row set per query (ts_search_biased_rowsets): both epilogues at once, the weight of the bias term taken per
+// query from the block's table (biased_rowsets_plan.h: BiasedRowsetsTable, whose first member is the row-set table).
+struct AnydBiasedRowsetsArgs {
+    AnydArgs a;
+    const float* bias;               // [n] floats, exactly
+    const BiasedRowsetsTable* table; // device
+};
+template <bool F32, int RB>
+__global__ void __launch_bounds__(kAnydThreads) mfma_anyd_biased_rowsets_kernel(AnydBiasedRowsetsArgs ba) {
+    constexpr bool BIAS = true;
+    constexpr bool ROWSETS = true;
+    constexpr bool QWEIGHT = true;
+    const AnydArgs& aa = ba.a;
+    const float* const bias = ba.bias;
+    const float bias_w = 0.0f;
+    const RowsetsTable* const rowsets = &ba.table->r;
+    const float* const qweight = ba.table->weight;
 #include "kernels_mfma_anyd_pass.inc"
 }
 

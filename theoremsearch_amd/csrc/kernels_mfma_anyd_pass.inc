@@ -1,7 +1,7 @@
 // The general-width full pass (kernels_mfma_anyd.h), the text of the kernels' bodies: included inside mfma_anyd_kernel,
-// mfma_anyd_biased_kernel and mfma_anyd_rowsets_kernel, which define   F32, RB (template parameters), BIAS, ROWSETS (constexpr
-// bool), aa (AnydArgs), bias (const float*, read only where BIAS), bias_w (float), rowsets (const RowsetsTable*, read only where
-// ROWSETS); it declares the dynamic LDS array srows itself and uses the names of
+// mfma_anyd_biased_kernel, mfma_anyd_rowsets_kernel and mfma_anyd_biased_rowsets_kernel, which define   F32, RB (template
+// parameters), BIAS, ROWSETS, QWEIGHT (constexpr bool), aa (AnydArgs), bias (const float*, read only where BIAS), bias_w (float),
+// rowsets (const RowsetsTable*, read only where ROWSETS), qweight (const float*, read only where QWEIGHT); it declares the dynamic LDS array srows itself and uses the names of
 // kernels_mfma_anyd.h (kAnydThreads, kAnydWaves, kAnydNBW, kAnydSeg, kAnydRowPad) and kernels_mfma.h.  Text and not a function
 // template: inside a __device__ __forceinline__ function the compiler simplifies the body on its own before it inlines it, and
 // the plain kernel comes out with other block placement and register numbers (make devasm + tools/devasm_diff.py show it);
@@ -11,6 +11,8 @@
 // ROWSETS: a row set per query (ts_search_rowsets).  A lane keeps the set NUMBER of its query of each block (one register per
 // block; the pointer would be two, and this kernel's budget is the plain kernel's: 8 waves per workgroup) and takes the mask
 // pointer from the table only behind s >= thr, where a.row_mask is tested otherwise.
+// QWEIGHT (with BIAS; ts_search_biased_rowsets): the weight of the bias term is the lane's query's own, qweight[query], one
+// register per block beside qset[b], in place of the launch constant bias_w.
     extern __shared__ __attribute__((aligned(16))) unsigned char srows[];
     const MfmaArgs& a = aa.m;
     constexpr int kRows = 16 * RB;
@@ -41,6 +43,11 @@
     if constexpr (ROWSETS) {
 #pragma unroll
         for (int b = 0; b < kAnydNBW; ++b) qset[b] = rowsets->set[qid[b]];     // qid < 256: inside the table
+    }
+    float qw[QWEIGHT ? kAnydNBW : 1];
+    if constexpr (QWEIGHT) {
+#pragma unroll
+        for (int b = 0; b < kAnydNBW; ++b) qw[b] = qweight[qid[b]];            // [256], as the table's other columns
     }
 
     const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) unsigned char*)srows;
@@ -124,7 +131,10 @@
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) acc[rb][g] = fmaf(bias_w, bterm[rb][g], acc[rb][g]);
+                    for (int g = 0; g < 4; ++g) {
+                        if constexpr (QWEIGHT) acc[rb][g] = fmaf(qw[b], bterm[rb][g], acc[rb][g]);
+                        else acc[rb][g] = fmaf(bias_w, bterm[rb][g], acc[rb][g]);
+                    }
             }
             bool any = false;
 #pragma unroll

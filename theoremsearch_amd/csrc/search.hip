@@ -521,8 +521,11 @@ extern "C" int ts_search_biased_rowset(ts_index* ix, const void* queries, int q_
 // ---- ts_search_rowsets: a row set per query (rowsets_plan.h holds the rules) ---------------------------------------------------
 // The shared pass for `nq` queries that all ride it (validated, routed): search_impl's stages with a mask per query.  which[q]:
 // the set of query q.  Blocks of kRowsetsBlock queries; each block waits for its re-run list (search_mfma.hip: rowsets_rerun).
+// ts_search_biased_rowsets: the same with `bias` (device) and weights[q], the weight of query q - the biased pass with a weight per
+// query, behind one histogram of the raw bias per distinct set of these queries (made here, once, before the first block).
 static int rowsets_pass(ts_index* ix, const void* queries, int q_dtype, int q_on_device, int32_t nq, int32_t k, const ts_rowset* const* sets,
-                        const int32_t* which, float* out_scores, int64_t* out_idx, int out_on_device, void* stream, ts_rowsets_stats* stats) {
+                        const int32_t* which, float* out_scores, int64_t* out_idx, int out_on_device, void* stream, ts_rowsets_stats* stats,
+                        const float* bias = nullptr, const float* weights = nullptr) {
     std::lock_guard<std::mutex> lock(ix->mu);
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t st;
@@ -533,7 +536,7 @@ static int rowsets_pass(ts_index* ix, const void* queries, int q_dtype, int q_on
     call.sets = sets;
     struct Scope {      // the sets are properties of this call only
         ts_index* ix;
-        ~Scope() { ix->active_rowsets = nullptr; ix->active_mask = nullptr; }
+        ~Scope() { ix->active_rowsets = nullptr; ix->active_mask = nullptr; ix->active_bias = nullptr; ix->active_bias_matrix = false; }
     } call_scope{ix};
     ix->active_rowsets = &call;
     float* dscores = out_scores;
@@ -543,10 +546,24 @@ static int rowsets_pass(ts_index* ix, const void* queries, int q_dtype, int q_on
     TS_TRY(query_feed_open(&feed, ix, queries, q_dtype, q_on_device, nq, true, st));
     const int block = mfma_block_queries(ix, nq);
     if (block != kRowsetsBlock) return fail(TS_ERR_INTERNAL, "a block of the row-set pass holds %d queries, not %d", kRowsetsBlock, block);
+    std::vector<int32_t> hist_of, hist_sets;
+    if (bias) {
+        ix->active_bias = bias;
+        ix->active_bias_w = 0.0f;           // (the pass reads the table's weights; the re-run sets its class's)
+        ix->active_bias_matrix = true;
+        call.nhists = biased_rowsets_hists(which, nq, &hist_of, &hist_sets);
+        std::vector<const uint32_t*> masks(hist_sets.size());
+        for (size_t h = 0; h < hist_sets.size(); ++h) masks[h] = hist_sets[h] < 0 ? nullptr : (const uint32_t*)sets[hist_sets[h]]->mask;
+        TS_TRY(biased_rowsets_histograms(ix, masks.data(), call.nhists, st));
+    }
     for (int q0 = 0; q0 < nq; q0 += block) {
         const int nb = std::min(block, nq - q0);
         const void* qsrc = feed.at(q0);
         call.which = which + q0;
+        if (bias) {
+            call.weights = weights + q0;
+            call.hist_of = hist_of.data() + q0;
+        }
         // device queries that already are what the kernels multiply are read where they lie (search_blocks' rule)
         if (feed.on_device && feed.q_dtype == ix->dtype && ix->metric == TS_METRIC_IP && ix->ld == ix->d && nb == block && ((uintptr_t)qsrc & 15) == 0) {
             TS_TRY(mfma_search(ix, nb, k, dscores + (size_t)q0 * k, didx + (size_t)q0 * k, st, nullptr, qsrc, true));
@@ -718,6 +735,144 @@ extern "C" int ts_search_rowsets(ts_index* ix, const void* queries, int q_dtype,
                               }));
     }
     return TS_OK;
+}
+
+// ---- ts_search_biased_rowsets: a weight and a row set per query (biased_rowsets_plan.h holds the rules) -----------------------
+// one class of the call as the existing biased search runs it (ts_search_biased_rowset, or ts_search_biased_ex for set -1)
+static int biased_class_search(ts_index* ix, const void* queries, int q_dtype, int q_on_device, int32_t nq, int32_t k, const float* bias,
+                               int bias_on_device, float weight, const ts_rowset* rows, float* out_scores, float* out_sims, int64_t* out_idx,
+                               int out_on_device, void* stream, int algo, ts_search_stats* stats) {
+    BiasSpec b;
+    b.bias = bias;
+    b.on_device = bias_on_device;
+    b.weight = weight;
+    b.out_sims = out_sims;
+    b.ex = true;
+    return search_impl(ix, queries, q_dtype, q_on_device, nq, k, out_scores, out_idx, out_on_device, stream, algo, stats,
+                       rows ? (const uint32_t*)rows->mask : nullptr, rows ? 1 : 0, &b, rows ? rows->allowed : -1);
+}
+
+// out_sims of a split call, from its finished outputs: fmaf(-weights[q], bias[row], score) per entry (unbias_kernel's rule).  Host
+// outputs go through device temporaries; the stream is drained before they are freed.
+static int biased_rowsets_unbias(ts_index* ix, const float* dbias, const float* weights, int32_t nq, int32_t k, const float* out_scores,
+                                 float* out_sims, const int64_t* out_idx, int out_on_device, hipStream_t st) {
+    const size_t cnt = (size_t)nq * k;
+    DevBuf tmp;             // weights [nq] | sims [cnt] | scores [cnt] | ids [cnt] (8-byte aligned: nq + 2 cnt floats padded to even)
+    const size_t head = ((size_t)nq + 1) / 2 * 2;
+    DEV_TRY(tmp.need((head + (out_on_device ? 0 : 2 * cnt + 2 * cnt)) * 4));
+    float* dw = tmp.as<float>();
+    int rc = TS_OK;
+    auto enqueue = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(dw, weights, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+        if (out_on_device) return launch_unbias_rows(ix, out_scores, out_idx, dbias, dw, k, out_sims, (int64_t)cnt, st);
+        float* dsims = dw + head;
+        float* dscores = dsims + cnt;
+        int64_t* didx = (int64_t*)(dscores + cnt);
+        HIP_TRY(hipMemcpyAsync(dscores, out_scores, cnt * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(didx, out_idx, cnt * 8, hipMemcpyHostToDevice, st));
+        TS_TRY(launch_unbias_rows(ix, dscores, didx, dbias, dw, k, dsims, (int64_t)cnt, st));
+        HIP_TRY(hipMemcpyAsync(out_sims, dsims, cnt * 4, hipMemcpyDeviceToHost, st));
+        return TS_OK;
+    };
+    rc = enqueue();
+    const hipError_t e = hipStreamSynchronize(st);
+    if (rc == TS_OK && e != hipSuccess) rc = fail(TS_ERR_HIP, "stream synchronize failed: %s", hipGetErrorString(e));
+    return rc;
+}
+
+extern "C" int ts_search_biased_rowsets(ts_index* ix, const void* queries, int q_dtype, int q_on_device, int32_t nq, int32_t k,
+                                        const float* bias, int bias_on_device, const float* weights, const ts_rowset* const* sets,
+                                        int32_t nsets, const int32_t* which, float* out_scores, float* out_sims, int64_t* out_idx,
+                                        int out_on_device, void* stream, int algo, ts_rowsets_stats* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (const char* bad = biased_rowsets_args_invalid(queries, out_scores, out_idx, sets, which, bias, weights, q_dtype, nq, k, nsets, algo))
+        return fail(TS_ERR_INVALID, "ts_search_biased_rowsets (nq = %d, k = %d, nsets = %d): %s", nq, k, nsets, bad);
+    std::vector<RowsetsSet> info((size_t)std::max(nsets, 1));
+    for (int s = 0; s < nsets; ++s) {
+        const ts_rowset* r = sets[s];
+        info[(size_t)s] = r ? RowsetsSet{true, r->n, r->allowed, r->device} : RowsetsSet{false, 0, 0, 0};
+    }
+    if (const char* bad = rowsets_sets_invalid(info.data(), nsets, which, nq, ix != nullptr, ix ? ix->n : 0, ix ? ix->device : 0))
+        return fail(TS_ERR_INVALID, "ts_search_biased_rowsets (nq = %d, nsets = %d, index of %lld rows): %s", nq, nsets, (long long)(ix ? ix->n : 0), bad);
+    if (ix->id_map) return fail(TS_ERR_UNSUPPORTED, "ts_search_biased_rowsets: a weight and a row set per query on a subset index");
+    if (nq == 0) return TS_OK;
+    RowsetsIndex ri;
+    ri.dtype = ix->dtype;
+    ri.d = ix->d;
+    ri.n = ix->n;
+    ri.unpadded = ix->ld == ix->d;
+    ri.two_level = two_level_search(ix);
+    ri.f32_matrix = ix->knobs.get(K_MFMA_F32, 16) != 0;
+    ri.mfma_min_rows = ix->knobs.get(K_MFMA_MIN_ROWS, 16384);
+    ri.scan_max_knob = ix->knobs.get(K_SCAN_MAX_QUERIES, bias_scan_max_queries(ix->dtype));
+    const BiasedRowsetsRoute route = biased_rowsets_route(ri, info.data(), nsets, which, weights, nq, k, algo);
+    if (route.kind == kBiasedRowsetsUnsupported) return fail(TS_ERR_UNSUPPORTED, "%s", route.unsupported);
+    if (stats) stats->sets_used = route.sets_used;
+    if (route.kind == kBiasedRowsetsOneClass) {
+        ts_search_stats ss;
+        TS_TRY(biased_class_search(ix, queries, q_dtype, q_on_device, nq, k, bias, bias_on_device, route.one_weight,
+                                   route.one_set >= 0 ? sets[route.one_set] : nullptr, out_scores, out_sims, out_idx, out_on_device, stream, algo, &ss));
+        if (stats) {
+            stats->algo = ss.algo;
+            stats->scan_queries = nq;
+            stats->scan_calls = 1;
+            stats->fallback_queries = ss.fallback_queries;
+            stats->candidates = ss.candidates;
+        }
+        return TS_OK;
+    }
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t st = stream ? (hipStream_t)stream : ix->stream;
+    // a host bias goes to the device once, for the pass and every per-class call (the call's own copy: the handle's belongs to the
+    // searches below)
+    DevBuf bias_copy;
+    const float* dbias = bias;
+    if (!bias_on_device) {
+        DEV_TRY(bias_copy.need(std::max<size_t>((size_t)ix->n * 4, 4)));
+        HIP_TRY(hipMemcpyAsync(bias_copy, bias, (size_t)ix->n * 4, hipMemcpyHostToDevice, st));
+        dbias = bias_copy.as<const float>();
+    }
+    const size_t q_row_bytes = (size_t)ix->d * (q_dtype == TS_BF16 ? 2 : 4);
+    if (stats) {
+        stats->algo = route.pass.empty() ? TS_ALGO_SCAN : TS_ALGO_MFMA;
+        stats->pass_queries = (int32_t)route.pass.size();
+        stats->scan_queries = route.scan_queries();
+        stats->scan_calls = route.scan_calls();
+    }
+    // from here on every path drains the stream before `bias_copy` is freed: failures are kept in rc
+    auto run = [&]() -> int {
+        std::vector<int32_t> which_pass(route.pass.size());
+        std::vector<float> weights_pass(route.pass.size());
+        for (size_t j = 0; j < route.pass.size(); ++j) {
+            which_pass[j] = which[route.pass[j]];
+            weights_pass[j] = weights[route.pass[j]];
+        }
+        TS_TRY(rowsets_subset(ix, route.pass, queries, q_row_bytes, q_on_device, nq, k, out_scores, out_idx, out_on_device, stream,
+                              [&](const void* q, float* os, int64_t* oi) {
+                                  return rowsets_pass(ix, q, q_dtype, q_on_device, (int32_t)route.pass.size(), k, sets, which_pass.data(), os, oi,
+                                                      out_on_device, stream, stats, dbias, weights_pass.data());
+                              }));
+        for (const BiasedRowsetsGroup& g : route.groups) {
+            if (g.empty) {
+                TS_TRY(rowsets_padding(ix, g.queries, k, out_scores, out_idx, out_on_device, stream));
+                continue;
+            }
+            const ts_rowset* one = g.set >= 0 ? sets[g.set] : nullptr;
+            TS_TRY(rowsets_subset(ix, g.queries, queries, q_row_bytes, q_on_device, nq, k, out_scores, out_idx, out_on_device, stream,
+                                  [&](const void* q, float* os, int64_t* oi) {
+                                      return biased_class_search(ix, q, q_dtype, q_on_device, (int32_t)g.queries.size(), k, dbias, 1, g.weight, one,
+                                                                 os, nullptr, oi, out_on_device, stream, route.group_algo, nullptr);
+                                  }));
+        }
+        if (out_sims) TS_TRY(biased_rowsets_unbias(ix, dbias, weights, nq, k, out_scores, out_sims, out_idx, out_on_device, st));
+        return TS_OK;
+    };
+    int rc = run();
+    if (!bias_on_device) {
+        const hipError_t e = hipStreamSynchronize(st);
+        if (rc == TS_OK && e != hipSuccess) rc = fail(TS_ERR_HIP, "stream synchronize failed: %s", hipGetErrorString(e));
+    }
+    return rc;
 }
 
 template <int DT, int CH, int G>

@@ -4,7 +4,9 @@
 // mfma_sample (level 0 as the dense sample) or mfma_level (a matrix kernel + its select).  A biased search (ts_search_biased_ex)
 // is the general-width form of all this at any served width, with its own sample select (kernels_sample_biased.h).  A search with
 // a row set per query (ts_search_rowsets: ix->active_rowsets) is that form too, with the row-set kernels of
-// launch_mfma_anyd_rowsets.hip, a table per block of queries (rowsets_table) and a re-run per set (rowsets_rerun).
+// launch_mfma_anyd_rowsets.hip, a table per block of queries (rowsets_table) and a re-run per set (rowsets_rerun).  Both at once
+// (ts_search_biased_rowsets: a weight per query in the block's table) is that form with the biased row-set pass, a histogram of the
+// raw bias per set (biased_rowsets_histograms), the sample select that reads it through the query's weight, and a re-run per class.
 //
 // What the plan fixes, as tests/threshold_common.py restates it and tests/test_threshold_gpu.py observes it: level i visits
 // tiles j * stride_i, so the sample is the rows 32 j stride + r (r < 32) below n - a partial last tile gives its real rows
@@ -19,6 +21,7 @@
 #include "kernels_mfma_f32.h"
 #include "kernels_sample.h"
 #include "kernels_sample_biased.h"
+#include "kernels_biased_rowsets.h"
 #include "kernels_level.h"
 
 struct Level { int64_t stride, ntiles; int run; };
@@ -164,6 +167,74 @@ int bias_histogram(ts_index* ix, hipStream_t st) {
     bias_range_kernel<<<grid, 256, 0, st>>>(a);
     HIP_TRY(hipGetLastError());
     bias_hist_kernel<<<grid, 256, 0, st>>>(a);
+    HIP_TRY(hipGetLastError());
+    return TS_OK;
+}
+
+// ts_search_biased_rowsets (a weight and a row set per query; kernels_biased_rowsets.h).
+// Once per call: the range of the raw bias over all rows, then one histogram per entry of `masks` (NULL = every row) into
+// ix->bias_sets_hist: [nhists][kBiasBins] counts, then the two range words.
+int biased_rowsets_histograms(ts_index* ix, const uint32_t* const* masks, int nhists, hipStream_t st) {
+    if (nhists < 1 || nhists > kRowsetsBlock + 1) return fail(TS_ERR_INTERNAL, "%d histograms of the raw bias", nhists);
+    if (!ix->active_bias) return fail(TS_ERR_INTERNAL, "the histograms need the call's bias on the device");
+    const size_t words = (size_t)nhists * kBiasBins + 2;
+    DEV_TRY(ix->bias_sets_hist.need(words * 4));
+    HIP_TRY(hipMemsetAsync(ix->bias_sets_hist, 0, words * 4, st));
+    u32* hists = ix->bias_sets_hist;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)ix->cu_count * 4, (ix->n + 255) / 256));
+    // bias_range_kernel writes its two words behind kBiasBins counters: handed the LAST histogram, they land behind them all
+    BiasHistArgs ra;
+    ra.bias = ix->active_bias;
+    ra.w = 1.0f;
+    ra.n = ix->n;
+    ra.row_mask = nullptr;
+    ra.out = hists + (size_t)(nhists - 1) * kBiasBins;
+    bias_range_kernel<<<grid, 256, 0, st>>>(ra);
+    HIP_TRY(hipGetLastError());
+    for (int h0 = 0; h0 < nhists; h0 += kBiasedRowsetsHistGroup) {
+        BiasHistSetsArgs a;
+        memset(&a, 0, sizeof(a));
+        a.bias = ix->active_bias;
+        a.n = ix->n;
+        a.nsets = std::min(kBiasedRowsetsHistGroup, nhists - h0);
+        for (int s = 0; s < a.nsets; ++s) a.mask[s] = masks[h0 + s];
+        a.range = hists + (size_t)nhists * kBiasBins;
+        a.out = hists + (size_t)h0 * kBiasBins;
+        TS_TRY((launch_lds<bias_hist_sets_kernel, kBiasedRowsetsHistGroup * kBiasBins * 4>(ix->device, grid, 256, a.nsets * kBiasBins * 4, st, a)));
+    }
+    return TS_OK;
+}
+
+int launch_sample_select_biased_rowsets(const ts_index* ix, int nq, int kk, int nhists, double target, const float* scores, int row_stride,
+                                        int64_t ntiles, int64_t tile_stride, int run, hipStream_t st) {
+    if (!ix->rowsets_dev || ix->rowsets_dev.bytes() < sizeof(BiasedRowsetsTable) || !ix->active_bias)
+        return fail(TS_ERR_INTERNAL, "the biased row-set sample select needs the block's table and the call's bias on the device");
+    if (nq > kRowsetsBlock) return fail(TS_ERR_INTERNAL, "a block of the biased row-set pass holds %d queries", kRowsetsBlock);
+    if (nhists < 1 || !ix->bias_sets_hist || ix->bias_sets_hist.bytes() < ((size_t)nhists * kBiasBins + 2) * 4)
+        return fail(TS_ERR_INTERNAL, "the biased row-set sample select needs the call's %d histograms", nhists);
+    BiasRowsetsSelectArgs b;
+    memset(&b, 0, sizeof(b));
+    b.scores = scores;
+    b.row_stride = row_stride;
+    b.ntiles = ntiles;
+    b.tile_stride = tile_stride;
+    b.run = run;
+    b.bias = ix->active_bias;
+    b.table = ix->rowsets_dev.as<const BiasedRowsetsTable>();
+    b.kk = kk;
+    b.hists = ix->bias_sets_hist;
+    b.range = ix->bias_sets_hist.as<const u32>() + (size_t)nhists * kBiasBins;
+    b.target = target;
+    b.thr = ix->thr;
+    b.count = ix->count;
+    if (kk <= 64) return launch_lds<sample_select_biased_rowsets_kernel<1>>(ix->device, nq, kLevelThreads, kBiasSelectLds, st, b);
+    return launch_lds<sample_select_biased_rowsets_kernel<4>>(ix->device, nq, kLevelThreads, kBiasSelectLds, st, b);
+}
+
+int launch_unbias_rows(const ts_index* ix, const float* scores, const int64_t* idx, const float* bias, const float* weights, int k, float* sims,
+                       int64_t count, hipStream_t st) {
+    if (count <= 0) return TS_OK;
+    unbias_rows_kernel<<<(unsigned)((count + 255) / 256), 256, 0, st>>>(scores, idx, bias, weights, k, ix->row_offset, sims, count);
     HIP_TRY(hipGetLastError());
     return TS_OK;
 }
@@ -361,6 +432,9 @@ static int mfma_sample(ts_index* ix, const MfmaPlan& p, int nq, const void* qmat
     const int kl = p.tail_p > 0.0f ? std::max(p.kk, 32) : p.kk;
     const double live = p.sample_rows * (double)p.pop / (double)std::max<int64_t>(ix->n, 1);
     const float z_sel = (float)normal_tail_z(std::min(0.25, 2.0 * kl / std::max(live, 1.0)));
+    if (p.biased && p.rowsets)           // ... with the query's own weight and its set's histogram of the raw bias
+        return launch_sample_select_biased_rowsets(ix, nq, p.kk, ix->active_rowsets->nhists, (double)p.stat_cands, ix->sample, sa.row_stride,
+                                                   lv0.ntiles, lv0.stride, lv0.run, st);
     if (p.biased) {
         // the weighted scores are not Gaussian: the select models the similarities and the known term apart (bias_plan.h)
         BiasSelectArgs b;
@@ -495,7 +569,8 @@ static int mfma_level(ts_index* ix, const MfmaPlan& p, size_t i, int nq, int k, 
     if (p.anyd && !full_pass) return fail(TS_ERR_INTERNAL, "the general-width matrix kernel has no sparse level");
     hipEvent_t stop = full_pass ? prof_begin(ix, st, ix->n) : nullptr;  // only the full pass is bracketed
     int rc;
-    if (p.rowsets) rc = launch_pass_mfma_anyd_rowsets(ix, p.grid, st, a);
+    if (p.rowsets && p.biased) rc = launch_pass_mfma_anyd_biased_rowsets(ix, p.grid, st, a);
+    else if (p.rowsets) rc = launch_pass_mfma_anyd_rowsets(ix, p.grid, st, a);
     else if (p.wide) rc = p.biased ? launch_pass_mfma_wide_biased(ix, p.grid, st, a) : launch_pass_mfma_wide(ix, p.grid, st, a);
     else if (p.biased) rc = launch_pass_mfma_anyd_biased(ix, p.grid, st, a);
     else if (p.anyd) rc = launch_pass_mfma_anyd(ix, p.grid, st, a);
@@ -545,12 +620,16 @@ static int mfma_level(ts_index* ix, const MfmaPlan& p, size_t i, int nq, int k, 
 // ts_search_rowsets: the block's table (rowsets_plan.h: RowsetsTable) from the call's sets and this plan, made on the host and
 // uploaded before the block's first launch.  The host copy is the handle's: the previous block's upload has run (every block
 // ends by waiting for its re-run list).
+// (one layout for both entries: the table of ts_search_biased_rowsets begins with ts_search_rowsets' and adds the weights)
+constexpr size_t kRowsetsTableBytes = sizeof(BiasedRowsetsTable);
+static_assert(offsetof(BiasedRowsetsTable, r) == 0, "the row-set kernels read the biased table's first member");
 static int rowsets_table(ts_index* ix, const MfmaPlan& p, int nq, int k, hipStream_t st) {
     const RowsetsCall& call = *ix->active_rowsets;
-    constexpr size_t kBytes = sizeof(RowsetsTable) + 2 * kRowsetsBlock * sizeof(int);
+    constexpr size_t kBytes = kRowsetsTableBytes + 2 * kRowsetsBlock * sizeof(int);
     DEV_TRY(ix->rowsets_dev.need(kBytes));
     ix->rowsets_host.resize(kBytes);
-    RowsetsTable* t = reinterpret_cast<RowsetsTable*>(ix->rowsets_host.data());
+    BiasedRowsetsTable* bt = reinterpret_cast<BiasedRowsetsTable*>(ix->rowsets_host.data());
+    RowsetsTable* t = &bt->r;
     const bool estimate = p.statistical && p.lv.size() == 2;
     const bool tail_fit = ix->knobs.get(K_MFMA_TAIL_FIT, 1) != 0;
     for (int s = 0; s < kRowsetsBlock; ++s) t->mask[s] = nullptr;
@@ -564,8 +643,10 @@ static int rowsets_table(ts_index* ix, const MfmaPlan& p, int nq, int k, hipStre
         t->min_fill[q] = num.min_fill;
         t->z_sel[q] = rowsets_z_sel(pop, ix->n, p.kk, num.tail_p, p.sample_rows);
         t->set[q] = s;
+        bt->weight[q] = (call.weights && q < nq) ? call.weights[q] : 0.0f;
+        bt->hist[q] = (call.hist_of && q < nq) ? call.hist_of[q] : 0;
     }
-    HIP_TRY(hipMemcpyAsync(ix->rowsets_dev, t, sizeof(RowsetsTable), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ix->rowsets_dev, bt, kRowsetsTableBytes, hipMemcpyHostToDevice, st));
     return TS_OK;
 }
 
@@ -586,16 +667,21 @@ static int rowsets_rerun(ts_index* ix, int nq, int k, float* out_scores, int64_t
     if (fb == 0) return TS_OK;
     for (int i = 0; i < fb; ++i)
         if (list[i] < 0 || list[i] >= nq) return fail(TS_ERR_INTERNAL, "the re-run list of a row-set pass names query %d of %d", list[i], nq);
-    std::stable_sort(list.begin(), list.begin() + fb, [&](int x, int y) { return call.which[x] < call.which[y]; });
+    // (under a weight per query: by class, set then weight - the scan's weight is one per launch)
+    auto weight_of = [&](int q) { return call.weights ? call.weights[q] : 0.0f; };
+    auto same_class = [&](int x, int y) { return biased_rowsets_same_class(call.which[x], weight_of(x), call.which[y], weight_of(y)); };
+    std::stable_sort(list.begin(), list.begin() + fb, [&](int x, int y) {
+        return call.which[x] != call.which[y] ? call.which[x] < call.which[y] : weight_of(x) < weight_of(y);
+    });
     // lists [256] | counts [256] behind the table, both in the handle's host copy
-    int* hl = reinterpret_cast<int*>(ix->rowsets_host.data() + sizeof(RowsetsTable));
+    int* hl = reinterpret_cast<int*>(ix->rowsets_host.data() + kRowsetsTableBytes);
     int* hc = hl + kRowsetsBlock;
-    int* dl = reinterpret_cast<int*>(ix->rowsets_dev.as<unsigned char>() + sizeof(RowsetsTable));
+    int* dl = reinterpret_cast<int*>(ix->rowsets_dev.as<unsigned char>() + kRowsetsTableBytes);
     int* dc = dl + kRowsetsBlock;
     int ngroups = 0;
     for (int i = 0; i < fb; ++i) {
         hl[i] = list[i];
-        if (i == 0 || call.which[list[i]] != call.which[list[i - 1]]) hc[ngroups++] = 0;
+        if (i == 0 || !same_class(list[i], list[i - 1])) hc[ngroups++] = 0;
         ++hc[ngroups - 1];
     }
     HIP_TRY(hipMemcpyAsync(dl, hl, (size_t)fb * 4, hipMemcpyHostToDevice, st));
@@ -604,6 +690,7 @@ static int rowsets_rerun(ts_index* ix, int nq, int k, float* out_scores, int64_t
     for (int g = 0, at = 0; g < ngroups && rc == TS_OK; at += hc[g], ++g) {
         const int32_t s = call.which[hl[at]];
         ix->active_mask = s < 0 ? nullptr : (const u32*)call.sets[s]->mask;
+        if (call.weights) ix->active_bias_w = call.weights[hl[at]];
         if (!in_place) rc = scan_search(ix, nq, k, out_scores, out_idx, dl + at, dc + g, st);
         else if (ix->dtype == TS_F32) rc = scan_search(ix, nq, k, out_scores, out_idx, dl + at, dc + g, st, (const float*)qmat);
         else rc = scan_search(ix, nq, k, out_scores, out_idx, dl + at, dc + g, st, nullptr, (const unsigned short*)qmat);

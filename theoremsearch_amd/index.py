@@ -329,6 +329,55 @@ class TheoremIndex:
                                                _ALGOS[algo], C.byref(stats)))
         return self._rowsets_stats(stats)
 
+    # -- a weight and a row set per query ---------------------------------------------------
+    @staticmethod
+    def _weights_arg(weights, nq):
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+        if w.shape[0] != nq:
+            raise ValueError(f"weights has {w.shape[0]} entries for {nq} queries")
+        return w
+
+    def search_biased_rowsets(self, queries, k: int, bias, weights, rowsets, which, algo: str = "auto", return_stats: bool = False):
+        """`search_biased` with a weight and a row set per query (``ts_search_biased_rowsets``): query ``i`` is ranked by
+        ``score + weights[i] * bias[row]`` over the rows ``rowsets[which[i]]`` allows (all rows where ``which[i] == -1``).
+        ``bias``: float32 per row of this index, one array for the call; ``weights``: one finite float per query; ``rowsets`` /
+        ``which``: as for `search_rowsets`.  Each output row is what `search_biased` returns for that query alone with its weight
+        and ``mask=`` its set; a batch whose queries differ in filter or weight crosses the corpus once.  Returns ``(weighted
+        scores, raw similarities, indices)`` and, with ``return_stats``, the routing's counters (those of `search_rowsets`)."""
+        if self._cpu_rows is not None:
+            raise ValueError("the host-only index (device=-1) has one algorithm and no filters")
+        q = _host_rows(queries)
+        if q.shape[1] != self.d:
+            raise ValueError(f"queries have d={q.shape[1]}, index has d={self.d}")
+        b = np.ascontiguousarray(np.asarray(bias, dtype=np.float32).reshape(-1))
+        if b.shape[0] != self.n:
+            raise ValueError(f"bias has {b.shape[0]} entries, index has {self.n} rows")
+        nq, k = q.shape[0], int(k)
+        rowsets, handles, w = self._rowsets_args(rowsets, which, nq)
+        wt = self._weights_arg(weights, nq)
+        scores = np.empty((nq, max(k, 0)), dtype=np.float32)
+        sims = np.empty((nq, max(k, 0)), dtype=np.float32)
+        idx = np.empty((nq, max(k, 0)), dtype=np.int64)
+        stats = _ffi.RowsetsStats()
+        _ffi.check(self._lib.ts_search_biased_rowsets(self._h, _ffi.as_ptr(q), _ffi.np_dtype_code(q), 0, nq, k, _ffi.as_ptr(b), 0,
+                                                      _ffi.as_ptr(wt), handles, len(rowsets), _ffi.as_ptr(w), _ffi.as_ptr(scores),
+                                                      _ffi.as_ptr(sims), _ffi.as_ptr(idx), 0, None, _ALGOS[algo], C.byref(stats)))
+        return (scores, sims, idx, self._rowsets_stats(stats)) if return_stats else (scores, sims, idx)
+
+    def search_biased_rowsets_device(self, q_ptr: int, q_dtype: str, nq: int, k: int, bias_ptr: int, weights, rowsets, which,
+                                     out_scores_ptr: int, out_sims_ptr: int, out_idx_ptr: int, stream: int = 0, algo: str = "auto") -> dict:
+        """`search_biased_rowsets` on device buffers (queries [nq x d] dense; bias float32 [n]; outputs [nq x k] f32 / f32 / i64,
+        ``out_sims_ptr`` may be 0) on ``stream`` (0 = the index's own); ``weights`` and ``which`` stay host arrays.  Like
+        `search_rowsets_device` the call WAITS for its pass and returns the routing's counters."""
+        rowsets, handles, w = self._rowsets_args(rowsets, which, int(nq))
+        wt = self._weights_arg(weights, int(nq))
+        stats = _ffi.RowsetsStats()
+        _ffi.check(self._lib.ts_search_biased_rowsets(self._h, C.c_void_p(q_ptr), _DTYPES[q_dtype], 1, int(nq), int(k), C.c_void_p(bias_ptr),
+                                                      1, _ffi.as_ptr(wt), handles, len(rowsets), _ffi.as_ptr(w), C.c_void_p(out_scores_ptr),
+                                                      C.c_void_p(out_sims_ptr) if out_sims_ptr else None, C.c_void_p(out_idx_ptr), 1,
+                                                      C.c_void_p(stream), _ALGOS[algo], C.byref(stats)))
+        return self._rowsets_stats(stats)
+
     # -- grouped search ---------------------------------------------------------------------
     @staticmethod
     def _group_column(meta, column) -> int:

@@ -177,12 +177,15 @@ def search_batch(index: TheoremIndex, query_vecs, top_k: int, citation_weight: f
     return out
 
 
-def search_sessions(index: TheoremIndex, query_vecs, top_ks, masks):
-    """The plain queries (citation weight 0) of many sessions in one call: session ``i`` asks for its ``top_ks[i]`` best rows
+def search_sessions(index: TheoremIndex, query_vecs, top_ks, masks, citation_weights=None, citations=None, bias=None):
+    """The queries of many sessions in one call; without ``citation_weights`` the plain queries (citation weight 0): session ``i`` asks for its ``top_ks[i]`` best rows
     behind ``masks[i]``, a `metadata.RowSet` or None (`MetaTable.eval_many` makes them, shared between sessions with the same
     sidebar state).  One `TheoremIndex.search_rowsets` at ``max(top_ks)`` - sessions behind different dense filters share one
     pass over the corpus - and each list cut to its own ``top_k``: a prefix of the canonical top k is the top k of the smaller
-    k.  Returns one list per session, each shaped like the result of `search`."""
+    k.  Returns one list per session, each shaped like the result of `search`.
+    ``citation_weights`` (one per session, with ``citations`` or a ready-made ``bias``): the sessions' slider values - one
+    `TheoremIndex.search_biased_rowsets` at ``max(top_ks)``, sessions with weight 0 included; session ``i``'s list is that of
+    ``search(..., citation_weight=w_i, exact=True, mask=masks[i])``."""
     q = np.asarray(query_vecs, dtype=np.float32)
     q = q.reshape(1, -1) if q.ndim == 1 else q
     top_ks = [int(t) for t in top_ks]
@@ -202,6 +205,27 @@ def search_sessions(index: TheoremIndex, query_vecs, top_ks, masks):
             number[id(m)] = len(rowsets)
             rowsets.append(m)
         which.append(number[id(m)])
+    if citation_weights is not None:
+        ws = [float(w) for w in citation_weights]
+        if len(ws) != q.shape[0]:
+            raise ValueError(f"{q.shape[0]} queries and {len(ws)} citation_weights")
+        if citations is None and bias is None:
+            raise ValueError("citation-weighted search needs the per-row citation counts")
+        b = citation_bias(citations) if bias is None else np.asarray(bias, dtype=np.float32)
+        _, sims, idx = index.search_biased_rowsets(q, max(top_ks), b, ws, rowsets, np.asarray(which, dtype=np.int32))
+        out = []
+        for srow, irow, k, w in zip(sims, idx, top_ks, ws):
+            rows = []
+            for s, i in zip(srow[:k], irow[:k]):
+                if i < 0:
+                    continue
+                sim = 1.0 + float(s)
+                rows.append({"row": int(i), "similarity": sim,
+                             "score": sim + w * float(b[int(i) - index.row_offset]) if w != 0.0 else sim})
+            if w != 0.0:
+                rows.sort(key=lambda r: (-r["score"], -r["similarity"]))
+            out.append(rows)
+        return out
     scores, idx = index.search_rowsets(q, max(top_ks), rowsets, np.asarray(which, dtype=np.int32))
     return [[{"row": int(i), "similarity": 1.0 + float(s), "score": 1.0 + float(s)} for s, i in zip(srow[:k], irow[:k]) if i >= 0]
             for srow, irow, k in zip(scores, idx, top_ks)]
